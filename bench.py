@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the MI-critic hot path: one critic forward + backward over a synthetic batch per step.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
       N > 1: either launched by torch.distributed.run (one rank per GPU; RANK / LOCAL_RANK / WORLD_SIZE from the
       environment) or, when WORLD_SIZE is not set, bench.py starts the N ranks itself as child processes and relays
       rank 0's line; --gpus must equal the number of ranks, anything else is an error
+      --dump-outputs DIR: after the K timed steps of the headline, what its last step handed back (loss, dX, dY and the
+      critic's parameter gradients) goes to DIR/<name>.npy, so that two builds can be compared output for output on the
+      same seeded inputs
 
 Headline workload (BASELINE.json configs[3], the configuration its metric is quoted on; it fits one GPU):
   global-batch "InfoNCE" (reference semantics, mi_critics.py:14-23), bilinear critic S = (X W) Y^T, B_global = 4096,
@@ -60,6 +63,8 @@ PEAK_HBM_GBS = 8000.0
 # the modes that hold the fp32 tolerances
 SECONDARY_FAST = {"concat_mlp": ["f16", "bf16"]}
 SECONDARY_PARITY = ["f32", "f32_exact"]  # "f32" = the two-part fp16 scheme (MI_PREC_F16X3); "f32_exact" = fp32-input MFMA
+# --dump-outputs: array bytes of one dump at most (the .npy headers stay well inside the 64 MB a dump may take)
+DUMP_BYTES = 60 * 10**6
 
 
 def parse_args():
@@ -97,7 +102,15 @@ def parse_args():
     p.add_argument("--rendezvous-only", action="store_true",
                    help="start the ranks, form the process group (backend: MI_BENCH_BACKEND, default nccl), all-reduce one "
                         "number and print {world, sum}: the launcher's own test (runs under gloo without a GPU)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the outputs of the headline's last timed step to DIR/<name>.npy (float32): loss, grad_x, "
+                        "grad_y (whole global batch) and grad_param<i> (the critic's parameters in C-ABI order); beyond "
+                        f"{DUMP_BYTES // 10**6} MB in all, every array keeps the same share of its rows, picked by a "
+                        "fixed seed")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def launch_ranks(args):
@@ -286,6 +299,37 @@ class Stepper:
     def loss(self):
         o = self.step_obj
         return float((o.loss if self.dist_mode else o.loss_buf).detach().float().sum().item())
+
+    def host_outputs(self):
+        """What the last step handed its caller, as float32 host tensors: the loss, dX, dY and the gradients of the
+        critic's parameters.  With several ranks the row blocks of dX and dY are gathered in rank order (a collective:
+        every rank calls this), so the arrays are those of the whole global batch."""
+        o = self.step_obj
+        out = {"loss": (o.loss if self.dist_mode else o.loss_buf).reshape(-1), "grad_x": o.grad_x, "grad_y": o.grad_y}
+        if self.dist_mode:
+            for k in ("grad_x", "grad_y"):
+                parts = [torch.empty_like(out[k]) for _ in range(self.world)]
+                dist.all_gather(parts, out[k].contiguous())
+                out[k] = torch.cat(parts)
+        for i, g in enumerate(o.grad_params):
+            out[f"grad_param{i}"] = g
+        return {k: v.detach().to("cpu", torch.float32) for k, v in out.items()}
+
+
+def dump_outputs(outputs, out_dir, budget=DUMP_BYTES):
+    """``outputs`` (name -> float32 host tensor) as ``out_dir/<name>.npy``.  Beyond ``budget`` bytes in all, every array
+    of more than one row keeps the same share of its rows; the rows are drawn from a fixed seed and kept in order, so two
+    runs of the same shapes keep the same rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.numpy() for k, v in outputs.items()}
+    fixed = sum(a.nbytes for a in arrays.values() if a.ndim == 0 or a.shape[0] <= 1)
+    rows_bytes = sum(a.nbytes for a in arrays.values()) - fixed
+    for name, a in arrays.items():
+        if fixed + rows_bytes > budget and a.ndim and a.shape[0] > 1:
+            keep = max(1, a.shape[0] * (budget - fixed) // rows_bytes)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def clock_warmup(stepper, budget_s, world):
@@ -595,7 +639,7 @@ def main():
     b, d, br = args.batch, args.dim, args.batch // world
 
     def run(kind, steps, warmup, precision=None, timed_iters=0, batch=None, dim=None, clock_ms=None, cold_first=False,
-            boundary="f32", probe=True):
+            boundary="f32", probe=True, keep_outputs=False):
         st = Stepper(kind, args, rank, world, device, group, precision=precision, graph=want_graph and probe, batch=batch,
                      dim=dim, boundary=boundary)
         if args.graph == "auto" and probe:
@@ -604,6 +648,7 @@ def main():
         st.cold_elapsed = timed_run(st, steps, warmup, world) if cold_first else None
         st.clock_warmup_steps = clock_warmup(st, (args.clock_warmup_ms if clock_ms is None else clock_ms) * 1e-3, world)
         elapsed = timed_run(st, steps, warmup, world)
+        st.outputs = st.host_outputs() if keep_outputs else None  # (after the timed region: the later steps overwrite them)
         timing = timing_summary(st, timed_iters) if timed_iters else None
         kernels = profile_kernels(st, args.profile_steps)
         return st, elapsed, kernels, timing
@@ -612,7 +657,9 @@ def main():
     boundary = args.boundary if (args.critic == "bilinear" and args.precision == "bf16" and world == 1 and
                                  not os.environ.get("MI_BENCH_FORCE_DIST")) else "f32"
     st, elapsed, kernels, timing = run(args.critic, args.steps, args.warmup, timed_iters=args.timed_iters, cold_first=True,
-                                       boundary=boundary)
+                                       boundary=boundary, keep_outputs=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(st.outputs, args.dump_outputs)
     ms = elapsed / args.steps * 1e3
     cold_ms = st.cold_elapsed / args.steps * 1e3
     flops = algorithmic_flops(args.critic, b, d, d)

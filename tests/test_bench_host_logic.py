@@ -57,3 +57,56 @@ def test_cpu_leg_thread_count(monkeypatch):
     assert 1 <= n <= min(len(os.sched_getaffinity(0)), 16) or n <= len(os.sched_getaffinity(0))
     monkeypatch.setenv("MI_BENCH_CPU_THREADS", "3")
     assert bench.host_cpu_share() == 3
+
+
+def test_dump_outputs_of_the_last_step(tmp_path):
+    """`--dump-outputs DIR`: the step's outputs as float32 .npy files under their names (bf16 gradients widened, the loss
+    as one element); below the budget every value is written."""
+    import types
+
+    import numpy as np
+    import torch
+    gx = torch.randn(64, 8, generator=torch.Generator().manual_seed(1))
+    step_obj = types.SimpleNamespace(loss_buf=torch.tensor([1.25]), grad_x=gx.bfloat16(), grad_y=gx * 2,
+                                     grad_params=[torch.ones(8, 8), torch.zeros(8)])
+    st = object.__new__(bench.Stepper)
+    st.step_obj, st.dist_mode, st.world = step_obj, False, 1
+    outs = st.host_outputs()
+    assert sorted(outs) == ["grad_param0", "grad_param1", "grad_x", "grad_y", "loss"]
+    bench.dump_outputs(outs, str(tmp_path / "d"))
+    got = {p.stem: np.load(p) for p in (tmp_path / "d").glob("*.npy")}
+    assert sorted(got) == sorted(outs) and all(a.dtype == np.float32 for a in got.values())
+    assert got["loss"].tolist() == [1.25]
+    np.testing.assert_array_equal(got["grad_x"], gx.bfloat16().float().numpy())
+    np.testing.assert_array_equal(got["grad_y"], (gx * 2).numpy())
+    assert got["grad_param1"].shape == (8,)
+
+
+def test_dump_outputs_sample_a_large_step(tmp_path):
+    """Beyond the budget every multi-row array keeps the same share of its rows, the same rows on every run."""
+    import numpy as np
+    import torch
+    outs = {"loss": torch.tensor([0.5]), "grad_x": torch.arange(4000 * 16, dtype=torch.float32).reshape(4000, 16),
+            "grad_param0": torch.arange(1000 * 16, dtype=torch.float32).reshape(1000, 16)}
+    budget = 100_000
+    for run in ("a", "b"):
+        bench.dump_outputs(outs, str(tmp_path / run), budget=budget)
+    a = {p.stem: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    b = {p.stem: np.load(p) for p in (tmp_path / "b").glob("*.npy")}
+    assert sum(v.nbytes for v in a.values()) <= budget
+    assert a["loss"].tolist() == [0.5] and a["grad_param0"].shape[0] > 0
+    assert abs(a["grad_x"].shape[0] / 4000 - a["grad_param0"].shape[0] / 1000) < 1e-3  # the same share (up to a row)
+    for name, v in a.items():
+        np.testing.assert_array_equal(v, b[name])
+    rows = a["grad_x"][:, 0] / 16  # the sampled rows are whole rows of the output, in order
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a["grad_x"], outs["grad_x"].numpy()[rows.astype(int)])
+
+
+def test_steps_must_be_positive(monkeypatch):
+    """`ms_per_step` divides by --steps: a run of no timed steps is refused at the command line."""
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse_args()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "7", "--warmup", "0", "--dump-outputs", "out"])
+    args = bench.parse_args()
+    assert args.steps == 7 and args.dump_outputs == "out"
