@@ -15,6 +15,9 @@
  *   mi_bilinear_*         <- same call site with the bilinear critic S = (X W) Y^T named by BASELINE.json
  *                            (an extension: the reference has no bilinear critic; the bound, the masking and the
  *                            pair semantics applied to its scores are the reference's)
+ *   mi_nce_*, mi_matrix_nce_* <- an extension: the per-sample (CPC / ConVIRT / CLIP) InfoNCE on the bilinear and
+ *                            separable critics and on materialised scores, with the reference's masking rule
+ *                            (main_utils.py:105); the reference has no such loss
  *
  * Conventions
  *   - every pointer is a DEVICE pointer unless the name ends in _host; all tensors are dense row-major
@@ -274,6 +277,41 @@ int mi_concat_mlp_bwd(const float* x, const float* y, const float* w1, const flo
  * rank order; writes the global stats and loss.  Merging in rank order makes every rank compute identical bits. */
 int mi_merge_partials(const float* partials, int64_t n_ranks, int64_t n_pos_global, int estimator,
                       float* loss_out, mi_stats* stats, void* stream);
+
+/* ---- per-sample InfoNCE (row-wise and symmetric image-report contrastive loss) ----------------------- */
+/* Scores S[i,j] = critic(img_i, txt_j) over a batch of b; a pair i != j with equal study ids is dropped.
+ *   r_i = log sum_{j in C_i} exp S[i,j],  C_i = {i} u {j : sid_j != sid_i}      (row LSE, lse_rows)
+ *   c_j = log sum_{i in R_j} exp S[i,j],  R_j = {j} u {i : sid_i != sid_j}      (column LSE, lse_cols)
+ *   MI_NCE_ROWWISE:   loss = (1/b) sum_i (r_i - S[i,i])                        (image -> report cross-entropy)
+ *   MI_NCE_SYMMETRIC: loss = 1/2 (1/b) sum_i (r_i - S[i,i]) + 1/2 (1/b) sum_j (c_j - S[j,j])
+ * A row whose only candidate is its own positive contributes 0 (a batch without negatives gives loss 0).  Not the
+ * reference's "infonce" estimator (MI_INFONCE: one LSE over every negative pair): a separate family of entry points whose
+ * `mode` codes are not estimator codes.  Deterministic: partial records merged in a fixed order, no float atomics.
+ * precision: MI_PREC_BF16 / MI_PREC_BF16X3 run the 16-bit GEMM chain where b and the widths are multiples of 8, every
+ * other shape and MI_PREC_F32 the generic kernels; MI_PREC_FP8 / F16 / F16X3 are rejected (MI_EINVAL).
+ * grad_out may be NULL (dL/dloss = 1); lse_rows / lse_cols ([b], optional) receive r and c. */
+#define MI_NCE_ROWWISE 0
+#define MI_NCE_SYMMETRIC 1
+/* S = (X W) Y^T, or S = X Y^T when w == NULL (projected embeddings, d_img == d_txt).  grad_x, grad_y (and grad_w when
+ * w != NULL) all NULL: forward only, no backward launches; otherwise all of them are written. */
+size_t mi_nce_bilinear_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int precision);
+int mi_nce_bilinear_step(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t d_img,
+                         int64_t d_txt, int mode, int precision, const float* grad_out, float* loss_out, float* lse_rows,
+                         float* lse_cols, float* grad_x, float* grad_y, float* grad_w, void* workspace,
+                         size_t workspace_bytes, void* stream);
+/* S = (X Wg)(Y Wh)^T; wg [d_img, d_proj], wh [d_txt, d_proj].  The four gradients all NULL: forward only. */
+size_t mi_nce_separable_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int precision);
+int mi_nce_separable_step(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid, int64_t b,
+                          int64_t d_img, int64_t d_txt, int64_t d_proj, int mode, int precision, const float* grad_out,
+                          float* loss_out, float* lse_rows, float* lse_cols, float* grad_x, float* grad_y,
+                          float* grad_wg, float* grad_wh, void* workspace, size_t workspace_bytes, void* stream);
+/* on a caller's fp32 [b, b] score matrix (any critic): forward writes loss_out[0] and the optional lse_rows / lse_cols;
+ * backward reads lse_rows (and lse_cols in the symmetric mode) and writes grad_scores = grad_out[0] * dloss/dS */
+size_t mi_matrix_nce_workspace_bytes(int64_t b);
+int mi_matrix_nce_fwd(const float* scores, const int64_t* sid, int64_t b, int mode, float* loss_out, float* lse_rows,
+                      float* lse_cols, void* workspace, size_t workspace_bytes, void* stream);
+int mi_matrix_nce_bwd(const float* scores, const int64_t* sid, int64_t b, int mode, const float* lse_rows,
+                      const float* lse_cols, const float* grad_out, float* grad_scores, void* stream);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,7 @@
 #include "mi_bilinear_flash.h"
 #include "mi_bilinear_tail.h"
 #include "mi_fp8.h"
+#include "mi_nce.h"
 
 namespace mi {
 
@@ -85,7 +86,9 @@ static bool fast_ok(int64_t br, int64_t b, int64_t dx, int64_t dy, int precision
          dx % 8 == 0 && dy % 8 == 0;
 }
 
-static BilinearPlan plan_bilinear(Workspace& ws, int64_t br, int64_t b, int64_t dx, int64_t dy, int precision) {
+// gemms_only: no fused B x B stage (the per-sample InfoNCE runs the G-materialising chain, mi_nce.h)
+static BilinearPlan plan_bilinear(Workspace& ws, int64_t br, int64_t b, int64_t dx, int64_t dy, int precision,
+                                  bool gemms_only = false) {
   BilinearPlan p{};
   p.n_partials = ((b + kTile - 1) / kTile) * ((br + kTile - 1) / kTile);
   p.partials = ws.take<Partial>(p.n_partials);
@@ -109,7 +112,7 @@ static BilinearPlan plan_bilinear(Workspace& ws, int64_t br, int64_t b, int64_t 
     p.f8sc = ws.take<Fp8Scales>(1);
   }
   p.fl = FlashPlan{};
-  if (precision == MI_PREC_BF16 && br % 8 == 0 && b % 8 == 0 && dx % 8 == 0) p.fl = flash_plan(br, b, dy);
+  if (precision == MI_PREC_BF16 && br % 8 == 0 && b % 8 == 0 && dx % 8 == 0 && !gemms_only) p.fl = flash_plan(br, b, dy);
   for (int q = 0; q < 2; ++q) {
     p.fl_rec[q] = p.fl.ok ? ws.take<Partial>(p.fl.n_rec[q]) : nullptr;
     p.fl_slab[q] = p.fl.ok ? ws.take<float>((p.fl.slab_bytes[q] + 3) / 4) : nullptr;
@@ -247,6 +250,8 @@ static int fast_prep_and_t_bf16(const bf16_t* x, const bf16_t* y, const float* w
 
 static int bilinear_bwd_small(int64_t br, int64_t dx, int64_t dy, float* grad_x, float* grad_w, const BilinearPlan& p,
                               hipStream_t st);
+static int bilinear_bwd_from_g(int64_t br, int64_t b, int64_t dx, int64_t dy, float* grad_x, float* grad_y, float* grad_w,
+                               bool has_w, const BilinearPlan& p, hipStream_t st);
 
 // the fused B x B launch: scores, masked log-sum-exp partials and (grad) the unnormalised sums U, V of both gradient
 // contractions.  Problem 0 sweeps the text rows for every local image row, problem 1 the local image rows for every
@@ -368,11 +373,20 @@ static int bilinear_bwd_fast(const int64_t* sid_rows, const int64_t* sid_cols, i
   }
   // G and G^T (bf16) from recomputed score tiles
   const int x3 = p.x3;
-  const int ra = x3 == 3 ? 1 : 0, rbk = x3 == 3 ? 2 : 0;
   rc = launch_gemm_bf16(one_problem(p.tb, x3 * dy, p.yb, x3 * dy, br, b, x3 * dy), 1,
                             EpiGradScore2{sid_rows, sid_cols, row_offset, stats, grad_out, p.gb, p.gtb, x3 == 3 ? 1 : 0}, st,
                             "bilinear G");
   if (rc) return rc;
+  return bilinear_bwd_from_g(br, b, dx, dy, grad_x, grad_y, grad_w, true, p, st);
+}
+
+// The backward behind G, G^T (bf16, in the plan): dT = G Y | dY = G^T T, then dW | dX.  has_w == false (S = X Y^T on
+// projected embeddings): dT is grad_x itself and there is no dW | dX launch.
+static int bilinear_bwd_from_g(int64_t br, int64_t b, int64_t dx, int64_t dy, float* grad_x, float* grad_y, float* grad_w,
+                               bool has_w, const BilinearPlan& p, hipStream_t st) {
+  int rc = MI_OK;
+  const int x3 = p.x3;
+  const int ra = x3 == 3 ? 1 : 0, rbk = x3 == 3 ? 2 : 0;
   // problem 0: dT[i, c] = sum_j G[i, j] Y[j, c]   (A = G [br][b], B = Y^T [dy][b])  -> bf16 both orientations
   // problem 1: dY[j, c] = sum_i G[i, j] T[i, c]   (A = G^T [b][br], B = T^T [dy][br]) -> fp32 grad_y
   GemmBf16Args two{};
@@ -381,10 +395,10 @@ static int bilinear_bwd_fast(const int64_t* sid_rows, const int64_t* sid_cols, i
   two.n_problems = 2;
   two.k_chunk = x3 * (b > br ? b : br);
   EpiStoreMulti e2{};
-  e2.out[0] = EpiOut{nullptr, 0, 0, p.dtb, dy, p.dttb, br, nullptr, ra, rbk};
+  e2.out[0] = has_w ? EpiOut{nullptr, 0, 0, p.dtb, dy, p.dttb, br, nullptr, ra, rbk} : EpiOut{grad_x, dy, 0, nullptr, 0, nullptr, 0};
   e2.out[1] = EpiOut{grad_y, dy, 0, nullptr, 0, nullptr, 0};
   bool split_done = false;
-  if (p.dt_splits > 1 && x3 == 1) {
+  if (p.dt_splits > 1 && x3 == 1 && has_w) {
     // sharded row block: dT partial sums over K chunks into fp32 slabs, beside dY; then one pass that adds the slabs and
     // writes the two bf16 orientations of dT
     EpiStoreMulti es{};
@@ -407,6 +421,7 @@ static int bilinear_bwd_fast(const int64_t* sid_rows, const int64_t* sid_cols, i
     rc = launch_gemm_bf16(two, 1, e2, st, "bilinear dT = G Y | dY = G^T T");
     if (rc) return rc;
   }
+  if (!has_w) return MI_OK;
   return bilinear_bwd_small(br, dx, dy, grad_x, grad_w, p, st);
 }
 
@@ -590,25 +605,37 @@ static int bilinear_fwd_impl(const float* x, const float* y, const float* w, con
 }
 
 template <typename OpT, typename TG>
+static int generic_bwd_from_g(const float* x, const float* y, const float* w, const float* t, const TG* g, int64_t br,
+                              int64_t b, int64_t dx, int64_t dy, float* grad_x, float* grad_y, float* grad_w,
+                              const BilinearPlan& p, hipStream_t st);
+
+template <typename OpT, typename TG>
 static int bilinear_bwd_impl(const float* x, const float* y, const float* w, const int64_t* sid_rows,
                              const int64_t* sid_cols, int64_t br, int64_t b, int64_t row_offset, int64_t dx, int64_t dy,
                              const mi_stats* stats, const float* grad_out, float* grad_x, float* grad_y, float* grad_w,
                              const BilinearPlan& p, hipStream_t st) {
   TG* g = (TG*)p.g;
   int rc = MI_OK;
-  const float* t = x;
-  float* dt = grad_x;  // w == nullptr: dT is dX
+  const float* t = x;  // w == nullptr: dT is dX
   if (w) {
     rc = generic_gemm_store<OpT>(make_operand(x, dx, 1), make_operand(w, 1, dy), br, dy, dx, p.t, dy, p, st,
                                  "bilinear T = X W (generic, bwd)");
     if (rc) return rc;
     t = p.t;
-    dt = p.dt;
   }
   rc = launch_gemm<OpT>(make_operand(t, dy, 1), make_operand(y, dy, 1), br, b, dy,
                         EpiGradScore<TG>{sid_rows, sid_cols, row_offset, stats, grad_out, g}, st, "bilinear G (generic)");
   if (rc) return rc;
-  rc = generic_gemm_store<OpT>(make_operand((const TG*)g, b, 1), make_operand(y, 1, dy), br, dy, b, dt, dy, p, st,
+  return generic_bwd_from_g<OpT, TG>(x, y, w, t, g, br, b, dx, dy, grad_x, grad_y, grad_w, p, st);
+}
+
+// The generic backward behind G [br][b] (TG): dT = G Y, dY = G^T T, dW = X^T dT, dX = dT W^T; w == nullptr: dT is dX.
+template <typename OpT, typename TG>
+static int generic_bwd_from_g(const float* x, const float* y, const float* w, const float* t, const TG* g, int64_t br,
+                              int64_t b, int64_t dx, int64_t dy, float* grad_x, float* grad_y, float* grad_w,
+                              const BilinearPlan& p, hipStream_t st) {
+  float* dt = w ? p.dt : grad_x;
+  int rc = generic_gemm_store<OpT>(make_operand((const TG*)g, b, 1), make_operand(y, 1, dy), br, dy, b, dt, dy, p, st,
                                "bilinear dT = G Y (generic)");
   if (rc) return rc;
   rc = generic_gemm_store<OpT>(make_operand((const TG*)g, 1, b), make_operand(t, 1, dy), b, dy, br, grad_y, dy, p, st,
@@ -1341,3 +1368,255 @@ extern "C" int mi_debug_set_stamps(void* buf) {
   return 0;
 }
 #endif
+
+// ================================================================================================ per-sample InfoNCE
+// (mi_nce.h)  The G-materialising chain with per-row and per-column statistics instead of one
+// global scalar:
+//   16-bit chain (bf16 / bf16x3, b and widths multiples of 8):
+//     prep + T = X W -> score GEMM with the row / column record epilogue -> merge -> loss
+//     [grads] G GEMM (recomputed scores -> G, G^T) -> dT = G Y | dY = G^T T -> dW = X^T dT | dX = dT W^T
+//   generic kernels (MI_PREC_F32, other shapes): the same sequence on mi_gemm.h, G in fp32 (bf16 in the bf16 mode)
+// The fused B x B kernel is not used: per-row normalisation needs r_i before any row's P tile can be weighted.
+namespace mi {
+
+static bool nce_fast_ok(int64_t b, int64_t dx, int64_t dy, int precision) {
+  return (precision == MI_PREC_BF16 || precision == MI_PREC_BF16X3) && b % 8 == 0 && dx % 8 == 0 && dy % 8 == 0;
+}
+
+static int nce_check(const char* fn, int64_t b, int64_t dx, int64_t dy, int mode, int precision) {
+  MI_CHECK_ARG(b >= 1 && dx >= 1 && dy >= 1, "%s: sizes must be >= 1 (b %lld, widths %lld, %lld)", fn, (long long)b,
+               (long long)dx, (long long)dy);
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || mode == MI_NCE_SYMMETRIC, "%s: unknown mode %d", fn, mode);
+  MI_CHECK_ARG(precision == MI_PREC_F32 || precision == MI_PREC_BF16 || precision == MI_PREC_BF16X3,
+               "%s: precision %d is not available for the per-sample InfoNCE (f32, bf16, bf16x3)", fn, precision);
+  return MI_OK;
+}
+
+struct NceBilinearPlan {
+  BilinearPlan p;
+  NcePlan q;
+  size_t bytes;
+};
+static NceBilinearPlan plan_nce_bilinear(Workspace& ws, int64_t b, int64_t dx, int64_t dy, int precision) {
+  NceBilinearPlan n{};
+  n.p = plan_bilinear(ws, b, b, dx, dy, precision, true);
+  n.q = plan_nce(ws, b);
+  n.bytes = ws.off;
+  return n;
+}
+
+// generic kernels: forward (T, scores -> records -> r, c, loss) and, when grad_y != nullptr, the backward
+template <typename OpT, typename TG>
+static int nce_step_generic(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t dx,
+                            int64_t dy, int mode, const float* grad_out, float* loss_out, float* lse_rows,
+                            float* lse_cols, float* grad_x, float* grad_y, float* grad_w, const NceBilinearPlan& n,
+                            hipStream_t st) {
+  const BilinearPlan& p = n.p;
+  int rc = MI_OK;
+  const float* t = x;  // w == nullptr: S = X Y^T
+  if (w) {
+    rc = generic_gemm_store<OpT>(make_operand(x, dx, 1), make_operand(w, 1, dy), b, dy, dx, p.t, dy, p, st,
+                                 "nce T = X W (generic)");
+    if (rc) return rc;
+    t = p.t;
+  }
+  rc = launch_gemm<OpT>(make_operand(t, dy, 1), make_operand(y, dy, 1), b, b, dy, EpiNceStats<false>{nce_stats_out(n.q, sid)},
+                        st, "nce score + row / column records (generic)");
+  if (rc) return rc;
+  rc = nce_finish(n.q, b, mode, loss_out, lse_rows, lse_cols, st);
+  if (rc || !grad_y) return rc;
+  TG* g = (TG*)p.g;
+  rc = launch_gemm<OpT>(make_operand(t, dy, 1), make_operand(y, dy, 1), b, b, dy,
+                        EpiNceGrad<TG>{nce_grad_in(sid, n.q.r, n.q.c, grad_out, b, mode), g}, st, "nce G (generic)");
+  if (rc) return rc;
+  return generic_bwd_from_g<OpT, TG>(x, y, w, t, g, b, b, dx, dy, grad_x, grad_y, grad_w, p, st);
+}
+
+// 16-bit chain
+static int nce_step_fast(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t dx,
+                         int64_t dy, int mode, const float* grad_out, float* loss_out, float* lse_rows, float* lse_cols,
+                         float* grad_x, float* grad_y, float* grad_w, const NceBilinearPlan& n, hipStream_t st) {
+  const BilinearPlan& p = n.p;
+  const int x3 = p.x3;
+  int rc = MI_OK;
+  if (w) {
+    rc = fast_prep_and_t(x, y, w, sid, sid, b, b, 0, dx, dy, p, st);  // p.fl.ok is false: the GEMM chain's preparation
+  } else {
+    // S = X Y^T: X takes the place of T (A operand of the scores, B operand of dY = G^T T)
+    const int ra = x3 == 3 ? 1 : 0, rb = x3 == 3 ? 2 : 0;
+    CvtJobs jobs{};
+    jobs.j[0] = CvtJob{x, b, dx, p.tb, p.ttb, 0, 0, nullptr, ra, rb};
+    jobs.j[1] = CvtJob{y, b, dy, p.yb, p.ytb, 0, 0, nullptr, rb, rb};
+    rc = launch_cvt_transpose3(jobs, st, "nce prep X Y");
+  }
+  if (rc) return rc;
+  const GemmBf16Args scores = one_problem(p.tb, x3 * dy, p.yb, x3 * dy, b, b, x3 * dy);
+  rc = launch_gemm_bf16(scores, 1, EpiNceStats<true>{nce_stats_out(n.q, sid)}, st, "nce score + row / column records");
+  if (rc) return rc;
+  rc = nce_finish(n.q, b, mode, loss_out, lse_rows, lse_cols, st);
+  if (rc || !grad_y) return rc;
+  rc = launch_gemm_bf16(scores, 1,
+                        EpiNceGrad2{nce_grad_in(sid, n.q.r, n.q.c, grad_out, b, mode), p.gb, p.gtb, x3 == 3 ? 1 : 0}, st,
+                        "nce G");
+  if (rc) return rc;
+  return bilinear_bwd_from_g(b, b, dx, dy, grad_x, grad_y, grad_w, w != nullptr, p, st);
+}
+
+static int nce_step_any(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t dx,
+                        int64_t dy, int mode, int precision, const float* grad_out, float* loss_out, float* lse_rows,
+                        float* lse_cols, float* grad_x, float* grad_y, float* grad_w, const NceBilinearPlan& n,
+                        hipStream_t st) {
+  if (nce_fast_ok(b, dx, dy, precision))
+    return nce_step_fast(x, y, w, sid, b, dx, dy, mode, grad_out, loss_out, lse_rows, lse_cols, grad_x, grad_y, grad_w, n,
+                         st);
+  if (precision == MI_PREC_BF16)
+    return nce_step_generic<bf16_t, bf16_t>(x, y, w, sid, b, dx, dy, mode, grad_out, loss_out, lse_rows, lse_cols, grad_x,
+                                            grad_y, grad_w, n, st);
+  return nce_step_generic<float, float>(x, y, w, sid, b, dx, dy, mode, grad_out, loss_out, lse_rows, lse_cols, grad_x,
+                                        grad_y, grad_w, n, st);
+}
+
+struct NceSeparablePlan {
+  float *a, *c, *da, *dc;
+  NceBilinearPlan n;
+  size_t bytes;
+};
+static NceSeparablePlan plan_nce_separable(Workspace& ws, int64_t b, int64_t k, int precision) {
+  NceSeparablePlan s{};
+  s.a = ws.take<float>(b * k);
+  s.c = ws.take<float>(b * k);
+  s.da = ws.take<float>(b * k);
+  s.dc = ws.take<float>(b * k);
+  s.n = plan_nce_bilinear(ws, b, k, k, precision);
+  s.bytes = ws.off;
+  return s;
+}
+
+}  // namespace mi
+
+extern "C" {
+
+size_t mi_nce_bilinear_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int precision) {
+  if (b <= 0 || d_img <= 0 || d_txt <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_nce_bilinear(ws, b, d_img, d_txt, precision).bytes + 256;
+}
+
+int mi_nce_bilinear_step(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t d_img,
+                         int64_t d_txt, int mode, int precision, const float* grad_out, float* loss_out, float* lse_rows,
+                         float* lse_cols, float* grad_x, float* grad_y, float* grad_w, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && sid && loss_out && workspace, "mi_nce_bilinear_step: null pointer");
+  int rc = nce_check("mi_nce_bilinear_step", b, d_img, d_txt, mode, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(w || d_img == d_txt, "mi_nce_bilinear_step: w == NULL (S = X Y^T) needs d_img == d_txt");
+  const bool any_grad = grad_x || grad_y || grad_w;
+  MI_CHECK_ARG(!any_grad || (grad_x && grad_y && (w ? grad_w != nullptr : grad_w == nullptr)),
+               "mi_nce_bilinear_step: pass grad_x, grad_y and (with w) grad_w, or none of them");
+  Workspace ws(workspace, workspace_bytes);
+  NceBilinearPlan n = plan_nce_bilinear(ws, b, d_img, d_txt, precision);
+  if (!ws.ok()) {
+    set_error("mi_nce_bilinear_step: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
+    return MI_EWORKSPACE;
+  }
+  return nce_step_any(x, y, w, sid, b, d_img, d_txt, mode, precision, grad_out, loss_out, lse_rows, lse_cols, grad_x,
+                      grad_y, grad_w, n, (hipStream_t)stream);
+}
+
+size_t mi_nce_separable_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int precision) {
+  if (b <= 0 || d_img <= 0 || d_txt <= 0 || d_proj <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_nce_separable(ws, b, d_proj, precision).bytes + 256;
+}
+
+int mi_nce_separable_step(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid, int64_t b,
+                          int64_t d_img, int64_t d_txt, int64_t d_proj, int mode, int precision, const float* grad_out,
+                          float* loss_out, float* lse_rows, float* lse_cols, float* grad_x, float* grad_y,
+                          float* grad_wg, float* grad_wh, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && wg && wh && sid && loss_out && workspace, "mi_nce_separable_step: null pointer");
+  int rc = nce_check("mi_nce_separable_step", b, d_img, d_txt, mode, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(d_proj >= 1, "mi_nce_separable_step: projection width must be >= 1");
+  const bool any_grad = grad_x || grad_y || grad_wg || grad_wh;
+  MI_CHECK_ARG(!any_grad || (grad_x && grad_y && grad_wg && grad_wh),
+               "mi_nce_separable_step: pass all four gradients or none of them");
+  Workspace ws(workspace, workspace_bytes);
+  NceSeparablePlan sp = plan_nce_separable(ws, b, d_proj, precision);
+  if (!ws.ok()) {
+    set_error("mi_nce_separable_step: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
+    return MI_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t k = d_proj;
+  // projections and their backward on the strided-operand kernels, as the separable critic's generic path (bf16 operands
+  // in the bf16 mode, exact fp32 products otherwise); the scores and their gradients on the bilinear chain with W = I
+  const bool bf = precision == MI_PREC_BF16;
+#define MI_NCE_GEMM(A, B, M, N, K, OUT, LD, WHAT)                                                              \
+  do {                                                                                                          \
+    rc = bf ? launch_gemm<bf16_t>(A, B, M, N, K, EpiStore{OUT, LD, nullptr, 1.0f, 0}, st, WHAT)                \
+            : launch_gemm<float>(A, B, M, N, K, EpiStore{OUT, LD, nullptr, 1.0f, 0}, st, WHAT);                \
+    if (rc) return rc;                                                                                          \
+  } while (0)
+  MI_NCE_GEMM(make_operand(x, d_img, 1), make_operand(wg, 1, k), b, k, d_img, sp.a, k, "nce separable A = X Wg");
+  MI_NCE_GEMM(make_operand(y, d_txt, 1), make_operand(wh, 1, k), b, k, d_txt, sp.c, k, "nce separable C = Y Wh");
+  rc = nce_step_any(sp.a, sp.c, nullptr, sid, b, k, k, mode, precision, grad_out, loss_out, lse_rows, lse_cols,
+                    any_grad ? sp.da : nullptr, any_grad ? sp.dc : nullptr, nullptr, sp.n, st);
+  if (rc || !any_grad) return rc;
+  MI_NCE_GEMM(make_operand((const float*)sp.da, k, 1), make_operand(wg, k, 1), b, d_img, k, grad_x, d_img,
+              "nce separable dX = dA Wg^T");
+  MI_NCE_GEMM(make_operand(x, 1, d_img), make_operand((const float*)sp.da, 1, k), d_img, k, b, grad_wg, k,
+              "nce separable dWg = X^T dA");
+  MI_NCE_GEMM(make_operand((const float*)sp.dc, k, 1), make_operand(wh, k, 1), b, d_txt, k, grad_y, d_txt,
+              "nce separable dY = dC Wh^T");
+  MI_NCE_GEMM(make_operand(y, 1, d_txt), make_operand((const float*)sp.dc, 1, k), d_txt, k, b, grad_wh, k,
+              "nce separable dWh = Y^T dC");
+#undef MI_NCE_GEMM
+  return MI_OK;
+}
+
+size_t mi_matrix_nce_workspace_bytes(int64_t b) {
+  if (b <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  plan_nce(ws, b);
+  return ws.off + 256;
+}
+
+int mi_matrix_nce_fwd(const float* scores, const int64_t* sid, int64_t b, int mode, float* loss_out, float* lse_rows,
+                      float* lse_cols, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(scores && sid && loss_out && workspace, "mi_matrix_nce_fwd: null pointer");
+  MI_CHECK_ARG(b >= 1, "mi_matrix_nce_fwd: b must be >= 1");
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || mode == MI_NCE_SYMMETRIC, "mi_matrix_nce_fwd: unknown mode %d", mode);
+  Workspace ws(workspace, workspace_bytes);
+  const NcePlan q = plan_nce(ws, b);
+  if (!ws.ok()) {
+    set_error("mi_matrix_nce_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
+    return MI_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  {
+    ProfScope prof_("nce_matrix_stats_kernel", st);
+    hipLaunchKernelGGL(nce_matrix_stats_kernel, dim3((unsigned)q.n_t, (unsigned)q.n_t), dim3(64), 0, st, scores, b,
+                       nce_stats_out(q, sid));
+  }
+  MI_LAUNCH_CHECK("nce_matrix_stats_kernel");
+  return nce_finish(q, b, mode, loss_out, lse_rows, lse_cols, st);
+}
+
+int mi_matrix_nce_bwd(const float* scores, const int64_t* sid, int64_t b, int mode, const float* lse_rows,
+                      const float* lse_cols, const float* grad_out, float* grad_scores, void* stream) {
+  MI_CHECK_ARG(scores && sid && lse_rows && grad_scores, "mi_matrix_nce_bwd: null pointer");
+  MI_CHECK_ARG(b >= 1, "mi_matrix_nce_bwd: b must be >= 1");
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || mode == MI_NCE_SYMMETRIC, "mi_matrix_nce_bwd: unknown mode %d", mode);
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || lse_cols, "mi_matrix_nce_bwd: the symmetric mode needs lse_cols");
+  const int64_t nt = (b + 63) / 64;
+  hipStream_t st = (hipStream_t)stream;
+  {
+    ProfScope prof_("nce_matrix_grad_kernel", st);
+    hipLaunchKernelGGL(nce_matrix_grad_kernel, dim3((unsigned)nt, (unsigned)nt), dim3(64), 0, st, scores, b,
+                       nce_grad_in(sid, lse_rows, lse_cols, grad_out, b, mode), grad_scores);
+  }
+  MI_LAUNCH_CHECK("nce_matrix_grad_kernel");
+  return MI_OK;
+}
+
+}  // extern "C"

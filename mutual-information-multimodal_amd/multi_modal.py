@@ -77,7 +77,8 @@ def train_mutual_information(args, device):
     logging.getLogger(__name__).info(f"args: {args}")
     critic = getattr(args, "critic", "concat_mlp")
     if getattr(args, "synthetic", False):
-        model_manager = MultiModalManager(d_img=args.embed_dim_img, d_txt=args.embed_dim_txt, critic=critic)
+        model_manager = MultiModalManager(d_img=args.embed_dim_img, d_txt=args.embed_dim_txt, critic=critic,
+                                          mi_estimator=getattr(args, "mi_estimator", None))
         source = synthetic_embedding_source(args, device)
     elif getattr(args, "synthetic_encoders", False):
         from mutual_info_img_txt.model import ResNet256_6_2_1, TextBert

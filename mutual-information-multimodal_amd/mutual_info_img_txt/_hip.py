@@ -19,6 +19,10 @@ LIB_PATH = os.environ.get("MI_CRITIC_LIB", os.path.join(_PKG_ROOT, "lib", "libmi
 MI_DV, MI_INFONCE = 0, 1
 MI_PREC_F32, MI_PREC_BF16, MI_PREC_BF16X3, MI_PREC_FP8, MI_PREC_F16, MI_PREC_F16X3 = 0, 1, 2, 3, 4, 5
 ESTIMATORS = {"dv": MI_DV, "infonce": MI_INFONCE}
+# the per-sample InfoNCE (mi_nce_* / mi_matrix_nce_*): mode codes of their own entry points, NOT estimator codes of the
+# entry points above
+MI_NCE_ROWWISE, MI_NCE_SYMMETRIC = 0, 1
+NCE_ESTIMATORS = {"infonce_rowwise": MI_NCE_ROWWISE, "infonce_symmetric": MI_NCE_SYMMETRIC}
 PRECISIONS = {"f32": MI_PREC_F32, "fp32": MI_PREC_F32, "float32": MI_PREC_F32, "f32_exact": MI_PREC_F32,
               "bf16": MI_PREC_BF16, "bfloat16": MI_PREC_BF16, "bf16x3": MI_PREC_BF16X3, "fp8": MI_PREC_FP8,
               "f16": MI_PREC_F16, "fp16": MI_PREC_F16, "float16": MI_PREC_F16, "f16x3": MI_PREC_F16X3}
@@ -86,6 +90,13 @@ SIGNATURES = {
     "mi_concat_mlp_fwd": (c_int, [_P] * 10 + [_I64] * 7 + [_I, _I, _I] + [_P] * 5 + [_SZ, _P]),
     "mi_concat_mlp_bwd": (c_int, [_P] * 10 + [_I64] * 7 + [_I] + [_P] * 12 + [_SZ, _P]),
     "mi_merge_partials": (c_int, [_P, _I64, _I64, _I, _P, _P, _P]),
+    "mi_nce_bilinear_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I]),
+    "mi_nce_bilinear_step": (c_int, [_P] * 4 + [_I64] * 3 + [_I, _I] + [_P] * 8 + [_SZ, _P]),
+    "mi_nce_separable_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I]),
+    "mi_nce_separable_step": (c_int, [_P] * 5 + [_I64] * 4 + [_I, _I] + [_P] * 9 + [_SZ, _P]),
+    "mi_matrix_nce_workspace_bytes": (_SZ, [_I64]),
+    "mi_matrix_nce_fwd": (c_int, [_P, _P, _I64, _I, _P, _P, _P, _P, _SZ, _P]),
+    "mi_matrix_nce_bwd": (c_int, [_P, _P, _I64, _I, _P, _P, _P, _P, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

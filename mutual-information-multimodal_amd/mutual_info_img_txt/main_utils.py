@@ -18,7 +18,7 @@ from __future__ import annotations
 import logging
 import os
 import time
-from typing import Sequence
+from typing import Optional, Sequence
 
 import torch
 
@@ -102,7 +102,7 @@ class MultiModalManager:
     def __init__(self, bert_pretrained_dir=None, bert_config_name=None, output_channels=None, image_model_name=None, *,
                  d_img: int = 768, d_txt: int = 768, critic: str = "concat_mlp", hidden_dims=(1024, 512),
                  d_proj: int = 256, image_model=None, text_model=None, bert_config=None, embed_proj_dim=None,
-                 autocast_dtype=None):
+                 autocast_dtype=None, mi_estimator: Optional[str] = None):
         self.bert_pretrained_dir = bert_pretrained_dir
         self.bert_config_name = bert_config_name
         self.output_channels = output_channels
@@ -132,6 +132,8 @@ class MultiModalManager:
         else:
             raise ValueError(f"unknown critic {critic!r}: expected concat_mlp, bilinear or separable")
         self.critic_kind = critic
+        if mi_estimator is not None:  # the per-sample InfoNCE needs the bilinear or separable critic
+            mi_critics.check_estimator(mi_estimator, critic)
         self.d_img, self.d_txt = d_img, d_txt
         self.training_loss = []
         self._graphed = None
@@ -151,7 +153,16 @@ class MultiModalManager:
                 fused: bool = True, graph: bool = False):
         """Reference main_utils.py:220-224.  ``fused=False`` runs the literal three-call sequence (pair kernel, critic
         module, bound kernel) and is only practical for small batches.  ``graph=True`` replays the fused step from
-        hipGraphs (``graphed.GraphedMiStep``, built on first use for this batch shape; the training loop's setting)."""
+        hipGraphs (``graphed.GraphedMiStep``, built on first use for this batch shape; the training loop's setting).
+        "infonce_rowwise" / "infonce_symmetric" always run eagerly through ``fused_mi_bound`` (one library call per step;
+        ``graph`` is ignored for them: GraphedMiStep captures the reference's estimators only)."""
+        if mi_estimator in mi_critics.NCE_ESTIMATORS:
+            mi_critics.check_estimator(mi_estimator, self.critic_kind)
+            if not fused:
+                scores = self.mi_discriminator(embedding_img, embedding_txt)
+                return mi_critics.matrix_bound_loss(scores, study_id, mi_estimator)
+            return mi_critics.fused_mi_bound(embedding_img, embedding_txt, study_id, self.mi_discriminator,
+                                             mi_estimator, precision)
         if fused and graph and self.critic_kind != "separable":
             g = self._graphed
             key = (tuple(embedding_img.shape), tuple(embedding_txt.shape), mi_estimator, precision)
@@ -249,7 +260,7 @@ class MultiModalManager:
         resuming (a new file name, so the reference's loaders are unaffected).  Returns the list of epoch losses (the
         reference returns None) and keeps it in ``self.training_loss``."""
         logger = logging.getLogger(__name__)
-        mi_critics._estimator_code(args.mi_estimator)  # eager validation (the reference fails late, main_utils.py:224)
+        mi_critics.check_estimator(args.mi_estimator, self.critic_kind)  # eager (the reference fails late, main_utils.py:224)
         self.mi_discriminator = self.mi_discriminator.to(device)
         if self.model is not None:
             self.model = self.model.to(device)

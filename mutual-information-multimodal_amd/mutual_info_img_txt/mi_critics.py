@@ -10,6 +10,11 @@ plus the fused entry point that replaces lines ``main_utils.py:220-224`` of the 
 
 * ``fused_mi_bound(embedding_img, embedding_txt, study_id, critic, estimator, ...)``
 
+Besides the reference's two estimators, ``fused_mi_bound`` (bilinear and separable critics) and ``matrix_bound_loss``
+take the per-sample InfoNCE of CPC / ConVIRT / CLIP: ``"infonce_rowwise"`` (image -> report cross-entropy) and
+``"infonce_symmetric"`` (its mean with report -> image), with the reference's masking of equal-id pairs (DESIGN.md
+section 8).
+
 Every function runs hand-written HIP kernels through the C ABI in ``include/mi_critic.h`` (loaded with ctypes,
 wrapped in ``torch.autograd.Function``).  There is no CPU path: CPU tensors raise.
 """
@@ -20,10 +25,11 @@ from typing import Optional, Sequence, Union
 import torch
 
 from . import _hip
-from ._hip import ESTIMATORS, PRECISIONS
+from ._hip import ESTIMATORS, NCE_ESTIMATORS, PRECISIONS
 
 __all__ = ["dv_bound_loss", "infonce_bound_loss", "matrix_bound_loss", "fused_mi_bound", "study_id_codes",
-           "BilinearCriticFn", "SeparableCriticFn", "ConcatMlpCriticFn"]
+           "BilinearCriticFn", "SeparableCriticFn", "ConcatMlpCriticFn", "NceBilinearFn", "NceSeparableFn",
+           "check_estimator"]
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -43,6 +49,20 @@ def _estimator_code(estimator: str) -> int:
         # at :224); here it is rejected eagerly
         raise ValueError(f"unknown mi_estimator {estimator!r}: expected one of {sorted(ESTIMATORS)}")
     return ESTIMATORS[estimator]
+
+
+def check_estimator(estimator: str, critic_kind: str) -> None:
+    """Eager validation of an estimator name for a critic kind ("concat_mlp", "bilinear", "separable"): the reference's
+    "dv" / "infonce" for every critic, the per-sample "infonce_rowwise" / "infonce_symmetric" for the bilinear and
+    separable critics only."""
+    if estimator in NCE_ESTIMATORS:
+        if critic_kind not in ("bilinear", "separable"):
+            raise ValueError(f"mi_estimator {estimator!r} is implemented for the bilinear and separable critics only "
+                             f"(got critic {critic_kind!r})")
+        return
+    if estimator not in ESTIMATORS:
+        raise ValueError(f"unknown mi_estimator {estimator!r}: expected one of "
+                         f"{sorted(ESTIMATORS) + sorted(NCE_ESTIMATORS)}")
 
 
 def _precision_code(precision: str) -> int:
@@ -138,12 +158,47 @@ class _MatrixBoundFn(torch.autograd.Function):
         return grad, None, None
 
 
+class _MatrixNceFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores: torch.Tensor, sid: torch.Tensor, mode: int):
+        lib = _hip.load()
+        s = _hip.f32c(scores, "scores")
+        b = s.shape[0]
+        dev = s.device
+        ws = _hip.workspace(lib.mi_matrix_nce_workspace_bytes(b), dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        r = torch.empty(b, dtype=torch.float32, device=dev)
+        c = torch.empty(b, dtype=torch.float32, device=dev)
+        _hip.call("mi_matrix_nce_fwd", dev, s.data_ptr(), sid.data_ptr(), b, mode, loss.data_ptr(), r.data_ptr(),
+                  c.data_ptr(), ws.data_ptr(), ws.numel())
+        ctx.save_for_backward(s, sid, r, c)
+        ctx.mode = mode
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        s, sid, r, c = ctx.saved_tensors
+        go = _grad_scalar(grad_loss)
+        grad = torch.empty_like(s)
+        _hip.call("mi_matrix_nce_bwd", s.device, s.data_ptr(), sid.data_ptr(), s.shape[0], ctx.mode, r.data_ptr(),
+                  c.data_ptr(), go.data_ptr(), grad.data_ptr())
+        return grad, None, None
+
+
 def matrix_bound_loss(scores: torch.Tensor, study_id, estimator: str = "dv") -> torch.Tensor:
     """The reference loss on a [B,B] score matrix S[i,j] = critic(img_i, txt_j): positives are the diagonal, negatives
-    the pairs with i != j and different study ids (main_utils.py:99-108).  Shape [1] (dv) / [] (infonce)."""
+    the pairs with i != j and different study ids (main_utils.py:99-108).  Shape [1] (dv) / [] (infonce).
+
+    "infonce_rowwise" / "infonce_symmetric": the per-sample InfoNCE on the same scores and masking,
+    shape [], gradients to ``scores``.  The way to that loss for any critic whose scores you compute yourself."""
     _hip.require_device(scores, "scores")
     if scores.dim() != 2 or scores.shape[0] != scores.shape[1]:
         raise ValueError("scores must be [B, B]")
+    if estimator in NCE_ESTIMATORS:
+        sid = study_id_codes(study_id, scores.device)
+        if sid.numel() != scores.shape[0]:
+            raise ValueError("study_id length must equal B")
+        return _MatrixNceFn.apply(scores, sid, NCE_ESTIMATORS[estimator]).reshape(())
     code = _estimator_code(estimator)
     sid = study_id_codes(study_id, scores.device)
     if sid.numel() != scores.shape[0]:
@@ -287,6 +342,118 @@ class ConcatMlpCriticFn(torch.autograd.Function):
         return (*grads, None, None, None, None)
 
 
+class NceBilinearFn(torch.autograd.Function):
+    """Per-sample InfoNCE of S = (X W) Y^T (W None: S = X Y^T) in one library call (mi_nce_bilinear_step).  With
+    ``need_grad`` the call also writes every gradient for dL/dloss = 1; the backward only scales them by grad_loss.
+    Returns (loss [1], lse_rows [B], lse_cols [B])."""
+
+    @staticmethod
+    def forward(ctx, x, y, w, sid, mode: int, precision: int, need_grad: bool):
+        lib = _hip.load()
+        x = _hip.f32c(x, "embedding_img")
+        y = _hip.f32c(y, "embedding_txt")
+        w = None if w is None else _hip.f32c(w, "bilinear weight")
+        b, dx = x.shape
+        dy = y.shape[1]
+        dev = x.device
+        ws = _hip.workspace(lib.mi_nce_bilinear_workspace_bytes(b, dx, dy, precision), dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        r = torch.empty(b, dtype=torch.float32, device=dev)
+        c = torch.empty(b, dtype=torch.float32, device=dev)
+        gx = torch.empty_like(x) if need_grad else None
+        gy = torch.empty_like(y) if need_grad else None
+        gw = torch.empty_like(w) if need_grad and w is not None else None
+        _hip.call("mi_nce_bilinear_step", dev, x.data_ptr(), y.data_ptr(), _hip.ptr(w), sid.data_ptr(), b, dx, dy, mode,
+                  precision, None, loss.data_ptr(), r.data_ptr(), c.data_ptr(), _hip.ptr(gx), _hip.ptr(gy), _hip.ptr(gw),
+                  ws.data_ptr(), ws.numel())
+        ctx.save_for_backward(*[g for g in (gx, gy, gw) if g is not None])
+        ctx.mark_non_differentiable(r, c)
+        return loss, r, c
+
+    @staticmethod
+    def backward(ctx, grad_loss, _gr, _gc):
+        saved = ctx.saved_tensors
+        if not saved:
+            raise RuntimeError("NceBilinearFn: the forward ran without gradients (need_grad=False)")
+        go = grad_loss.reshape(-1)[:1].to(torch.float32)
+        gx, gy = saved[0] * go, saved[1] * go
+        gw = saved[2] * go if len(saved) > 2 else None
+        return gx, gy, gw, None, None, None, None
+
+
+class NceSeparableFn(torch.autograd.Function):
+    """Per-sample InfoNCE of S = (X Wg)(Y Wh)^T in one library call (mi_nce_separable_step); see NceBilinearFn."""
+
+    @staticmethod
+    def forward(ctx, x, y, wg, wh, sid, mode: int, precision: int, need_grad: bool):
+        lib = _hip.load()
+        x, y = _hip.f32c(x, "embedding_img"), _hip.f32c(y, "embedding_txt")
+        wg, wh = _hip.f32c(wg, "image projection"), _hip.f32c(wh, "text projection")
+        b, dx = x.shape
+        dy, k = y.shape[1], wg.shape[1]
+        if wg.shape[0] != dx or wh.shape != (dy, k):
+            raise ValueError("projection shapes must be [d_img, d_proj] and [d_txt, d_proj]")
+        dev = x.device
+        ws = _hip.workspace(lib.mi_nce_separable_workspace_bytes(b, dx, dy, k, precision), dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        r = torch.empty(b, dtype=torch.float32, device=dev)
+        c = torch.empty(b, dtype=torch.float32, device=dev)
+        grads = [torch.empty_like(t) for t in (x, y, wg, wh)] if need_grad else [None] * 4
+        _hip.call("mi_nce_separable_step", dev, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(), sid.data_ptr(),
+                  b, dx, dy, k, mode, precision, None, loss.data_ptr(), r.data_ptr(), c.data_ptr(),
+                  *[_hip.ptr(g) for g in grads], ws.data_ptr(), ws.numel())
+        ctx.save_for_backward(*[g for g in grads if g is not None])
+        ctx.mark_non_differentiable(r, c)
+        return loss, r, c
+
+    @staticmethod
+    def backward(ctx, grad_loss, _gr, _gc):
+        saved = ctx.saved_tensors
+        if not saved:
+            raise RuntimeError("NceSeparableFn: the forward ran without gradients (need_grad=False)")
+        go = grad_loss.reshape(-1)[:1].to(torch.float32)
+        return (*(g * go for g in saved), None, None, None, None)
+
+
+def _fused_nce(embedding_img, embedding_txt, study_id, critic, estimator, precision, return_scores, return_stats):
+    """fused_mi_bound for "infonce_rowwise" / "infonce_symmetric"."""
+    from . import model as _model
+
+    if not isinstance(critic, (_model.BilinearCritic, _model.SeparableCritic)):
+        raise ValueError(f"mi_estimator {estimator!r} is implemented for BilinearCritic and SeparableCritic only; for "
+                         "scores you compute yourself (e.g. a make_mlp critic applied to every pair) use "
+                         "matrix_bound_loss(scores, study_id, estimator)")
+    if embedding_img.dim() != 2 or embedding_txt.dim() != 2 or embedding_img.shape[0] != embedding_txt.shape[0]:
+        raise ValueError("embedding_img / embedding_txt must be [B, d_img] / [B, d_txt]")
+    sid = study_id_codes(study_id, embedding_img.device)
+    if sid.numel() != embedding_img.shape[0]:
+        raise ValueError("study_id length must equal the batch size")
+    mode = NCE_ESTIMATORS[estimator]
+    b, dx, dy = embedding_img.shape[0], embedding_img.shape[1], embedding_txt.shape[1]
+    bilinear = isinstance(critic, _model.BilinearCritic)
+    # "f32": bf16x3 on the bilinear critic where every size is a multiple of 8, exact fp32 products otherwise (the library
+    # rejects fp8 / f16 / f16x3 for this loss)
+    prec = _hip.resolve_precision(precision, bilinear, (b, dx, dy))
+    params = (critic.weight,) if bilinear else (critic.wg, critic.wh)
+    need_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (embedding_img, embedding_txt) + params)
+    if bilinear:
+        loss, r, c = NceBilinearFn.apply(embedding_img, embedding_txt, critic.weight, sid, mode, prec, need_grad)
+    else:
+        loss, r, c = NceSeparableFn.apply(embedding_img, embedding_txt, critic.wg, critic.wh, sid, mode, prec, need_grad)
+    out = [loss.reshape(())]
+    if return_scores:  # diagnostic output, as for the reference's estimators: no gradient flows through it
+        with torch.no_grad():
+            if bilinear:
+                s = BilinearCriticFn.apply(embedding_img, embedding_txt, critic.weight, sid, _hip.MI_DV, prec, True)[2]
+            else:
+                a, cc = critic.project_img(embedding_img), critic.project_txt(embedding_txt)
+                s = BilinearCriticFn.apply(a, cc, None, sid, _hip.MI_DV, prec, True)[2]
+        out.append(s)
+    if return_stats:
+        out.append((r, c))
+    return out[0] if len(out) == 1 else tuple(out)
+
+
 def _concat_params(critic):
     """(W1,b1,W2,b2,W3,b3) of an nn.Sequential built by make_mlp(input_dim,[h1,h2]) (reference model.py:18-32)."""
     mods = list(critic)
@@ -321,6 +488,11 @@ def fused_mi_bound(embedding_img: torch.Tensor, embedding_txt: torch.Tensor, stu
     and runs both forward products on the fp8 MFMA (BASELINE configs[4]); its results match an oracle fed the same
     quantised values, not the fp32 reference.  Embeddings in float64 are cast to float32 (the reference would run them in fp64; this path computes in
     fp32).
+
+    ``estimator`` = "infonce_rowwise" / "infonce_symmetric" (BilinearCritic, SeparableCritic): the per-sample InfoNCE
+    (DESIGN.md section 8), loss of shape [], precisions "f32" / "f32_exact" / "bf16" / "bf16x3";
+    ``return_stats=True`` then gives ``(lse_rows, lse_cols)``, the row and column log-sum-exps.  A make_mlp critic raises
+    ValueError: apply it to the pairs yourself and call ``matrix_bound_loss(scores, study_id, estimator)``.
     """
     from . import model as _model  # local import: model.py imports nothing from here
 
@@ -330,6 +502,8 @@ def fused_mi_bound(embedding_img: torch.Tensor, embedding_txt: torch.Tensor, stu
         embedding_img = embedding_img.float()
     if embedding_txt.dtype == torch.float64:
         embedding_txt = embedding_txt.float()
+    if estimator in NCE_ESTIMATORS:
+        return _fused_nce(embedding_img, embedding_txt, study_id, critic, estimator, precision, return_scores, return_stats)
     code = _estimator_code(estimator)
     prec = _precision_code(precision)
     if isinstance(critic, _model.BilinearCritic) and embedding_img.dim() == 2 and embedding_txt.dim() == 2:

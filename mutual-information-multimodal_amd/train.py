@@ -32,10 +32,21 @@ def construct_training_parameters(argv=None):
     return p.parse_args(argv)
 
 
+MI_ESTIMATORS = ('dv', 'infonce', 'infonce_rowwise', 'infonce_symmetric')
+PER_SAMPLE_ESTIMATORS = ('infonce_rowwise', 'infonce_symmetric')  # per-sample InfoNCE: bilinear / separable critics only
+
+
+def check_training_parameters(args):
+    """Eager validation of the flags that the reference only trips over inside the training step."""
+    if args.mi_estimator not in MI_ESTIMATORS:
+        raise ValueError(f"unknown --mi_estimator {args.mi_estimator!r}: expected one of {MI_ESTIMATORS}")
+    if args.mi_estimator in PER_SAMPLE_ESTIMATORS and args.critic == 'concat_mlp':
+        raise ValueError(f"--mi_estimator {args.mi_estimator} needs --critic bilinear or --critic separable")
+    return args
+
+
 def train_MI_models(argv=None):
-    args = construct_training_parameters(argv)
-    if args.mi_estimator not in ('dv', 'infonce'):
-        raise ValueError(f"unknown --mi_estimator {args.mi_estimator!r}")
+    args = check_training_parameters(construct_training_parameters(argv))
     if not torch.cuda.is_available():
         raise RuntimeError("the MI critic path needs an MI355X (ROCm) device; there is no CPU fallback")
     device = torch.device('cuda')
