@@ -1,0 +1,351 @@
+"""The one binding of the critic entry points of the C ABI (mi_bilinear_*, mi_separable_*, mi_concat_mlp_*, mi_nce_*),
+shared by ``mi_critics`` (eager autograd), ``graphed`` (hipGraph step) and ``distributed`` (sharded step).
+
+An ops object scores the row block ``x`` [b_rows, d_img] (starting at ``row_offset``) against all of ``y_all``
+[b, d_txt]; a whole batch is ``b_rows == b``, ``row_offset == 0``.  Each ``*_call`` method writes one entry point's
+argument list and returns the launch bound to the given tensors (a ``functools.partial`` of ``_hip.call``, which looks
+up the current stream per call): eager callers issue it at once, ``GraphedMiStep`` binds its static buffers once.
+"""
+from __future__ import annotations
+
+import ctypes
+from functools import partial
+
+import torch
+
+from . import _hip
+from ._hip import PRECISIONS, ptr as _p
+
+
+def _precision_code(precision: str) -> int:
+    if precision not in PRECISIONS:
+        raise ValueError(f"unknown precision {precision!r}: expected one of {sorted(PRECISIONS)}")
+    return PRECISIONS[precision]
+
+
+def _concat_params(critic):
+    """(W1,b1,W2,b2,W3,b3) of an nn.Sequential built by make_mlp(input_dim,[h1,h2]) (reference model.py:18-32)."""
+    mods = list(critic)
+    lin = [m for m in mods if isinstance(m, torch.nn.Linear)]
+    act = [m for m in mods if not isinstance(m, torch.nn.Linear)]
+    if len(lin) != 3 or len(mods) != 5 or not all(isinstance(a, torch.nn.ReLU) for a in act) or lin[2].out_features != 1:
+        raise ValueError("the fused concat-MLP path supports make_mlp(input_dim, [h1, h2]) critics "
+                         "(Linear-ReLU-Linear-ReLU-Linear(->1)); use create_mi_pairs + the critic module otherwise")
+    return lin[0].weight, lin[0].bias, lin[1].weight, lin[1].bias, lin[2].weight, lin[2].bias
+
+
+def resolve_critic(critic, precision: str, b: int, d_img: int, d_txt: int, params=None):
+    """(kind, params, precision code) of a critic: a ``BilinearCritic``, a ``SeparableCritic``, the reference's make_mlp
+    critic, None (S = X Y^T), or -- for the sharded path -- a kind name with its ``params``.
+
+    "f32" means fp32-grade results (``_hip.resolve_precision``): the bf16x3 scheme on the bilinear critic with a weight
+    where b, d_img and d_txt are multiples of 8, the f16x3 scheme on make_mlp critics of the fused hidden sizes, exact
+    fp32 products otherwise.  ``params`` of a make_mlp critic are the module's own tensors (W3 is [1, h2])."""
+    from . import model as _model  # local import: model.py imports nothing from here
+    weighted = False
+    if isinstance(critic, str):
+        kind, params, weighted = critic, list(params or ()), critic == "bilinear"
+    elif isinstance(critic, _model.BilinearCritic):
+        kind, params, weighted = "bilinear", [critic.weight], True
+    elif isinstance(critic, _model.SeparableCritic):
+        kind, params = "separable", [critic.wg, critic.wh]
+        if critic.wg.shape[0] != d_img or tuple(critic.wh.shape) != (d_txt, critic.wg.shape[1]):
+            raise ValueError("projection shapes must be [d_img, d_proj] and [d_txt, d_proj]")
+    elif critic is None:
+        # GraphedMiStep's weightless form; unlike BilinearCritic, "f32" stays exact fp32 here (no bf16x3)
+        if d_img != d_txt:
+            raise ValueError("critic=None is the separable form S = X Y^T: widths must agree")
+        kind, params = "bilinear", []
+    else:
+        kind, params = "concat_mlp", list(_concat_params(critic))
+        if params[0].shape[1] != d_img + d_txt:
+            raise ValueError(f"critic expects {params[0].shape[1]} inputs, embeddings give {d_img} + {d_txt}")
+    hidden = (params[0].shape[0], params[2].shape[0]) if kind == "concat_mlp" and len(params) == 6 else None
+    return kind, params, _hip.resolve_precision(precision, weighted, (b, d_img, d_txt), concat_hidden=hidden)
+
+
+def fwd_outputs(device, scores=None):
+    """(loss [1], statistics, partial record, scores) -- the outputs of one forward call."""
+    return (torch.empty(1, dtype=torch.float32, device=device), _hip.new_stats(device),
+            torch.empty(_hip.RECORD_FLOATS, dtype=torch.float32, device=device), scores)
+
+
+def _call(name, device, *args):
+    return partial(_hip.call, name, device, *args)
+
+
+class _HipOps:
+    """The ops protocol of ``distributed.GlobalBatchCriticFn`` (forward / merge / backward) on the C ABI.  ``saved`` is
+    (x, y_all, params, sid_rows, sid_all, row_offset, precision, scores, ws) for every critic."""
+
+    def _scores(self, x, y_all):
+        return None
+
+    def _workspace(self, x, y_all, params, precision, flags):
+        """(workspace, extra need_grad bits) of a forward without a caller-provided workspace."""
+        nbytes = self.workspace_bytes(x.shape[0], y_all.shape[0], x.shape[1], y_all.shape[1], params, precision, flags)
+        return _hip.workspace(nbytes, x.device), 0
+
+    def forward(self, x, y_all, params, sid_rows, sid_all, row_offset, estimator, precision, need_grad, out=None, ws=None):
+        """Partial record of the row block -> (record, saved).  ``out`` = preallocated ``fwd_outputs``; ``ws`` = a
+        workspace sized by ``workspace_bytes``."""
+        flags = int(bool(need_grad))
+        if ws is None:
+            ws, bits = self._workspace(x, y_all, params, precision, flags)
+            flags |= bits
+        if out is None:
+            out = fwd_outputs(x.device, self._scores(x, y_all))
+        self.fwd_call(x, y_all, params, sid_rows, sid_all, row_offset, estimator, precision, flags, out, ws)()
+        return out[2], (x, y_all, list(params), sid_rows, sid_all, row_offset, precision, out[3], ws)
+
+    def backward(self, saved, stats, grad_out, out=None):
+        """``out`` = (grad_x, grad_y_partial, [grad_params...]) preallocated buffers (e.g. views of one flat all-reduce
+        buffer); allocated here when None."""
+        x, y_all, params = saved[:3]
+        if out is None:
+            out = (torch.empty_like(x), torch.empty_like(y_all), [torch.empty_like(p) for p in params])
+        self.bwd_call(saved, stats, grad_out, out)()
+        return out
+
+    def merge(self, records, n_pos, estimator):
+        dev = records.device
+        loss, stats = torch.empty(1, dtype=torch.float32, device=dev), _hip.new_stats(dev)
+        _hip.call("mi_merge_partials", dev, records.data_ptr(), records.shape[0], n_pos, estimator, loss.data_ptr(),
+                  stats.data_ptr())
+        return loss, stats
+
+    def nce_step(self, x, y, params, sid, mode, precision, need_grad):
+        """Per-sample InfoNCE of the whole batch in one call, with the gradients of 1 * loss when ``need_grad``:
+        (loss [1], lse_rows [B], lse_cols [B], [grad_x, grad_y, grad_params...] or [])."""
+        b, dev = x.shape[0], x.device
+        ws = _hip.workspace(self.nce_workspace_bytes(b, x.shape[1], y.shape[1], params, precision), dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        r, c = torch.empty(b, dtype=torch.float32, device=dev), torch.empty(b, dtype=torch.float32, device=dev)
+        grads = [torch.empty_like(t) for t in (x, y, *params)] if need_grad else []
+        self.nce_call(x, y, params, sid, mode, precision, loss, r, c, grads, ws)()
+        return loss, r, c, grads
+
+
+class HipBilinearOps(_HipOps):
+    """S = (X W) Y^T row block; params = [W] ([] on one GPU: S = X Y^T)."""
+
+    def __init__(self):
+        self._fp8_ws = None    # workspace of a staged fp8 preparation, handed on to forward()
+        self._local_ws = None  # workspace in which prep_local() prepared the rank's own part, handed on to forward()
+        self._local_key = None
+
+    @staticmethod
+    def workspace_bytes(br, b, dx, dy, params, precision, need_grad=1):
+        return _hip.load().mi_bilinear_workspace_bytes(br, b, dx, dy, precision)
+
+    def fwd_call(self, x, y, params, sid_rows, sid_all, row_offset, estimator, precision, flags, out, ws):
+        loss, stats, record, scores = out
+        w = params[0] if params else None
+        return _call("mi_bilinear_fwd", x.device, x.data_ptr(), y.data_ptr(), _p(w), sid_rows.data_ptr(),
+                     sid_all.data_ptr(), x.shape[0], y.shape[0], row_offset, x.shape[1], y.shape[1], estimator, precision,
+                     flags, _p(loss), stats.data_ptr(), _p(record), _p(scores), ws.data_ptr(), ws.numel())
+
+    def bwd_call(self, saved, stats, grad_out, out):
+        x, y, params, sid_rows, sid_all, row_offset, precision, _, ws = saved
+        gx, gy, gp = out
+        return _call("mi_bilinear_bwd", x.device, x.data_ptr(), y.data_ptr(), _p(params[0] if params else None),
+                     sid_rows.data_ptr(), sid_all.data_ptr(), x.shape[0], y.shape[0], row_offset, x.shape[1], y.shape[1],
+                     precision, stats.data_ptr(), grad_out.data_ptr(), gx.data_ptr(), gy.data_ptr(),
+                     _p(gp[0] if gp else None), ws.data_ptr(), ws.numel(), 1)
+
+    def step_call(self, x, y, params, sid, estimator, precision, grad_out, out, grads, ws):
+        """Forward + backward of the whole batch in one call: mi_bilinear_step, or mi_bilinear_step_bf16 for bfloat16
+        embeddings (and gradients)."""
+        loss, stats, record, _ = out
+        gx, gy, gp = grads
+        w, gw = (params[0], gp[0]) if params else (None, None)
+        b, dx, dy = x.shape[0], x.shape[1], y.shape[1]
+        if x.dtype == torch.bfloat16:
+            return _call("mi_bilinear_step_bf16", x.device, x.data_ptr(), y.data_ptr(), w.data_ptr(), sid.data_ptr(), b,
+                         dx, dy, estimator, grad_out.data_ptr(), loss.data_ptr(), stats.data_ptr(), record.data_ptr(),
+                         gx.data_ptr(), gy.data_ptr(), int(gx.dtype == torch.bfloat16), gw.data_ptr(), ws.data_ptr(),
+                         ws.numel())
+        return _call("mi_bilinear_step", x.device, x.data_ptr(), y.data_ptr(), _p(w), sid.data_ptr(), b, dx, dy,
+                     estimator, precision, grad_out.data_ptr(), loss.data_ptr(), stats.data_ptr(), record.data_ptr(),
+                     gx.data_ptr(), gy.data_ptr(), _p(gw), ws.data_ptr(), ws.numel())
+
+    @staticmethod
+    def nce_workspace_bytes(b, dx, dy, params, precision):
+        return _hip.load().mi_nce_bilinear_workspace_bytes(b, dx, dy, precision)
+
+    def nce_call(self, x, y, params, sid, mode, precision, loss, r, c, grads, ws):
+        w = params[0] if params else None
+        gx, gy, gw = (grads + [None] * 3)[:3]
+        return _call("mi_nce_bilinear_step", x.device, x.data_ptr(), y.data_ptr(), _p(w), sid.data_ptr(), x.shape[0],
+                     x.shape[1], y.shape[1], mode, precision, None, loss.data_ptr(), r.data_ptr(), c.data_ptr(), _p(gx),
+                     _p(gy), _p(gw), ws.data_ptr(), ws.numel())
+
+    # ------------------------------------------------------------------------------------------ sharded extras
+    def prep_local(self, x, params, b, precision) -> bool:
+        """The part of the forward that needs neither the gathered text embeddings nor the gathered ids -- bf16 copies of
+        X and W, T = X W (mi_bilinear_prep_local) -- issued while the all-gather is in flight.  False where the shape or
+        precision does not take the fused kernels (forward() then does everything, as before)."""
+        lib = _hip.load()
+        (w,) = params
+        br, dx = x.shape
+        dy = w.shape[1]
+        if precision == _hip.MI_PREC_FP8:
+            return False
+        ws = _hip.workspace(lib.mi_bilinear_workspace_bytes(br, b, dx, dy, precision), x.device)
+        with torch.cuda.device(x.device):
+            rc = lib.mi_bilinear_prep_local(x.data_ptr(), w.data_ptr(), br, b, dx, dy, precision, ws.data_ptr(), ws.numel(),
+                                            torch.cuda.current_stream(x.device).cuda_stream)
+        if rc == _hip.MI_ESHAPE:
+            return False
+        _hip.check(rc, "mi_bilinear_prep_local")
+        self._local_ws = ws
+        self._local_key = (x.data_ptr(), w.data_ptr(), br, b, dx, dy, precision)
+        return True
+
+    def _take_local_ws(self, x, w, br, b, dx, dy, precision):
+        """The workspace prep_local() filled -- only for the call it was made for (same tensors, shapes, precision)."""
+        ws, self._local_ws = self._local_ws, None
+        if ws is not None and self._local_key != (x.data_ptr(), w.data_ptr(), br, b, dx, dy, precision):
+            return None  # a prep_local() whose forward never came: not this call's
+        return ws
+
+    def _workspace(self, x, y_all, params, precision, flags):
+        if precision == _hip.MI_PREC_FP8 and self._fp8_ws is not None:
+            ws, self._fp8_ws = self._fp8_ws, None
+            return ws, 2  # bit 1: the fp8 operands are staged in this workspace
+        if params:
+            ws = self._take_local_ws(x, params[0], x.shape[0], y_all.shape[0], x.shape[1], y_all.shape[1], precision)
+            if ws is not None:
+                return ws, 4  # bit 2: prep_local() already ran in this workspace
+        return super()._workspace(x, y_all, params, precision, flags)
+
+    def fp8_stage(self, stage, x, y_all, params, amax):
+        """One stage of the fp8 mode's preparation (mi_bilinear_fp8_stage): ``amax`` (4 floats on the device: x, y, W, T)
+        is MAX-all-reduced by the caller between the stages, so that every rank quantises with the whole batch's scales."""
+        (w,) = params
+        br, dx = x.shape
+        b, dy = y_all.shape
+        if stage == 0:
+            self._fp8_ws = _hip.workspace(self.workspace_bytes(br, b, dx, dy, params, _hip.MI_PREC_FP8), x.device)
+        ws = self._fp8_ws
+        _hip.call("mi_bilinear_fp8_stage", x.device, x.data_ptr(), y_all.data_ptr(), w.data_ptr(), br, b, dx, dy, int(stage),
+                  amax.data_ptr(), ws.data_ptr(), ws.numel())
+
+    def forward_raw(self, x, y_all, params, sid_rows, sid_all, row_offset, estimator, precision):
+        """Forward WITHOUT the finalize launch (mi_bilinear_fwd, need_grad bit 3): returns the fused kernel's per-wave
+        records ([n, 4] float32, a view of the workspace) for the caller to all-gather, or None where the shape does not take
+        that path.  `merge_backward` then merges the gathered records inside the backward's first launch."""
+        off = ctypes.c_size_t(0)
+        n = _hip.load().mi_bilinear_raw_records(x.shape[0], y_all.shape[0], x.shape[1], y_all.shape[1], precision,
+                                                ctypes.byref(off))
+        if n == 0:
+            return None
+        ws, bits = self._workspace(x, y_all, params, precision, 1)
+        stats = _hip.new_stats(x.device)  # (untouched by this call; the C ABI wants a valid pointer)
+        self.fwd_call(x, y_all, params, sid_rows, sid_all, row_offset, estimator, precision, 1 | 8 | bits,
+                      (None, stats, None, None), ws)()
+        records = ws[off.value:off.value + 16 * n].view(torch.float32).view(n, 4)
+        return records, (x, y_all, list(params), sid_rows, sid_all, row_offset, precision, None, ws)
+
+    def merge_backward(self, saved, records_all, n_pos, estimator, grad_out, out=None, dw=True):
+        """mi_bilinear_bwd_records: merge of the gathered raw records (rank order), loss, statistics and all gradients in
+        the backward's two launches -> (loss, stats, grad_x, grad_y, [grad_w]).  ``dw=False``: the first launch only."""
+        x, y, params, sid_rows, sid_all, row_offset, precision, _, ws = saved
+        dev = x.device
+        gx, gy, gp = out if out is not None else (torch.empty_like(x), torch.empty_like(y), [torch.empty_like(params[0])])
+        loss, stats = torch.empty(1, dtype=torch.float32, device=dev), _hip.new_stats(dev)
+        _hip.call("mi_bilinear_bwd_records", dev, x.data_ptr(), y.data_ptr(), params[0].data_ptr(), sid_rows.data_ptr(),
+                  sid_all.data_ptr(), x.shape[0], y.shape[0], row_offset, x.shape[1], y.shape[1], precision, estimator,
+                  records_all.data_ptr(), records_all.shape[0], n_pos, grad_out.data_ptr(), loss.data_ptr(),
+                  stats.data_ptr(), gx.data_ptr(), gy.data_ptr(), gp[0].data_ptr() if dw else None, ws.data_ptr(),
+                  ws.numel())
+        return loss, stats, gx, gy, gp
+
+    def merge_backward_tail(self, saved, records_all, n_pos, estimator, grad_out, out=None):
+        """The first launch of merge_backward only (mi_bilinear_bwd_records with grad_w = NULL): statistics, loss, grad_x and
+        the partial grad_y.  The caller starts the reduce-scatter of grad_y and then calls ``backward_dw``."""
+        if out is None:
+            out = (torch.empty_like(saved[0]), torch.empty_like(saved[1]), [None])
+        return self.merge_backward(saved, records_all, n_pos, estimator, grad_out, out, dw=False)[:4]
+
+    def backward_dw(self, saved, out=None):
+        """dW = X^T dT (mi_bilinear_bwd_dw) from the workspace merge_backward_tail left."""
+        x, y_all, params, _sr, _sa, _ro, precision, _, ws = saved
+        gw = torch.empty_like(params[0]) if out is None else out[2][0]
+        _hip.call("mi_bilinear_bwd_dw", x.device, x.shape[0], y_all.shape[0], x.shape[1], y_all.shape[1], precision,
+                  gw.data_ptr(), ws.data_ptr(), ws.numel())
+        return [gw]
+
+
+class HipSeparableOps(_HipOps):
+    """S = (X Wg)(Y Wh)^T row block (BASELINE.json configs[1]); params = [Wg, Wh].  Every rank projects ALL text rows
+    (B d k flops, small beside the B^2 stage); d(Wh) and dY are partials over the row block like the bilinear dY."""
+
+    @staticmethod
+    def workspace_bytes(br, b, dx, dy, params, precision, need_grad=1):
+        return _hip.load().mi_separable_workspace_bytes(br, b, dx, dy, params[0].shape[1], precision)
+
+    def fwd_call(self, x, y, params, sid_rows, sid_all, row_offset, estimator, precision, flags, out, ws):
+        (wg, wh), (loss, stats, record, _) = params, out
+        return _call("mi_separable_fwd", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
+                     sid_rows.data_ptr(), sid_all.data_ptr(), x.shape[0], y.shape[0], row_offset, x.shape[1], y.shape[1],
+                     wg.shape[1], estimator, precision, flags, loss.data_ptr(), stats.data_ptr(), record.data_ptr(),
+                     ws.data_ptr(), ws.numel())
+
+    def bwd_call(self, saved, stats, grad_out, out):
+        x, y, (wg, wh), sid_rows, sid_all, row_offset, precision, _, ws = saved
+        gx, gy, (gg, gh) = out
+        return _call("mi_separable_bwd", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
+                     sid_rows.data_ptr(), sid_all.data_ptr(), x.shape[0], y.shape[0], row_offset, x.shape[1], y.shape[1],
+                     wg.shape[1], precision, stats.data_ptr(), grad_out.data_ptr(), gx.data_ptr(), gy.data_ptr(),
+                     gg.data_ptr(), gh.data_ptr(), ws.data_ptr(), ws.numel(), 1)
+
+    def step_call(self, x, y, params, sid, estimator, precision, grad_out, out, grads, ws):
+        """Forward + backward of the whole batch in one call (mi_separable_step)."""
+        (wg, wh), (loss, stats, record, _), (gx, gy, (gg, gh)) = params, out, grads
+        return _call("mi_separable_step", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
+                     sid.data_ptr(), x.shape[0], x.shape[1], y.shape[1], wg.shape[1], estimator, precision,
+                     grad_out.data_ptr(), loss.data_ptr(), stats.data_ptr(), record.data_ptr(), gx.data_ptr(),
+                     gy.data_ptr(), gg.data_ptr(), gh.data_ptr(), ws.data_ptr(), ws.numel())
+
+    @staticmethod
+    def nce_workspace_bytes(b, dx, dy, params, precision):
+        return _hip.load().mi_nce_separable_workspace_bytes(b, dx, dy, params[0].shape[1], precision)
+
+    def nce_call(self, x, y, params, sid, mode, precision, loss, r, c, grads, ws):
+        wg, wh = params
+        return _call("mi_nce_separable_step", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
+                     sid.data_ptr(), x.shape[0], x.shape[1], y.shape[1], wg.shape[1], mode, precision, None,
+                     loss.data_ptr(), r.data_ptr(), c.data_ptr(), *[_p(g) for g in grads or [None] * 4], ws.data_ptr(),
+                     ws.numel())
+
+
+class HipConcatMlpOps(_HipOps):
+    """S[i,j] = MLP([x_i ; y_j]) row block; params = [W1, b1, W2, b2, w3, b3] (w3 flat or [1, h2])."""
+
+    def _scores(self, x, y_all):
+        return torch.empty(x.shape[0], y_all.shape[0], dtype=torch.float32, device=x.device)
+
+    @staticmethod
+    def workspace_bytes(br, b, dx, dy, params, precision, need_grad=1):
+        return _hip.load().mi_concat_mlp_workspace_bytes(br, b, dx, dy, params[0].shape[0], params[2].shape[0],
+                                                         precision, int(need_grad))
+
+    def fwd_call(self, x, y, params, sid_rows, sid_all, row_offset, estimator, precision, flags, out, ws):
+        loss, stats, record, scores = out
+        return _call("mi_concat_mlp_fwd", x.device, x.data_ptr(), y.data_ptr(), *[p.data_ptr() for p in params],
+                     sid_rows.data_ptr(), sid_all.data_ptr(), x.shape[0], y.shape[0], row_offset, x.shape[1], y.shape[1],
+                     params[0].shape[0], params[2].shape[0], estimator, precision, flags, loss.data_ptr(),
+                     stats.data_ptr(), record.data_ptr(), scores.data_ptr(), ws.data_ptr(), ws.numel())
+
+    def bwd_call(self, saved, stats, grad_out, out):
+        x, y, params, sid_rows, sid_all, row_offset, precision, scores, ws = saved
+        gx, gy, gp = out
+        return _call("mi_concat_mlp_bwd", x.device, x.data_ptr(), y.data_ptr(), *[p.data_ptr() for p in params],
+                     sid_rows.data_ptr(), sid_all.data_ptr(), x.shape[0], y.shape[0], row_offset, x.shape[1], y.shape[1],
+                     params[0].shape[0], params[2].shape[0], precision, stats.data_ptr(), grad_out.data_ptr(),
+                     scores.data_ptr(), gx.data_ptr(), gy.data_ptr(), *[g.data_ptr() for g in gp], ws.data_ptr(),
+                     ws.numel())
+
+
+OPS = {"bilinear": HipBilinearOps, "separable": HipSeparableOps, "concat_mlp": HipConcatMlpOps}

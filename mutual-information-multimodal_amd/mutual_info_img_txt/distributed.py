@@ -15,7 +15,6 @@ The local compute is an ``ops`` object.  The product default runs the HIP kernel
 """
 from __future__ import annotations
 
-import ctypes
 import os
 from typing import List, Optional, Sequence
 
@@ -23,266 +22,8 @@ import torch
 import torch.distributed as dist
 
 from . import _hip
-
-
-# ----------------------------------------------------------------------------------------------------------
-# local ops through the C ABI (the product path)
-# ----------------------------------------------------------------------------------------------------------
-class HipBilinearOps:
-    """S = (X W) Y^T row block; params = [W]."""
-    n_params = 1
-
-    def __init__(self):
-        self._fp8_ws = None    # workspace of a staged fp8 preparation, handed on to forward()
-        self._local_ws = None  # workspace in which prep_local() prepared the rank's own part, handed on to forward()
-        self._local_key = None
-
-    def prep_local(self, x, params, b, precision) -> bool:
-        """The part of the forward that needs neither the gathered text embeddings nor the gathered ids -- bf16 copies of
-        X and W, T = X W (mi_bilinear_prep_local) -- issued while the all-gather is in flight.  False where the shape or
-        precision does not take the fused kernels (forward() then does everything, as before)."""
-        lib = _hip.load()
-        (w,) = params
-        br, dx = x.shape
-        dy = w.shape[1]
-        if precision == _hip.MI_PREC_FP8:
-            return False
-        ws = _hip.workspace(lib.mi_bilinear_workspace_bytes(br, b, dx, dy, precision), x.device)
-        with torch.cuda.device(x.device):
-            rc = lib.mi_bilinear_prep_local(x.data_ptr(), w.data_ptr(), br, b, dx, dy, precision, ws.data_ptr(), ws.numel(),
-                                            torch.cuda.current_stream(x.device).cuda_stream)
-        if rc == _hip.MI_ESHAPE:
-            return False
-        _hip.check(rc, "mi_bilinear_prep_local")
-        self._local_ws = ws
-        self._local_key = (x.data_ptr(), w.data_ptr(), br, b, dx, dy, precision)
-        return True
-
-    def _take_local_ws(self, x, w, br, b, dx, dy, precision):
-        """The workspace prep_local() filled -- only for the call it was made for (same tensors, shapes, precision)."""
-        ws, self._local_ws = self._local_ws, None
-        if ws is not None and self._local_key != (x.data_ptr(), w.data_ptr(), br, b, dx, dy, precision):
-            return None  # a prep_local() whose forward never came: not this call's
-        return ws
-
-    def fp8_stage(self, stage, x, y_all, params, amax):
-        """One stage of the fp8 mode's preparation (mi_bilinear_fp8_stage): ``amax`` (4 floats on the device: x, y, W, T)
-        is MAX-all-reduced by the caller between the stages, so that every rank quantises with the whole batch's scales."""
-        lib = _hip.load()
-        (w,) = params
-        br, dx = x.shape
-        b, dy = y_all.shape
-        if stage == 0:
-            self._fp8_ws = _hip.workspace(lib.mi_bilinear_workspace_bytes(br, b, dx, dy, _hip.MI_PREC_FP8), x.device)
-        ws = self._fp8_ws
-        _hip.call("mi_bilinear_fp8_stage", x.device, x.data_ptr(), y_all.data_ptr(), w.data_ptr(), br, b, dx, dy, int(stage),
-                  amax.data_ptr(), ws.data_ptr(), ws.numel())
-
-    def forward(self, x, y_all, params, sid_rows, sid_all, row_offset, estimator, precision, need_grad):
-        lib = _hip.load()
-        (w,) = params
-        br, dx = x.shape
-        b, dy = y_all.shape
-        dev = x.device
-        staged = precision == _hip.MI_PREC_FP8 and self._fp8_ws is not None
-        if staged:
-            ws, self._fp8_ws = self._fp8_ws, None
-            need_grad = int(bool(need_grad)) | 2  # bit 1: the fp8 operands are staged in this workspace
-        else:
-            ws = self._take_local_ws(x, w, br, b, dx, dy, precision)
-            if ws is not None:
-                need_grad = int(bool(need_grad)) | 4  # bit 2: prep_local() already ran in this workspace
-            else:
-                ws = _hip.workspace(lib.mi_bilinear_workspace_bytes(br, b, dx, dy, precision), dev)
-        stats = _hip.new_stats(dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        record = torch.empty(_hip.RECORD_FLOATS, dtype=torch.float32, device=dev)
-        _hip.call("mi_bilinear_fwd", dev, x.data_ptr(), y_all.data_ptr(), w.data_ptr(), sid_rows.data_ptr(),
-                                       sid_all.data_ptr(), br, b, row_offset, dx, dy, estimator, precision,
-                                       int(need_grad), loss.data_ptr(), stats.data_ptr(), record.data_ptr(), None,
-                                       ws.data_ptr(),
-                                       ws.numel())
-        return record, (x, y_all, w, sid_rows, sid_all, row_offset, precision, ws)
-
-    def forward_raw(self, x, y_all, params, sid_rows, sid_all, row_offset, estimator, precision):
-        """Forward WITHOUT the finalize launch (mi_bilinear_fwd, need_grad bit 3): returns the fused kernel's per-wave
-        records ([n, 4] float32, a view of the workspace) for the caller to all-gather, or None where the shape does not take
-        that path.  `merge_backward` then merges the gathered records inside the backward's first launch."""
-        lib = _hip.load()
-        (w,) = params
-        br, dx = x.shape
-        b, dy = y_all.shape
-        off = ctypes.c_size_t(0)
-        n = lib.mi_bilinear_raw_records(br, b, dx, dy, precision, ctypes.byref(off))
-        if n == 0:
-            return None
-        dev = x.device
-        flags = 1 | 8
-        ws = self._take_local_ws(x, w, br, b, dx, dy, precision)
-        if ws is not None:
-            flags |= 4
-        else:
-            ws = _hip.workspace(lib.mi_bilinear_workspace_bytes(br, b, dx, dy, precision), dev)
-        stats = _hip.new_stats(dev)  # (untouched by this call; the C ABI wants a valid pointer)
-        _hip.call("mi_bilinear_fwd", dev, x.data_ptr(), y_all.data_ptr(), w.data_ptr(), sid_rows.data_ptr(),
-                  sid_all.data_ptr(), br, b, row_offset, dx, dy, estimator, precision, flags, None, stats.data_ptr(), None,
-                  None, ws.data_ptr(), ws.numel())
-        records = ws[off.value:off.value + 16 * n].view(torch.float32).view(n, 4)
-        return records, (x, y_all, w, sid_rows, sid_all, row_offset, precision, ws)
-
-    def merge_backward(self, saved, records_all, n_pos, estimator, grad_out, out=None):
-        """mi_bilinear_bwd_records: merge of the gathered raw records (rank order), loss, statistics and all gradients in
-        the backward's two launches."""
-        x, y_all, w, sid_rows, sid_all, row_offset, precision, ws = saved
-        br, dx = x.shape
-        b, dy = y_all.shape
-        dev = x.device
-        if out is None:
-            gx, gy, gw = torch.empty_like(x), torch.empty_like(y_all), torch.empty_like(w)
-        else:
-            gx, gy, (gw,) = out
-        stats = _hip.new_stats(dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        _hip.call("mi_bilinear_bwd_records", dev, x.data_ptr(), y_all.data_ptr(), w.data_ptr(), sid_rows.data_ptr(),
-                  sid_all.data_ptr(), br, b, row_offset, dx, dy, precision, estimator, records_all.data_ptr(),
-                  records_all.shape[0], n_pos, grad_out.data_ptr(), loss.data_ptr(), stats.data_ptr(), gx.data_ptr(),
-                  gy.data_ptr(), gw.data_ptr(), ws.data_ptr(), ws.numel())
-        return loss, stats, gx, gy, [gw]
-
-    def merge_backward_tail(self, saved, records_all, n_pos, estimator, grad_out, out=None):
-        """The first launch of merge_backward only (mi_bilinear_bwd_records with grad_w = NULL): statistics, loss, grad_x and
-        the partial grad_y.  The caller starts the reduce-scatter of grad_y and then calls ``backward_dw``."""
-        x, y_all, w, sid_rows, sid_all, row_offset, precision, ws = saved
-        br, dx = x.shape
-        b, dy = y_all.shape
-        dev = x.device
-        if out is None:
-            gx, gy = torch.empty_like(x), torch.empty_like(y_all)
-        else:
-            gx, gy, _ = out
-        stats = _hip.new_stats(dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        _hip.call("mi_bilinear_bwd_records", dev, x.data_ptr(), y_all.data_ptr(), w.data_ptr(), sid_rows.data_ptr(),
-                  sid_all.data_ptr(), br, b, row_offset, dx, dy, precision, estimator, records_all.data_ptr(),
-                  records_all.shape[0], n_pos, grad_out.data_ptr(), loss.data_ptr(), stats.data_ptr(), gx.data_ptr(),
-                  gy.data_ptr(), None, ws.data_ptr(), ws.numel())
-        return loss, stats, gx, gy
-
-    def backward_dw(self, saved, out=None):
-        """dW = X^T dT (mi_bilinear_bwd_dw) from the workspace merge_backward_tail left."""
-        x, y_all, w, _sr, _sa, _ro, precision, ws = saved
-        br, dx = x.shape
-        b, dy = y_all.shape
-        gw = torch.empty_like(w) if out is None else out[2][0]
-        _hip.call("mi_bilinear_bwd_dw", x.device, br, b, dx, dy, precision, gw.data_ptr(), ws.data_ptr(), ws.numel())
-        return [gw]
-
-    def merge(self, records, n_pos, estimator):
-        lib = _hip.load()
-        dev = records.device
-        stats = _hip.new_stats(dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        _hip.call("mi_merge_partials", dev, records.data_ptr(), records.shape[0], n_pos, estimator, loss.data_ptr(),
-                                         stats.data_ptr())
-        return loss, stats
-
-    def backward(self, saved, stats, grad_out, out=None):
-        """``out`` = (grad_x, grad_y_partial, [grad_params...]) preallocated buffers (e.g. views of one flat all-reduce
-        buffer); allocated here when None."""
-        lib = _hip.load()
-        x, y_all, w, sid_rows, sid_all, row_offset, precision, ws = saved
-        br, dx = x.shape
-        b, dy = y_all.shape
-        if out is None:
-            gx, gy, gw = torch.empty_like(x), torch.empty_like(y_all), torch.empty_like(w)
-        else:
-            gx, gy, (gw,) = out
-        _hip.call("mi_bilinear_bwd", x.device, x.data_ptr(), y_all.data_ptr(), w.data_ptr(), sid_rows.data_ptr(),
-                                       sid_all.data_ptr(), br, b, row_offset, dx, dy, precision, stats.data_ptr(),
-                                       grad_out.data_ptr(), gx.data_ptr(), gy.data_ptr(), gw.data_ptr(), ws.data_ptr(),
-                                       ws.numel(), 1)
-        return gx, gy, [gw]
-
-
-class HipSeparableOps:
-    """S = (X Wg)(Y Wh)^T row block (BASELINE.json configs[1]); params = [Wg, Wh].  Every rank projects ALL text rows
-    (B d k flops, small beside the B^2 stage); d(Wh) and dY are partials over the row block like the bilinear dY."""
-    n_params = 2
-
-    def forward(self, x, y_all, params, sid_rows, sid_all, row_offset, estimator, precision, need_grad):
-        lib = _hip.load()
-        wg, wh = params
-        br, dx = x.shape
-        b, dy = y_all.shape
-        k = wg.shape[1]
-        dev = x.device
-        ws = _hip.workspace(lib.mi_separable_workspace_bytes(br, b, dx, dy, k, precision), dev)
-        stats = _hip.new_stats(dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        record = torch.empty(_hip.RECORD_FLOATS, dtype=torch.float32, device=dev)
-        _hip.call("mi_separable_fwd", dev, x.data_ptr(), y_all.data_ptr(), wg.data_ptr(), wh.data_ptr(), sid_rows.data_ptr(),
-                  sid_all.data_ptr(), br, b, row_offset, dx, dy, k, estimator, precision, int(bool(need_grad)),
-                  loss.data_ptr(), stats.data_ptr(), record.data_ptr(), ws.data_ptr(), ws.numel())
-        return record, (x, y_all, wg, wh, sid_rows, sid_all, row_offset, precision, ws)
-
-    def backward(self, saved, stats, grad_out, out=None):
-        x, y_all, wg, wh, sid_rows, sid_all, row_offset, precision, ws = saved
-        br, dx = x.shape
-        b, dy = y_all.shape
-        k = wg.shape[1]
-        if out is None:
-            gx, gy, gg, gh = (torch.empty_like(t) for t in (x, y_all, wg, wh))
-        else:
-            gx, gy, (gg, gh) = out
-        _hip.call("mi_separable_bwd", x.device, x.data_ptr(), y_all.data_ptr(), wg.data_ptr(), wh.data_ptr(),
-                  sid_rows.data_ptr(), sid_all.data_ptr(), br, b, row_offset, dx, dy, k, precision, stats.data_ptr(),
-                  grad_out.data_ptr(), gx.data_ptr(), gy.data_ptr(), gg.data_ptr(), gh.data_ptr(), ws.data_ptr(), ws.numel(),
-                  1)
-        return gx, gy, [gg, gh]
-
-    merge = HipBilinearOps.merge
-
-
-class HipConcatMlpOps:
-    """S[i,j] = MLP([x_i ; y_j]) row block; params = [W1, b1, W2, b2, w3 (flat), b3]."""
-    n_params = 6
-
-    def forward(self, x, y_all, params, sid_rows, sid_all, row_offset, estimator, precision, need_grad):
-        lib = _hip.load()
-        br, dx = x.shape
-        b, dy = y_all.shape
-        h1, h2 = params[0].shape[0], params[2].shape[0]
-        dev = x.device
-        ws = _hip.workspace(lib.mi_concat_mlp_workspace_bytes(br, b, dx, dy, h1, h2, precision, int(need_grad)), dev)
-        stats = _hip.new_stats(dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        record = torch.empty(_hip.RECORD_FLOATS, dtype=torch.float32, device=dev)
-        scores = torch.empty(br, b, dtype=torch.float32, device=dev)
-        _hip.call("mi_concat_mlp_fwd", dev, x.data_ptr(), y_all.data_ptr(), *[p.data_ptr() for p in params],
-                                         sid_rows.data_ptr(), sid_all.data_ptr(), br, b, row_offset, dx, dy, h1, h2,
-                                         estimator, precision, int(need_grad), loss.data_ptr(), stats.data_ptr(),
-                                         record.data_ptr(), scores.data_ptr(), ws.data_ptr(), ws.numel())
-        return record, (x, y_all, list(params), sid_rows, sid_all, row_offset, precision, scores, ws)
-
-    merge = HipBilinearOps.merge
-
-    def backward(self, saved, stats, grad_out, out=None):
-        lib = _hip.load()
-        x, y_all, params, sid_rows, sid_all, row_offset, precision, scores, ws = saved
-        br, dx = x.shape
-        b, dy = y_all.shape
-        h1, h2 = params[0].shape[0], params[2].shape[0]
-        if out is None:
-            gx, gy = torch.empty_like(x), torch.empty_like(y_all)
-            gp = [torch.empty_like(p) for p in params]
-        else:
-            gx, gy, gp = out
-        _hip.call("mi_concat_mlp_bwd", x.device, x.data_ptr(), y_all.data_ptr(), *[p.data_ptr() for p in params],
-                                         sid_rows.data_ptr(), sid_all.data_ptr(), br, b, row_offset, dx, dy, h1, h2,
-                                         precision, stats.data_ptr(), grad_out.data_ptr(), scores.data_ptr(),
-                                         gx.data_ptr(), gy.data_ptr(), *[g.data_ptr() for g in gp], ws.data_ptr(),
-                                         ws.numel())
-        return gx, gy, gp
+# the product's local ops (through the C ABI); re-exported under their historical home
+from .critic_ops import OPS, HipBilinearOps, HipConcatMlpOps, HipSeparableOps, resolve_critic  # noqa: F401
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -439,18 +180,6 @@ class GlobalBatchCriticFn(torch.autograd.Function):
         return (None, None, None, None, None, gx, gy, *gparams)
 
 
-def _sharded_precision(precision: str, critic: str, x, y, params=None) -> int:
-    """The same name -> code resolution as on one GPU (_hip.resolve_precision): "f32" on the bilinear critic is the bf16x3
-    scheme where every size is a multiple of 8 (fp32 tolerances at a sixth of the time), exact fp32 products otherwise and
-    under "f32_exact" -- so that a precision name means the same numerics and speed on one GPU and on a sharded batch."""
-    from .mi_critics import _precision_code
-    if critic == "bilinear" and x.dim() == 2 and y.dim() == 2:
-        return _hip.resolve_precision(precision, True, (x.shape[0], x.shape[1], y.shape[1]))
-    if critic == "concat_mlp" and params is not None and len(params) == 6:
-        return _hip.resolve_precision(precision, False, concat_hidden=(params[0].shape[0], params[2].shape[0]))
-    return _precision_code(precision)
-
-
 def global_batch_mi_bound(embedding_img, embedding_txt, study_id_codes, critic_params: Sequence[torch.Tensor],
                           estimator: str = "infonce", precision: str = "bf16", critic: str = "bilinear", group=None,
                           ops=None, return_stats: bool = False):
@@ -458,11 +187,14 @@ def global_batch_mi_bound(embedding_img, embedding_txt, study_id_codes, critic_p
     ``study_id_codes``: int64 tensor [B/G] (codes must be consistent across ranks, e.g. the integer study ids).
     Every rank returns the same loss; ``.backward()`` leaves the gradient of the global loss w.r.t. the local
     embeddings and the (all-reduced) gradient w.r.t. the critic parameters."""
-    from .mi_critics import _estimator_code, _precision_code
+    from .mi_critics import _estimator_code
     if ops is None:
-        ops = {"bilinear": HipBilinearOps, "separable": HipSeparableOps, "concat_mlp": HipConcatMlpOps}[critic]()
+        ops = OPS[critic]()
     est = _estimator_code(estimator)
-    prec = _sharded_precision(precision, critic, embedding_img, embedding_txt, critic_params)
+    # the same name -> code resolution as on one GPU, except that the bf16x3 condition looks at this rank's row count
+    # rather than at the global batch (kept as it is; tests/test_critic_resolution.py pins it)
+    prec = resolve_critic(critic, precision, embedding_img.shape[0], embedding_img.shape[1], embedding_txt.shape[1],
+                          critic_params)[2]
     loss, stats = GlobalBatchCriticFn.apply(ops, group, est, prec, study_id_codes, embedding_img, embedding_txt,
                                             *critic_params)
     loss = loss if estimator == "dv" else loss.reshape(())
@@ -491,7 +223,7 @@ class GlobalBatchGraphStep:
 
     def __init__(self, x, y, sid, params: Sequence[torch.Tensor], estimator: str = "infonce", precision: str = "bf16",
                  critic: str = "bilinear", group=None, ops=None, capture: bool = True, overlap_reduce_scatter=None):
-        from .mi_critics import _estimator_code, _precision_code
+        from .mi_critics import _estimator_code
         self.group = group
         # step_eager(): start the reduce-scatter of dY between the backward's two launches (it then runs beside dW).  OFF by
         # default: with direct calls the step is bound by the HOST (one-rank RCCL rehearsal, B = 4096: 0.196 ms per step
@@ -501,8 +233,9 @@ class GlobalBatchGraphStep:
                                        else bool(overlap_reduce_scatter))
         self.world = dist.get_world_size(group)
         self.rank = dist.get_rank(group)
-        self.ops = ops if ops is not None else {"bilinear": HipBilinearOps, "separable": HipSeparableOps, "concat_mlp": HipConcatMlpOps}[critic]()
-        self.est, self.prec = _estimator_code(estimator), _sharded_precision(precision, critic, x, y, params)
+        self.ops = ops if ops is not None else OPS[critic]()
+        self.est = _estimator_code(estimator)
+        self.prec = resolve_critic(critic, precision, x.shape[0], x.shape[1], y.shape[1], params)[2]  # as above
         self.x, self.y, self.sid = x.detach(), y.detach(), sid
         self.params = [p.detach() for p in params]
         for t in (self.x, self.y, self.sid, *self.params):

@@ -6,8 +6,8 @@ launches of one forward and of one backward into two hipGraphs, ONCE, for fixed 
 
 * nothing of autograd is inside a capture (a backward captured through ``loss.backward()`` drags ``AccumulateGrad``
   nodes of whatever stream created the leaves into the capture; that is how round 1's benchmark managed to abort inside
-  ``capture_end``).  The captures hold exactly the library calls of ``mi_critics.BilinearCriticFn`` /
-  ``ConcatMlpCriticFn``;
+  ``capture_end``).  The captures hold the C-ABI calls of the critic's ops object (``critic_ops``), bound once to
+  static buffers -- the same calls the eager ``mi_critics.fused_mi_bound`` makes;
 * ``step()`` replays both graphs on the static buffers (benchmarks, custom loops);
 * ``loss(embedding_img, embedding_txt, study_id)`` returns a loss that is connected to autograd through a thin
   ``torch.autograd.Function``: forward = copy the embeddings into the static buffers + replay graph 1, backward = copy
@@ -19,12 +19,13 @@ The critic's parameters are read IN PLACE on every replay (optimizers update the
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+from typing import Optional
 
 import torch
 
 from . import _hip, mi_critics
-from .mi_critics import _concat_params, _estimator_code, _precision_code
+from .critic_ops import OPS, resolve_critic
+from .mi_critics import _estimator_code
 
 
 class GraphedMiStep:
@@ -34,33 +35,16 @@ class GraphedMiStep:
         embeddings -- what the encoders emit under autocast -- and returns their gradients in bfloat16
         (``mi_bilinear_step_bf16``: the same bits as the fp32 boundary fed the same values, without the 25 MB of
         conversion traffic per step at B = 4096, d = 512).  The critic's parameters and their gradients stay float32."""
-        from . import model as _model
         self.device = torch.device(device if device is not None else "cuda")
         if self.device.type != "cuda":
             raise _hip.MiCriticError("GraphedMiStep needs a ROCm device (no CPU fallback)")
         self.lib = _hip.load()
-        self.est, self.prec = _estimator_code(estimator), _precision_code(precision)
+        self.est = _estimator_code(estimator)
         self.estimator = estimator
         self.b, self.dx, self.dy = int(batch_size), int(d_img), int(d_txt)
         dev = self.device
-        if isinstance(critic, _model.BilinearCritic):
-            self.kind = "bilinear"
-            self.params: List[torch.Tensor] = [critic.weight]
-            self.prec = _hip.resolve_precision(precision, True, (self.b, self.dx, self.dy))  # "f32" -> bf16x3 here
-        elif isinstance(critic, _model.SeparableCritic):
-            self.kind = "separable"  # S = (X Wg)(Y Wh)^T: projections, B x B stage and gradients by mi_separable_fwd/bwd
-            self.params = [critic.wg, critic.wh]
-            self.k = int(critic.wg.shape[1])
-        elif critic is None:
-            if d_img != d_txt:
-                raise ValueError("critic=None is the separable form S = X Y^T: widths must agree")
-            self.kind = "bilinear"
-            self.params = []
-        else:
-            self.kind = "concat_mlp"
-            w1, b1, w2, b2, w3, b3 = _concat_params(critic)
-            self.params = [w1, b1, w2, b2, w3, b3]
-            self.prec = _hip.resolve_precision(precision, False, concat_hidden=(w1.shape[0], w2.shape[0]))  # "f32" -> f16x3
+        # critic=None: S = X Y^T through the bilinear entry points; concat: "f32" -> f16x3 on the fused hidden sizes
+        self.kind, self.params, self.prec = resolve_critic(critic, precision, self.b, self.dx, self.dy)
         for p in self.params:
             if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
                 raise ValueError("critic parameters must be contiguous float32 tensors on the step's device")
@@ -86,22 +70,24 @@ class GraphedMiStep:
         self.grad_y = torch.zeros_like(self.y)
         self.grad_params = [torch.zeros_like(p) for p in self.params]
         self.path = None
-        if self.kind == "bilinear":
-            if self.params:
-                self.path = _hip.note_path("bilinear", (self.b, self.b, self.dx, self.dy), self.prec)
-            nbytes = self.lib.mi_bilinear_workspace_bytes(self.b, self.b, self.dx, self.dy, self.prec)
+        if self.kind == "bilinear" and self.params:
+            self.path = _hip.note_path("bilinear", (self.b, self.b, self.dx, self.dy), self.prec)
         elif self.kind == "separable":
-            if tuple(self.params[0].shape) != (self.dx, self.k) or tuple(self.params[1].shape) != (self.dy, self.k):
-                raise ValueError("projection shapes must be [d_img, d_proj] and [d_txt, d_proj]")
-            self.path = _hip.note_path("separable", (self.b, self.b, self.dx, self.dy, self.k), self.prec)
-            nbytes = self.lib.mi_separable_workspace_bytes(self.b, self.b, self.dx, self.dy, self.k, self.prec)
-        else:
-            self.h1, self.h2 = self.params[0].shape[0], self.params[2].shape[0]
-            if self.params[0].shape[1] != self.dx + self.dy:
-                raise ValueError("critic input width does not match d_img + d_txt")
-            nbytes = self.lib.mi_concat_mlp_workspace_bytes(self.b, self.b, self.dx, self.dy, self.h1, self.h2, self.prec, 1)
-            self.scores = torch.zeros(self.b, self.b, dtype=torch.float32, device=dev)
-        self.ws = _hip.workspace(nbytes, dev)
+            self.path = _hip.note_path("separable", (self.b, self.b, self.dx, self.dy, self.params[0].shape[1]), self.prec)
+        self.scores = torch.zeros(self.b, self.b, dtype=torch.float32, device=dev) if self.kind == "concat_mlp" else None
+        ops = OPS[self.kind]()
+        self.ws = _hip.workspace(ops.workspace_bytes(self.b, self.b, self.dx, self.dy, self.params, self.prec, 1), dev)
+        # the C-ABI calls of a step, bound once to the static buffers (the critic's parameters are read in place)
+        out = (self.loss_buf, self.stats, self.record, self.scores)
+        grads = (self.grad_x, self.grad_y, self.grad_params)
+        saved = (self.x, self.y, self.params, self.sid, self.sid, 0, self.prec, self.scores, self.ws)
+        self._fwd_call = ops.fwd_call(self.x, self.y, self.params, self.sid, self.sid, 0, self.est, self.prec, 1, out,
+                                      self.ws)
+        self._bwd_call = ops.bwd_call(saved, self.stats, self.grad_out, grads)
+        self._step_call = None  # the concat-MLP critic has no one-call step: forward + backward
+        if self.kind != "concat_mlp":
+            self._step_call = ops.step_call(self.x, self.y, self.params, self.sid, self.est, self.prec, self.grad_out,
+                                            out, grads, self.ws)
         self.graph_fwd: Optional[torch.cuda.CUDAGraph] = None
         self.graph_bwd: Optional[torch.cuda.CUDAGraph] = None
         self.graph_step: Optional[torch.cuda.CUDAGraph] = None
@@ -113,72 +99,22 @@ class GraphedMiStep:
             self._capture()
 
     # ------------------------------------------------------------------------------------------ raw C-ABI calls
-    def _w3_flat(self):
-        return self.params[4].reshape(-1)  # [1, h2] -> [h2], a view of the parameter's storage
-
     def _fwd(self):
-        p = self.params
         if self.boundary == "bf16":
             raise _hip.MiCriticError('boundary="bf16" has the one-call step only (step() / step_eager() / loss())')
-        if self.kind == "bilinear":
-            _hip.call("mi_bilinear_fwd", self.device, self.x.data_ptr(), self.y.data_ptr(), p[0].data_ptr() if p else None,
-                      self.sid.data_ptr(), self.sid.data_ptr(), self.b, self.b, 0, self.dx, self.dy, self.est, self.prec, 1,
-                      self.loss_buf.data_ptr(), self.stats.data_ptr(), self.record.data_ptr(), None, self.ws.data_ptr(),
-                      self.ws.numel())
-        elif self.kind == "separable":
-            _hip.call("mi_separable_fwd", self.device, self.x.data_ptr(), self.y.data_ptr(), p[0].data_ptr(), p[1].data_ptr(),
-                      self.sid.data_ptr(), self.sid.data_ptr(), self.b, self.b, 0, self.dx, self.dy, self.k, self.est,
-                      self.prec, 1, self.loss_buf.data_ptr(), self.stats.data_ptr(), self.record.data_ptr(),
-                      self.ws.data_ptr(), self.ws.numel())
-        else:
-            _hip.call("mi_concat_mlp_fwd", self.device, self.x.data_ptr(), self.y.data_ptr(), p[0].data_ptr(),
-                      p[1].data_ptr(), p[2].data_ptr(), p[3].data_ptr(), p[4].data_ptr(), p[5].data_ptr(),
-                      self.sid.data_ptr(), self.sid.data_ptr(), self.b, self.b, 0, self.dx, self.dy, self.h1, self.h2,
-                      self.est, self.prec, 1, self.loss_buf.data_ptr(), self.stats.data_ptr(), self.record.data_ptr(),
-                      self.scores.data_ptr(), self.ws.data_ptr(), self.ws.numel())
+        self._fwd_call()
 
     def _bwd(self):
-        p, g = self.params, self.grad_params
-        if self.kind == "bilinear":
-            _hip.call("mi_bilinear_bwd", self.device, self.x.data_ptr(), self.y.data_ptr(), p[0].data_ptr() if p else None,
-                      self.sid.data_ptr(), self.sid.data_ptr(), self.b, self.b, 0, self.dx, self.dy, self.prec,
-                      self.stats.data_ptr(), self.grad_out.data_ptr(), self.grad_x.data_ptr(), self.grad_y.data_ptr(),
-                      g[0].data_ptr() if g else None, self.ws.data_ptr(), self.ws.numel(), 1)
-        elif self.kind == "separable":
-            _hip.call("mi_separable_bwd", self.device, self.x.data_ptr(), self.y.data_ptr(), p[0].data_ptr(), p[1].data_ptr(),
-                      self.sid.data_ptr(), self.sid.data_ptr(), self.b, self.b, 0, self.dx, self.dy, self.k, self.prec,
-                      self.stats.data_ptr(), self.grad_out.data_ptr(), self.grad_x.data_ptr(), self.grad_y.data_ptr(),
-                      g[0].data_ptr(), g[1].data_ptr(), self.ws.data_ptr(), self.ws.numel(), 1)
-        else:
-            _hip.call("mi_concat_mlp_bwd", self.device, self.x.data_ptr(), self.y.data_ptr(), p[0].data_ptr(),
-                      p[1].data_ptr(), p[2].data_ptr(), p[3].data_ptr(), p[4].data_ptr(), p[5].data_ptr(),
-                      self.sid.data_ptr(), self.sid.data_ptr(), self.b, self.b, 0, self.dx, self.dy, self.h1, self.h2,
-                      self.prec, self.stats.data_ptr(), self.grad_out.data_ptr(), self.scores.data_ptr(),
-                      self.grad_x.data_ptr(), self.grad_y.data_ptr(), *[t.data_ptr() for t in g], self.ws.data_ptr(),
-                      self.ws.numel())
+        self._bwd_call()
 
     def _step(self):
         """Forward + backward as ONE C-ABI call where the library has one (bilinear critic: mi_bilinear_step, four launches
         and no finalize kernel); the two calls otherwise."""
-        p, g = self.params, self.grad_params
-        if self.boundary == "bf16":
-            _hip.call("mi_bilinear_step_bf16", self.device, self.x.data_ptr(), self.y.data_ptr(), p[0].data_ptr(),
-                      self.sid.data_ptr(), self.b, self.dx, self.dy, self.est, self.grad_out.data_ptr(),
-                      self.loss_buf.data_ptr(), self.stats.data_ptr(), self.record.data_ptr(), self.grad_x.data_ptr(),
-                      self.grad_y.data_ptr(), 1, g[0].data_ptr(), self.ws.data_ptr(), self.ws.numel())
-        elif self.kind == "bilinear":
-            _hip.call("mi_bilinear_step", self.device, self.x.data_ptr(), self.y.data_ptr(), p[0].data_ptr() if p else None,
-                      self.sid.data_ptr(), self.b, self.dx, self.dy, self.est, self.prec, self.grad_out.data_ptr(),
-                      self.loss_buf.data_ptr(), self.stats.data_ptr(), self.record.data_ptr(), self.grad_x.data_ptr(),
-                      self.grad_y.data_ptr(), g[0].data_ptr() if g else None, self.ws.data_ptr(), self.ws.numel())
-        elif self.kind == "separable":
-            _hip.call("mi_separable_step", self.device, self.x.data_ptr(), self.y.data_ptr(), p[0].data_ptr(), p[1].data_ptr(),
-                      self.sid.data_ptr(), self.b, self.dx, self.dy, self.k, self.est, self.prec, self.grad_out.data_ptr(),
-                      self.loss_buf.data_ptr(), self.stats.data_ptr(), self.record.data_ptr(), self.grad_x.data_ptr(),
-                      self.grad_y.data_ptr(), g[0].data_ptr(), g[1].data_ptr(), self.ws.data_ptr(), self.ws.numel())
+        if self._step_call is None:
+            self._fwd_call()
+            self._bwd_call()
         else:
-            self._fwd()
-            self._bwd()
+            self._step_call()
 
     def _capture(self):
         # warm-up on a side stream: module loading and the one-time kernel-attribute calls must not fall into a capture

@@ -25,7 +25,9 @@ from typing import Optional, Sequence, Union
 import torch
 
 from . import _hip
-from ._hip import ESTIMATORS, NCE_ESTIMATORS, PRECISIONS
+from ._hip import ESTIMATORS, NCE_ESTIMATORS
+from .critic_ops import (HipBilinearOps, HipConcatMlpOps, HipSeparableOps, _concat_params,  # noqa: F401 (re-exported)
+                         _precision_code, fwd_outputs, resolve_critic)
 
 __all__ = ["dv_bound_loss", "infonce_bound_loss", "matrix_bound_loss", "fused_mi_bound", "study_id_codes",
            "BilinearCriticFn", "SeparableCriticFn", "ConcatMlpCriticFn", "NceBilinearFn", "NceSeparableFn",
@@ -63,12 +65,6 @@ def check_estimator(estimator: str, critic_kind: str) -> None:
     if estimator not in ESTIMATORS:
         raise ValueError(f"unknown mi_estimator {estimator!r}: expected one of "
                          f"{sorted(ESTIMATORS) + sorted(NCE_ESTIMATORS)}")
-
-
-def _precision_code(precision: str) -> int:
-    if precision not in PRECISIONS:
-        raise ValueError(f"unknown precision {precision!r}: expected one of {sorted(PRECISIONS)}")
-    return PRECISIONS[precision]
 
 
 def _grad_scalar(grad: torch.Tensor) -> torch.Tensor:
@@ -208,94 +204,58 @@ def matrix_bound_loss(scores: torch.Tensor, study_id, estimator: str = "dv") -> 
 
 
 # ----------------------------------------------------------------------------------------------------------
-# fused critics
+# fused critics: thin autograd Functions over the ops objects of critic_ops (whole batch: b_rows = b, row_offset = 0)
 # ----------------------------------------------------------------------------------------------------------
+def _critic_forward(ctx, ops, x, y, params, sid, estimator, precision, scores):
+    loss, stats, _, scores = out = fwd_outputs(x.device, scores)
+    _, saved = ops.forward(x, y, params, sid, sid, 0, estimator, precision, any(ctx.needs_input_grad), out=out)
+    ctx.save_for_backward(x, y, sid, stats, scores, saved[-1], *params)
+    ctx.ops, ctx.precision = ops, precision
+    ctx.mark_non_differentiable(*[t for t in (stats, scores) if t is not None])
+    return loss, stats, scores
+
+
+def _critic_backward(ctx, grad_loss):
+    """(grad_x, grad_y, [grad_params...]) of grad_loss * loss."""
+    x, y, sid, stats, scores, ws, *params = ctx.saved_tensors
+    return ctx.ops.backward((x, y, params, sid, sid, 0, ctx.precision, scores, ws), stats, _grad_scalar(grad_loss))
+
+
 class BilinearCriticFn(torch.autograd.Function):
-    """loss = bound(S), S = (X W) Y^T with study-id masking; all gradients by the HIP backward."""
+    """loss = bound(S), S = (X W) Y^T (W None: X Y^T) with study-id masking; all gradients by the HIP backward."""
 
     @staticmethod
     def forward(ctx, x, y, w, sid, estimator: int, precision: int, want_scores: bool):
-        lib = _hip.load()
-        x = _hip.f32c(x, "embedding_img")
-        y = _hip.f32c(y, "embedding_txt")
-        w = None if w is None else _hip.f32c(w, "bilinear weight")
-        b, dx = x.shape
-        dy = y.shape[1]
-        dev = x.device
-        if w is not None:
-            _hip.note_path("bilinear", (b, b, dx, dy), precision)
-        ws = _hip.workspace(lib.mi_bilinear_workspace_bytes(b, b, dx, dy, precision), dev)
-        stats = _hip.new_stats(dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        record = torch.empty(_hip.RECORD_FLOATS, dtype=torch.float32, device=dev)
-        scores = torch.empty(b, b, dtype=torch.float32, device=dev) if want_scores else None
-        need_grad = 1 if any(ctx.needs_input_grad[:3]) else 0
-        _hip.call("mi_bilinear_fwd", dev, x.data_ptr(), y.data_ptr(), _hip.ptr(w), sid.data_ptr(), sid.data_ptr(), b, b, 0,
-                                       dx, dy, estimator, precision, need_grad, loss.data_ptr(), stats.data_ptr(),
-                                       record.data_ptr(), _hip.ptr(scores), ws.data_ptr(), ws.numel())
-        ctx.save_for_backward(x, y, sid, stats, ws, *([] if w is None else [w]))
-        ctx.precision = precision
-        ctx.mark_non_differentiable(stats)
-        if want_scores:
-            ctx.mark_non_differentiable(scores)
-            return loss, stats, scores
-        return loss, stats, None
+        x, y = _hip.f32c(x, "embedding_img"), _hip.f32c(y, "embedding_txt")
+        params = [] if w is None else [_hip.f32c(w, "bilinear weight")]
+        b = x.shape[0]
+        if params:
+            _hip.note_path("bilinear", (b, b, x.shape[1], y.shape[1]), precision)
+        scores = torch.empty(b, b, dtype=torch.float32, device=x.device) if want_scores else None
+        return _critic_forward(ctx, HipBilinearOps(), x, y, params, sid, estimator, precision, scores)
 
     @staticmethod
     def backward(ctx, grad_loss, _gs, _gsc):
-        lib = _hip.load()
-        x, y, sid, stats, ws, *rest = ctx.saved_tensors
-        w = rest[0] if rest else None
-        b, dx = x.shape
-        dy = y.shape[1]
-        go = _grad_scalar(grad_loss)
-        gx, gy = torch.empty_like(x), torch.empty_like(y)
-        gw = None if w is None else torch.empty_like(w)
-        _hip.call("mi_bilinear_bwd", x.device, x.data_ptr(), y.data_ptr(), _hip.ptr(w), sid.data_ptr(), sid.data_ptr(), b, b, 0,
-                                       dx, dy, ctx.precision, stats.data_ptr(), go.data_ptr(), gx.data_ptr(),
-                                       gy.data_ptr(), _hip.ptr(gw), ws.data_ptr(), ws.numel(), 1)
-        return gx, gy, gw, None, None, None, None
+        gx, gy, gp = _critic_backward(ctx, grad_loss)
+        return gx, gy, (gp[0] if gp else None), None, None, None, None
 
 
 class SeparableCriticFn(torch.autograd.Function):
     """loss = bound(S), S = (X Wg)(Y Wh)^T with study-id masking; projections, fused B x B stage and all gradients by
-    the HIP library (BASELINE.json configs[1])."""
+    the HIP library (BASELINE.json configs[1]).  Projection shapes are checked by ``resolve_critic``."""
 
     @staticmethod
     def forward(ctx, x, y, wg, wh, sid, estimator: int, precision: int):
-        lib = _hip.load()
         x, y = _hip.f32c(x, "embedding_img"), _hip.f32c(y, "embedding_txt")
-        wg, wh = _hip.f32c(wg, "image projection"), _hip.f32c(wh, "text projection")
-        b, dx = x.shape
-        dy, k = y.shape[1], wg.shape[1]
-        if wg.shape[0] != dx or wh.shape != (dy, k):
-            raise ValueError("projection shapes must be [d_img, d_proj] and [d_txt, d_proj]")
-        dev = x.device
-        _hip.note_path("separable", (b, b, dx, dy, k), precision)
-        ws = _hip.workspace(lib.mi_separable_workspace_bytes(b, b, dx, dy, k, precision), dev)
-        stats = _hip.new_stats(dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        record = torch.empty(_hip.RECORD_FLOATS, dtype=torch.float32, device=dev)
-        need_grad = 1 if any(ctx.needs_input_grad[:4]) else 0
-        _hip.call("mi_separable_fwd", dev, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(), sid.data_ptr(),
-                  sid.data_ptr(), b, b, 0, dx, dy, k, estimator, precision, need_grad, loss.data_ptr(), stats.data_ptr(),
-                  record.data_ptr(), ws.data_ptr(), ws.numel())
-        ctx.save_for_backward(x, y, wg, wh, sid, stats, ws)
-        ctx.precision = precision
-        ctx.mark_non_differentiable(stats)
-        return loss, stats
+        params = [_hip.f32c(wg, "image projection"), _hip.f32c(wh, "text projection")]
+        b = x.shape[0]
+        _hip.note_path("separable", (b, b, x.shape[1], y.shape[1], wg.shape[1]), precision)
+        return _critic_forward(ctx, HipSeparableOps(), x, y, params, sid, estimator, precision, None)
 
     @staticmethod
-    def backward(ctx, grad_loss, _gs):
-        x, y, wg, wh, sid, stats, ws = ctx.saved_tensors
-        b, dx = x.shape
-        dy, k = y.shape[1], wg.shape[1]
-        go = _grad_scalar(grad_loss)
-        gx, gy, gg, gh = (torch.empty_like(t) for t in (x, y, wg, wh))
-        _hip.call("mi_separable_bwd", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(), sid.data_ptr(),
-                  sid.data_ptr(), b, b, 0, dx, dy, k, ctx.precision, stats.data_ptr(), go.data_ptr(), gx.data_ptr(),
-                  gy.data_ptr(), gg.data_ptr(), gh.data_ptr(), ws.data_ptr(), ws.numel(), 1)
-        return gx, gy, gg, gh, None, None, None
+    def backward(ctx, grad_loss, _gs, _gsc):
+        gx, gy, gp = _critic_backward(ctx, grad_loss)
+        return (gx, gy, *gp, None, None, None)
 
 
 class ConcatMlpCriticFn(torch.autograd.Function):
@@ -303,43 +263,31 @@ class ConcatMlpCriticFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, w1, b1, w2, b2, w3, b3, sid, estimator: int, precision: int, want_scores: bool):
-        lib = _hip.load()
-        x = _hip.f32c(x, "embedding_img")
-        y = _hip.f32c(y, "embedding_txt")
+        x, y = _hip.f32c(x, "embedding_img"), _hip.f32c(y, "embedding_txt")
         params = [_hip.f32c(p, f"critic param {n}") for n, p in enumerate((w1, b1, w2, b2, w3, b3))]
-        b, dx = x.shape
-        dy = y.shape[1]
-        h1, h2 = params[0].shape[0], params[2].shape[0]
-        dev = x.device
-        need_grad = 1 if any(ctx.needs_input_grad[:8]) else 0
-        ws = _hip.workspace(lib.mi_concat_mlp_workspace_bytes(b, b, dx, dy, h1, h2, precision, need_grad), dev)
-        stats = _hip.new_stats(dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        record = torch.empty(_hip.RECORD_FLOATS, dtype=torch.float32, device=dev)
-        scores = torch.empty(b, b, dtype=torch.float32, device=dev)
-        _hip.call("mi_concat_mlp_fwd", dev, x.data_ptr(), y.data_ptr(), *[p.data_ptr() for p in params], sid.data_ptr(),
-                                         sid.data_ptr(), b, b, 0, dx, dy, h1, h2, estimator, precision, need_grad,
-                                         loss.data_ptr(), stats.data_ptr(), record.data_ptr(), scores.data_ptr(),
-                                         ws.data_ptr(), ws.numel())
-        ctx.save_for_backward(x, y, *params, sid, stats, scores, ws)
-        ctx.precision = precision
-        ctx.mark_non_differentiable(stats, scores)
-        return loss, stats, scores
+        scores = torch.empty(x.shape[0], x.shape[0], dtype=torch.float32, device=x.device)  # the backward reads them
+        return _critic_forward(ctx, HipConcatMlpOps(), x, y, params, sid, estimator, precision, scores)
 
     @staticmethod
     def backward(ctx, grad_loss, _gs, _gsc):
-        lib = _hip.load()
-        x, y, w1, b1, w2, b2, w3, b3, sid, stats, scores, ws = ctx.saved_tensors
-        b, dx = x.shape
-        dy = y.shape[1]
-        h1, h2 = w1.shape[0], w2.shape[0]
-        go = _grad_scalar(grad_loss)
-        grads = [torch.empty_like(t) for t in (x, y, w1, b1, w2, b2, w3, b3)]
-        _hip.call("mi_concat_mlp_bwd", x.device, x.data_ptr(), y.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
-                                         b2.data_ptr(), w3.data_ptr(), b3.data_ptr(), sid.data_ptr(), sid.data_ptr(), b,
-                                         b, 0, dx, dy, h1, h2, ctx.precision, stats.data_ptr(), go.data_ptr(),
-                                         scores.data_ptr(), *[g.data_ptr() for g in grads], ws.data_ptr(), ws.numel())
-        return (*grads, None, None, None, None)
+        gx, gy, gp = _critic_backward(ctx, grad_loss)
+        return (gx, gy, *gp, None, None, None, None)
+
+
+def _nce_forward(ctx, ops, x, y, params, sid, mode, precision, need_grad):
+    loss, r, c, grads = ops.nce_step(x, y, params, sid, mode, precision, need_grad)
+    ctx.save_for_backward(*grads)
+    ctx.mark_non_differentiable(r, c)
+    return loss, r, c
+
+
+def _nce_backward(ctx, grad_loss, name):
+    """The gradients the forward call wrote for dL/dloss = 1, scaled by grad_loss."""
+    saved = ctx.saved_tensors
+    if not saved:
+        raise RuntimeError(f"{name}: the forward ran without gradients (need_grad=False)")
+    go = grad_loss.reshape(-1)[:1].to(torch.float32)
+    return (*(g * go for g in saved), *[None] * (len(ctx.needs_input_grad) - len(saved)))
 
 
 class NceBilinearFn(torch.autograd.Function):
@@ -349,36 +297,13 @@ class NceBilinearFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, w, sid, mode: int, precision: int, need_grad: bool):
-        lib = _hip.load()
-        x = _hip.f32c(x, "embedding_img")
-        y = _hip.f32c(y, "embedding_txt")
-        w = None if w is None else _hip.f32c(w, "bilinear weight")
-        b, dx = x.shape
-        dy = y.shape[1]
-        dev = x.device
-        ws = _hip.workspace(lib.mi_nce_bilinear_workspace_bytes(b, dx, dy, precision), dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        r = torch.empty(b, dtype=torch.float32, device=dev)
-        c = torch.empty(b, dtype=torch.float32, device=dev)
-        gx = torch.empty_like(x) if need_grad else None
-        gy = torch.empty_like(y) if need_grad else None
-        gw = torch.empty_like(w) if need_grad and w is not None else None
-        _hip.call("mi_nce_bilinear_step", dev, x.data_ptr(), y.data_ptr(), _hip.ptr(w), sid.data_ptr(), b, dx, dy, mode,
-                  precision, None, loss.data_ptr(), r.data_ptr(), c.data_ptr(), _hip.ptr(gx), _hip.ptr(gy), _hip.ptr(gw),
-                  ws.data_ptr(), ws.numel())
-        ctx.save_for_backward(*[g for g in (gx, gy, gw) if g is not None])
-        ctx.mark_non_differentiable(r, c)
-        return loss, r, c
+        x, y = _hip.f32c(x, "embedding_img"), _hip.f32c(y, "embedding_txt")
+        params = [] if w is None else [_hip.f32c(w, "bilinear weight")]
+        return _nce_forward(ctx, HipBilinearOps(), x, y, params, sid, mode, precision, need_grad)
 
     @staticmethod
     def backward(ctx, grad_loss, _gr, _gc):
-        saved = ctx.saved_tensors
-        if not saved:
-            raise RuntimeError("NceBilinearFn: the forward ran without gradients (need_grad=False)")
-        go = grad_loss.reshape(-1)[:1].to(torch.float32)
-        gx, gy = saved[0] * go, saved[1] * go
-        gw = saved[2] * go if len(saved) > 2 else None
-        return gx, gy, gw, None, None, None, None
+        return _nce_backward(ctx, grad_loss, "NceBilinearFn")
 
 
 class NceSeparableFn(torch.autograd.Function):
@@ -386,36 +311,26 @@ class NceSeparableFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, wg, wh, sid, mode: int, precision: int, need_grad: bool):
-        lib = _hip.load()
         x, y = _hip.f32c(x, "embedding_img"), _hip.f32c(y, "embedding_txt")
-        wg, wh = _hip.f32c(wg, "image projection"), _hip.f32c(wh, "text projection")
-        b, dx = x.shape
-        dy, k = y.shape[1], wg.shape[1]
-        if wg.shape[0] != dx or wh.shape != (dy, k):
-            raise ValueError("projection shapes must be [d_img, d_proj] and [d_txt, d_proj]")
-        dev = x.device
-        ws = _hip.workspace(lib.mi_nce_separable_workspace_bytes(b, dx, dy, k, precision), dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        r = torch.empty(b, dtype=torch.float32, device=dev)
-        c = torch.empty(b, dtype=torch.float32, device=dev)
-        grads = [torch.empty_like(t) for t in (x, y, wg, wh)] if need_grad else [None] * 4
-        _hip.call("mi_nce_separable_step", dev, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(), sid.data_ptr(),
-                  b, dx, dy, k, mode, precision, None, loss.data_ptr(), r.data_ptr(), c.data_ptr(),
-                  *[_hip.ptr(g) for g in grads], ws.data_ptr(), ws.numel())
-        ctx.save_for_backward(*[g for g in grads if g is not None])
-        ctx.mark_non_differentiable(r, c)
-        return loss, r, c
+        params = [_hip.f32c(wg, "image projection"), _hip.f32c(wh, "text projection")]
+        return _nce_forward(ctx, HipSeparableOps(), x, y, params, sid, mode, precision, need_grad)
 
     @staticmethod
     def backward(ctx, grad_loss, _gr, _gc):
-        saved = ctx.saved_tensors
-        if not saved:
-            raise RuntimeError("NceSeparableFn: the forward ran without gradients (need_grad=False)")
-        go = grad_loss.reshape(-1)[:1].to(torch.float32)
-        return (*(g * go for g in saved), None, None, None, None)
+        return _nce_backward(ctx, grad_loss, "NceSeparableFn")
 
 
-def _fused_nce(embedding_img, embedding_txt, study_id, critic, estimator, precision, return_scores, return_stats):
+def _batch_codes(embedding_img, embedding_txt, study_id) -> torch.Tensor:
+    """Shape checks of one batch; its study-id codes."""
+    if embedding_img.dim() != 2 or embedding_txt.dim() != 2 or embedding_img.shape[0] != embedding_txt.shape[0]:
+        raise ValueError("embedding_img / embedding_txt must be [B, d_img] / [B, d_txt]")
+    sid = study_id_codes(study_id, embedding_img.device)
+    if sid.numel() != embedding_img.shape[0]:
+        raise ValueError("study_id length must equal the batch size")
+    return sid
+
+
+def _fused_nce(x, y, study_id, critic, estimator, precision, return_scores, return_stats):
     """fused_mi_bound for "infonce_rowwise" / "infonce_symmetric"."""
     from . import model as _model
 
@@ -423,46 +338,25 @@ def _fused_nce(embedding_img, embedding_txt, study_id, critic, estimator, precis
         raise ValueError(f"mi_estimator {estimator!r} is implemented for BilinearCritic and SeparableCritic only; for "
                          "scores you compute yourself (e.g. a make_mlp critic applied to every pair) use "
                          "matrix_bound_loss(scores, study_id, estimator)")
-    if embedding_img.dim() != 2 or embedding_txt.dim() != 2 or embedding_img.shape[0] != embedding_txt.shape[0]:
-        raise ValueError("embedding_img / embedding_txt must be [B, d_img] / [B, d_txt]")
-    sid = study_id_codes(study_id, embedding_img.device)
-    if sid.numel() != embedding_img.shape[0]:
-        raise ValueError("study_id length must equal the batch size")
-    mode = NCE_ESTIMATORS[estimator]
-    b, dx, dy = embedding_img.shape[0], embedding_img.shape[1], embedding_txt.shape[1]
-    bilinear = isinstance(critic, _model.BilinearCritic)
+    sid = _batch_codes(x, y, study_id)
     # "f32": bf16x3 on the bilinear critic where every size is a multiple of 8, exact fp32 products otherwise (the library
     # rejects fp8 / f16 / f16x3 for this loss)
-    prec = _hip.resolve_precision(precision, bilinear, (b, dx, dy))
-    params = (critic.weight,) if bilinear else (critic.wg, critic.wh)
-    need_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (embedding_img, embedding_txt) + params)
-    if bilinear:
-        loss, r, c = NceBilinearFn.apply(embedding_img, embedding_txt, critic.weight, sid, mode, prec, need_grad)
-    else:
-        loss, r, c = NceSeparableFn.apply(embedding_img, embedding_txt, critic.wg, critic.wh, sid, mode, prec, need_grad)
+    kind, params, prec = resolve_critic(critic, precision, x.shape[0], x.shape[1], y.shape[1])
+    need_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, *params))
+    fn = NceBilinearFn if kind == "bilinear" else NceSeparableFn
+    loss, r, c = fn.apply(x, y, *params, sid, NCE_ESTIMATORS[estimator], prec, need_grad)
     out = [loss.reshape(())]
     if return_scores:  # diagnostic output, as for the reference's estimators: no gradient flows through it
         with torch.no_grad():
-            if bilinear:
-                s = BilinearCriticFn.apply(embedding_img, embedding_txt, critic.weight, sid, _hip.MI_DV, prec, True)[2]
+            if kind == "bilinear":
+                s = BilinearCriticFn.apply(x, y, critic.weight, sid, _hip.MI_DV, prec, True)[2]
             else:
-                a, cc = critic.project_img(embedding_img), critic.project_txt(embedding_txt)
-                s = BilinearCriticFn.apply(a, cc, None, sid, _hip.MI_DV, prec, True)[2]
+                s = BilinearCriticFn.apply(critic.project_img(x), critic.project_txt(y), None, sid, _hip.MI_DV, prec,
+                                           True)[2]
         out.append(s)
     if return_stats:
         out.append((r, c))
     return out[0] if len(out) == 1 else tuple(out)
-
-
-def _concat_params(critic):
-    """(W1,b1,W2,b2,W3,b3) of an nn.Sequential built by make_mlp(input_dim,[h1,h2]) (reference model.py:18-32)."""
-    mods = list(critic)
-    lin = [m for m in mods if isinstance(m, torch.nn.Linear)]
-    act = [m for m in mods if not isinstance(m, torch.nn.Linear)]
-    if len(lin) != 3 or len(mods) != 5 or not all(isinstance(a, torch.nn.ReLU) for a in act) or lin[2].out_features != 1:
-        raise ValueError("the fused concat-MLP path supports make_mlp(input_dim, [h1, h2]) critics "
-                         "(Linear-ReLU-Linear-ReLU-Linear(->1)); use create_mi_pairs + the critic module otherwise")
-    return lin[0].weight, lin[0].bias, lin[1].weight, lin[1].bias, lin[2].weight, lin[2].bias
 
 
 def fused_mi_bound(embedding_img: torch.Tensor, embedding_txt: torch.Tensor, study_id, critic, estimator: str = "dv",
@@ -494,8 +388,6 @@ def fused_mi_bound(embedding_img: torch.Tensor, embedding_txt: torch.Tensor, stu
     ``return_stats=True`` then gives ``(lse_rows, lse_cols)``, the row and column log-sum-exps.  A make_mlp critic raises
     ValueError: apply it to the pairs yourself and call ``matrix_bound_loss(scores, study_id, estimator)``.
     """
-    from . import model as _model  # local import: model.py imports nothing from here
-
     _hip.require_device(embedding_img, "embedding_img")
     _hip.require_device(embedding_txt, "embedding_txt")
     if embedding_img.dtype == torch.float64:
@@ -505,38 +397,26 @@ def fused_mi_bound(embedding_img: torch.Tensor, embedding_txt: torch.Tensor, stu
     if estimator in NCE_ESTIMATORS:
         return _fused_nce(embedding_img, embedding_txt, study_id, critic, estimator, precision, return_scores, return_stats)
     code = _estimator_code(estimator)
-    prec = _precision_code(precision)
-    if isinstance(critic, _model.BilinearCritic) and embedding_img.dim() == 2 and embedding_txt.dim() == 2:
-        # "f32" on the bilinear critic: fp32-grade results from three bf16 MFMAs per product (_hip.resolve_precision)
-        prec = _hip.resolve_precision(precision, True, (embedding_img.shape[0], embedding_img.shape[1], embedding_txt.shape[1]))
-    if embedding_img.dim() != 2 or embedding_txt.dim() != 2 or embedding_img.shape[0] != embedding_txt.shape[0]:
-        raise ValueError("embedding_img / embedding_txt must be [B, d_img] / [B, d_txt]")
-    sid = study_id_codes(study_id, embedding_img.device)
-    if sid.numel() != embedding_img.shape[0]:
-        raise ValueError("study_id length must equal the batch size")
-    if prec in (_hip.MI_PREC_BF16X3, _hip.MI_PREC_FP8) and not isinstance(critic, _model.BilinearCritic):
+    if critic is None:
+        raise TypeError("critic must be a make_mlp critic, a BilinearCritic or a SeparableCritic")
+    sid = _batch_codes(embedding_img, embedding_txt, study_id)
+    kind, params, prec = resolve_critic(critic, precision, embedding_img.shape[0], embedding_img.shape[1],
+                                        embedding_txt.shape[1])
+    if prec in (_hip.MI_PREC_BF16X3, _hip.MI_PREC_FP8) and kind != "bilinear":
         raise ValueError(f'precision="{precision}" is implemented for BilinearCritic only')
-    if prec in (_hip.MI_PREC_F16, _hip.MI_PREC_F16X3) and isinstance(critic, (_model.BilinearCritic, _model.SeparableCritic)):
+    if prec in (_hip.MI_PREC_F16, _hip.MI_PREC_F16X3) and kind != "concat_mlp":
         raise ValueError(f'precision="{precision}" is the fp16-operand mode of the make_mlp critic (its generated operand '
                          'relu(U_i + V_j) is formed by packed fp16 arithmetic); use "bf16" for this critic')
-    if isinstance(critic, _model.BilinearCritic):
-        loss, stats, scores = BilinearCriticFn.apply(embedding_img, embedding_txt, critic.weight, sid, code, prec,
+    if kind == "bilinear":
+        loss, stats, scores = BilinearCriticFn.apply(embedding_img, embedding_txt, *params, sid, code, prec,
                                                      bool(return_scores))
-    elif isinstance(critic, _model.SeparableCritic):
-        if return_scores:  # per-pair scores are a diagnostic output: eager projections + the bilinear form with W = None
-            a = critic.project_img(embedding_img)
-            c = critic.project_txt(embedding_txt)
-            loss, stats, scores = BilinearCriticFn.apply(a, c, None, sid, code, prec, True)
-        else:
-            loss, stats = SeparableCriticFn.apply(embedding_img, embedding_txt, critic.wg, critic.wh, sid, code, prec)
-            scores = None
+    elif kind == "separable" and return_scores:  # per-pair scores are a diagnostic output: eager projections + the
+        a, c = critic.project_img(embedding_img), critic.project_txt(embedding_txt)
+        loss, stats, scores = BilinearCriticFn.apply(a, c, None, sid, code, prec, True)  # bilinear form with W = None
+    elif kind == "separable":
+        loss, stats, scores = SeparableCriticFn.apply(embedding_img, embedding_txt, *params, sid, code, prec)
     else:
-        w1, b1, w2, b2, w3, b3 = _concat_params(critic)
-        # "f32" on the reference's critic: fp32-grade results from the two-part fp16 scheme (_hip.resolve_precision)
-        prec = _hip.resolve_precision(precision, False, concat_hidden=(w1.shape[0], w2.shape[0]))
-        if w1.shape[1] != embedding_img.shape[1] + embedding_txt.shape[1]:
-            raise ValueError(f"critic expects {w1.shape[1]} inputs, embeddings give "
-                             f"{embedding_img.shape[1]} + {embedding_txt.shape[1]}")
+        w1, b1, w2, b2, w3, b3 = params
         loss, stats, scores = ConcatMlpCriticFn.apply(embedding_img, embedding_txt, w1, b1, w2, b2, w3.reshape(-1), b3,
                                                       sid, code, prec, bool(return_scores))
     loss = loss if estimator == "dv" else loss.reshape(())
