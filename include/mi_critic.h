@@ -313,6 +313,49 @@ int mi_matrix_nce_fwd(const float* scores, const int64_t* sid, int64_t b, int mo
 int mi_matrix_nce_bwd(const float* scores, const int64_t* sid, int64_t b, int mode, const float* lse_rows,
                       const float* lse_cols, const float* grad_out, float* grad_scores, void* stream);
 
+/* ---- per-sample InfoNCE on a sharded batch (row blocks, global-batch normalisation) ---------------------- */
+/* Rank g of n_ranks owns rows [row_offset, row_offset + b_rows) of the global b x b matrix, row_offset = g * b_rows,
+ * b = n_ranks * b_rows: x [b_rows, d_img] and sid_rows [b_rows] are its own rows, y [b, d_txt] and sid_cols [b] every
+ * rank's (all-gathered in rank order).  Masking and loss are those above at the global b (weights 1/b).  Per step:
+ *   1. *_shard_fwd: the rank's scores, r_i of its rows (lse_rows [b_rows], optional) and its PART, part_out[P] with
+ *      P = mi_nce_part_floats(b_rows, b) = 2 b + 2 b_rows floats:
+ *        [0, 2b)                   (max, sum exp(S - max)) of column j over this rank's candidate rows, j = 0 .. b-1
+ *        [2b, 2b + b_rows)         row terms r_i - S[i, row_offset + i]
+ *        [2b + b_rows, 2b + 2 b_rows) the diagonal scores S[i, row_offset + i]
+ *      The workspace keeps what the backward needs (operand copies, T, r): pass the SAME workspace to *_shard_bwd.
+ *   2. all-gather the parts in rank order -> parts [n_ranks][P]; mi_nce_merge_parts merges every column in rank order
+ *      (c_j, lse_cols [b]) and reduces the 2b per-sample terms in a fixed order: every rank computes identical bits, and
+ *      n_ranks == 1 gives the bits of mi_nce_*_step.  Its workspace: mi_nce_merge_workspace_bytes(b).
+ *   3. *_shard_bwd with the merged lse_cols (may be NULL in MI_NCE_ROWWISE): gradients of grad_out[0] * loss.
+ *      grad_x [b_rows, d_img] is complete; grad_y [b, d_txt] and grad_w / grad_wg / grad_wh are this rank's PARTIAL sums
+ *      (reduce-scatter grad_y, all-reduce the parameter gradients).
+ * Precisions and paths as for mi_nce_*_step (16-bit chain where b_rows, b and the widths are multiples of 8). */
+size_t mi_nce_part_floats(int64_t b_rows, int64_t b);
+size_t mi_nce_bilinear_shard_workspace_bytes(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, int precision);
+int mi_nce_bilinear_shard_fwd(const float* x, const float* y, const float* w, const int64_t* sid_rows,
+                              const int64_t* sid_cols, int64_t b_rows, int64_t b, int64_t row_offset, int64_t d_img,
+                              int64_t d_txt, int mode, int precision, float* part_out, float* lse_rows, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int mi_nce_bilinear_shard_bwd(const float* x, const float* y, const float* w, const int64_t* sid_rows,
+                              const int64_t* sid_cols, int64_t b_rows, int64_t b, int64_t row_offset, int64_t d_img,
+                              int64_t d_txt, int mode, int precision, const float* lse_cols, const float* grad_out,
+                              float* grad_x, float* grad_y, float* grad_w, void* workspace, size_t workspace_bytes,
+                              void* stream);
+size_t mi_nce_merge_workspace_bytes(int64_t b);
+int mi_nce_merge_parts(const float* parts, int64_t n_ranks, int64_t b_rows, int64_t b, int mode, float* loss_out,
+                       float* lse_cols, void* workspace, size_t workspace_bytes, void* stream);
+size_t mi_nce_separable_shard_workspace_bytes(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj,
+                                              int precision);
+int mi_nce_separable_shard_fwd(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid_rows,
+                               const int64_t* sid_cols, int64_t b_rows, int64_t b, int64_t row_offset, int64_t d_img,
+                               int64_t d_txt, int64_t d_proj, int mode, int precision, float* part_out, float* lse_rows,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int mi_nce_separable_shard_bwd(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid_rows,
+                               const int64_t* sid_cols, int64_t b_rows, int64_t b, int64_t row_offset, int64_t d_img,
+                               int64_t d_txt, int64_t d_proj, int mode, int precision, const float* lse_cols,
+                               const float* grad_out, float* grad_x, float* grad_y, float* grad_wg, float* grad_wh,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1379,9 +1379,11 @@ extern "C" int mi_debug_set_stamps(void* buf) {
 // The fused B x B kernel is not used: per-row normalisation needs r_i before any row's P tile can be weighted.
 namespace mi {
 
-static bool nce_fast_ok(int64_t b, int64_t dx, int64_t dy, int precision) {
-  return (precision == MI_PREC_BF16 || precision == MI_PREC_BF16X3) && b % 8 == 0 && dx % 8 == 0 && dy % 8 == 0;
+static bool nce_fast_ok(int64_t br, int64_t b, int64_t dx, int64_t dy, int precision) {
+  return (precision == MI_PREC_BF16 || precision == MI_PREC_BF16X3) && br % 8 == 0 && b % 8 == 0 && dx % 8 == 0 &&
+         dy % 8 == 0;
 }
+static bool nce_fast_ok(int64_t b, int64_t dx, int64_t dy, int precision) { return nce_fast_ok(b, b, dx, dy, precision); }
 
 static int nce_check(const char* fn, int64_t b, int64_t dx, int64_t dy, int mode, int precision) {
   MI_CHECK_ARG(b >= 1 && dx >= 1 && dy >= 1, "%s: sizes must be >= 1 (b %lld, widths %lld, %lld)", fn, (long long)b,
@@ -1432,23 +1434,25 @@ static int nce_step_generic(const float* x, const float* y, const float* w, cons
   return generic_bwd_from_g<OpT, TG>(x, y, w, t, g, b, b, dx, dy, grad_x, grad_y, grad_w, p, st);
 }
 
-// 16-bit chain
+// 16-bit chain: bf16 operand copies and T = X W of the row block [br] against all b columns
+static int nce_prep_fast(const float* x, const float* y, const float* w, const int64_t* sid_rows, const int64_t* sid_cols,
+                         int64_t br, int64_t b, int64_t row_offset, int64_t dx, int64_t dy, const BilinearPlan& p,
+                         hipStream_t st) {
+  if (w) return fast_prep_and_t(x, y, w, sid_rows, sid_cols, br, b, row_offset, dx, dy, p, st);  // p.fl.ok is false
+  // S = X Y^T: X takes the place of T (A operand of the scores, B operand of dY = G^T T)
+  const int ra = p.x3 == 3 ? 1 : 0, rb = p.x3 == 3 ? 2 : 0;
+  CvtJobs jobs{};
+  jobs.j[0] = CvtJob{x, br, dx, p.tb, p.ttb, 0, 0, nullptr, ra, rb};
+  jobs.j[1] = CvtJob{y, b, dy, p.yb, p.ytb, 0, 0, nullptr, rb, rb};
+  return launch_cvt_transpose3(jobs, st, "nce prep X Y");
+}
+
 static int nce_step_fast(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t dx,
                          int64_t dy, int mode, const float* grad_out, float* loss_out, float* lse_rows, float* lse_cols,
                          float* grad_x, float* grad_y, float* grad_w, const NceBilinearPlan& n, hipStream_t st) {
   const BilinearPlan& p = n.p;
   const int x3 = p.x3;
-  int rc = MI_OK;
-  if (w) {
-    rc = fast_prep_and_t(x, y, w, sid, sid, b, b, 0, dx, dy, p, st);  // p.fl.ok is false: the GEMM chain's preparation
-  } else {
-    // S = X Y^T: X takes the place of T (A operand of the scores, B operand of dY = G^T T)
-    const int ra = x3 == 3 ? 1 : 0, rb = x3 == 3 ? 2 : 0;
-    CvtJobs jobs{};
-    jobs.j[0] = CvtJob{x, b, dx, p.tb, p.ttb, 0, 0, nullptr, ra, rb};
-    jobs.j[1] = CvtJob{y, b, dy, p.yb, p.ytb, 0, 0, nullptr, rb, rb};
-    rc = launch_cvt_transpose3(jobs, st, "nce prep X Y");
-  }
+  int rc = nce_prep_fast(x, y, w, sid, sid, b, b, 0, dx, dy, p, st);
   if (rc) return rc;
   const GemmBf16Args scores = one_problem(p.tb, x3 * dy, p.yb, x3 * dy, b, b, x3 * dy);
   rc = launch_gemm_bf16(scores, 1, EpiNceStats<true>{nce_stats_out(n.q, sid)}, st, "nce score + row / column records");
@@ -1490,6 +1494,126 @@ static NceSeparablePlan plan_nce_separable(Workspace& ws, int64_t b, int64_t k, 
   s.n = plan_nce_bilinear(ws, b, k, k, precision);
   s.bytes = ws.off;
   return s;
+}
+
+// ------------------------------------------------------------------------------------------------ row blocks (sharded)
+// A rank's row block [br] x [b]: the forward leaves T / the operand copies, the records and r in
+// its workspace and writes the rank's part; the caller gathers the parts, mi_nce_merge_parts gives c and the loss; the
+// backward reads r and the operands from the same workspace and the merged c from the caller.  br == b, row_offset == 0
+// issues exactly the launches (and bits) of the whole-batch step plus the two small part / merge kernels.
+struct NceShardBilinearPlan {
+  BilinearPlan p;
+  NceShardPlan q;
+  size_t bytes;
+};
+static NceShardBilinearPlan plan_nce_shard_bilinear(Workspace& ws, int64_t br, int64_t b, int64_t dx, int64_t dy,
+                                                    int precision) {
+  NceShardBilinearPlan n{};
+  n.p = plan_bilinear(ws, br, b, dx, dy, precision, true);
+  n.q = plan_nce_shard(ws, br, b);
+  n.bytes = ws.off;
+  return n;
+}
+
+template <typename OpT>
+static int nce_shard_scores_generic(const float* x, const float* y, const float* w, int64_t br, int64_t b, int64_t dx,
+                                    int64_t dy, const NceStatsOut& so, const BilinearPlan& p, hipStream_t st) {
+  const float* t = x;
+  if (w) {
+    const int rc = generic_gemm_store<OpT>(make_operand(x, dx, 1), make_operand(w, 1, dy), br, dy, dx, p.t, dy, p, st,
+                                           "nce T = X W (generic)");
+    if (rc) return rc;
+    t = p.t;
+  }
+  return launch_gemm<OpT>(make_operand(t, dy, 1), make_operand(y, dy, 1), br, b, dy, EpiNceStats<false>{so}, st,
+                          "nce score + row / column records (generic)");
+}
+
+static int nce_shard_fwd_any(const float* x, const float* y, const float* w, const int64_t* sid_rows,
+                             const int64_t* sid_cols, int64_t br, int64_t b, int64_t row_offset, int64_t dx, int64_t dy,
+                             int precision, float* part_out, float* lse_rows, const NceShardBilinearPlan& n,
+                             hipStream_t st) {
+  const BilinearPlan& p = n.p;
+  const NceStatsOut so = nce_stats_out(n.q, sid_rows, sid_cols, row_offset);
+  int rc = MI_OK;
+  if (nce_fast_ok(br, b, dx, dy, precision)) {
+    rc = nce_prep_fast(x, y, w, sid_rows, sid_cols, br, b, row_offset, dx, dy, p, st);
+    if (rc) return rc;
+    const int x3 = p.x3;
+    rc = launch_gemm_bf16(one_problem(p.tb, x3 * dy, p.yb, x3 * dy, br, b, x3 * dy), 1, EpiNceStats<true>{so}, st,
+                          "nce score + row / column records");
+  } else if (precision == MI_PREC_BF16) {
+    rc = nce_shard_scores_generic<bf16_t>(x, y, w, br, b, dx, dy, so, p, st);
+  } else {
+    rc = nce_shard_scores_generic<float>(x, y, w, br, b, dx, dy, so, p, st);
+  }
+  if (rc) return rc;
+  return nce_rank_part(n.q, br, b, part_out, lse_rows, st);
+}
+
+template <typename OpT, typename TG>
+static int nce_shard_bwd_generic(const float* x, const float* y, const float* w, int64_t br, int64_t b, int64_t dx,
+                                 int64_t dy, const NceGradIn& gi, float* grad_x, float* grad_y, float* grad_w,
+                                 const BilinearPlan& p, hipStream_t st) {
+  const float* t = w ? p.t : x;  // T = X W is the forward's (same workspace)
+  TG* g = (TG*)p.g;
+  const int rc = launch_gemm<OpT>(make_operand(t, dy, 1), make_operand(y, dy, 1), br, b, dy, EpiNceGrad<TG>{gi, g}, st,
+                                  "nce G (generic)");
+  if (rc) return rc;
+  return generic_bwd_from_g<OpT, TG>(x, y, w, t, g, br, b, dx, dy, grad_x, grad_y, grad_w, p, st);
+}
+
+static int nce_shard_bwd_any(const float* x, const float* y, const float* w, const int64_t* sid_rows,
+                             const int64_t* sid_cols, int64_t br, int64_t b, int64_t row_offset, int64_t dx, int64_t dy,
+                             int mode, int precision, const float* lse_cols, const float* grad_out, float* grad_x,
+                             float* grad_y, float* grad_w, const NceShardBilinearPlan& n, hipStream_t st) {
+  const BilinearPlan& p = n.p;
+  const NceGradIn gi = nce_grad_in(sid_rows, sid_cols, row_offset, n.q.r, lse_cols, grad_out, b, mode);
+  if (nce_fast_ok(br, b, dx, dy, precision)) {
+    const int x3 = p.x3;
+    const int rc = launch_gemm_bf16(one_problem(p.tb, x3 * dy, p.yb, x3 * dy, br, b, x3 * dy), 1,
+                                    EpiNceGrad2{gi, p.gb, p.gtb, x3 == 3 ? 1 : 0}, st, "nce G");
+    if (rc) return rc;
+    return bilinear_bwd_from_g(br, b, dx, dy, grad_x, grad_y, grad_w, w != nullptr, p, st);
+  }
+  if (precision == MI_PREC_BF16)
+    return nce_shard_bwd_generic<bf16_t, bf16_t>(x, y, w, br, b, dx, dy, gi, grad_x, grad_y, grad_w, p, st);
+  return nce_shard_bwd_generic<float, float>(x, y, w, br, b, dx, dy, gi, grad_x, grad_y, grad_w, p, st);
+}
+
+// separable critic: A = X Wg [br][k], C = Y Wh [b][k] (every rank projects all b text rows), the row block on (A, C)
+struct NceShardSeparablePlan {
+  float *a, *c, *da, *dc;
+  NceShardBilinearPlan n;
+  size_t bytes;
+};
+static NceShardSeparablePlan plan_nce_shard_separable(Workspace& ws, int64_t br, int64_t b, int64_t k, int precision) {
+  NceShardSeparablePlan s{};
+  s.a = ws.take<float>(br * k);
+  s.c = ws.take<float>(b * k);
+  s.da = ws.take<float>(br * k);
+  s.dc = ws.take<float>(b * k);
+  s.n = plan_nce_shard_bilinear(ws, br, b, k, k, precision);
+  s.bytes = ws.off;
+  return s;
+}
+
+// out [M][N] = A B^T on the strided-operand kernels: bf16 operands in the bf16 mode, exact fp32 products otherwise (the
+// projections of mi_nce_separable_step)
+static int nce_proj_gemm(bool bf, const Operand<float>& A, const Operand<float>& B, int64_t M, int64_t N, int64_t K,
+                         float* out, int64_t ld, hipStream_t st, const char* what) {
+  return bf ? launch_gemm<bf16_t>(A, B, M, N, K, EpiStore{out, ld, nullptr, 1.0f, 0}, st, what)
+            : launch_gemm<float>(A, B, M, N, K, EpiStore{out, ld, nullptr, 1.0f, 0}, st, what);
+}
+
+static int nce_shard_check(const char* fn, int64_t br, int64_t b, int64_t row_offset, int64_t dx, int64_t dy, int mode,
+                           int precision) {
+  const int rc = nce_check(fn, b, dx, dy, mode, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(br >= 1 && br <= b, "%s: need 1 <= b_rows <= b (got %lld, %lld)", fn, (long long)br, (long long)b);
+  MI_CHECK_ARG(row_offset >= 0 && row_offset + br <= b, "%s: row block [%lld, %lld) outside [0, %lld)", fn,
+               (long long)row_offset, (long long)(row_offset + br), (long long)b);
+  return MI_OK;
 }
 
 }  // namespace mi
@@ -1572,6 +1696,151 @@ int mi_nce_separable_step(const float* x, const float* y, const float* wg, const
               "nce separable dWh = Y^T dC");
 #undef MI_NCE_GEMM
   return MI_OK;
+}
+
+/* Row blocks of a sharded batch (include/mi_critic.h): forward -> part, merge of the gathered parts -> loss and c,
+ * backward from the forward's workspace and the merged c. */
+size_t mi_nce_part_floats(int64_t b_rows, int64_t b) {
+  if (b_rows <= 0 || b <= 0) return 0;
+  return (size_t)nce_part_floats(b_rows, b);
+}
+
+size_t mi_nce_bilinear_shard_workspace_bytes(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, int precision) {
+  if (b_rows <= 0 || b <= 0 || d_img <= 0 || d_txt <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_nce_shard_bilinear(ws, b_rows, b, d_img, d_txt, precision).bytes + 256;
+}
+
+int mi_nce_bilinear_shard_fwd(const float* x, const float* y, const float* w, const int64_t* sid_rows,
+                              const int64_t* sid_cols, int64_t b_rows, int64_t b, int64_t row_offset, int64_t d_img,
+                              int64_t d_txt, int mode, int precision, float* part_out, float* lse_rows, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && sid_rows && sid_cols && part_out && workspace, "mi_nce_bilinear_shard_fwd: null pointer");
+  int rc = nce_shard_check("mi_nce_bilinear_shard_fwd", b_rows, b, row_offset, d_img, d_txt, mode, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(w || d_img == d_txt, "mi_nce_bilinear_shard_fwd: w == NULL (S = X Y^T) needs d_img == d_txt");
+  Workspace ws(workspace, workspace_bytes);
+  NceShardBilinearPlan n = plan_nce_shard_bilinear(ws, b_rows, b, d_img, d_txt, precision);
+  if (!ws.ok()) {
+    set_error("mi_nce_bilinear_shard_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
+    return MI_EWORKSPACE;
+  }
+  return nce_shard_fwd_any(x, y, w, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, precision, part_out,
+                           lse_rows, n, (hipStream_t)stream);
+}
+
+int mi_nce_bilinear_shard_bwd(const float* x, const float* y, const float* w, const int64_t* sid_rows,
+                              const int64_t* sid_cols, int64_t b_rows, int64_t b, int64_t row_offset, int64_t d_img,
+                              int64_t d_txt, int mode, int precision, const float* lse_cols, const float* grad_out,
+                              float* grad_x, float* grad_y, float* grad_w, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+  MI_CHECK_ARG(x && y && sid_rows && sid_cols && grad_x && grad_y && workspace, "mi_nce_bilinear_shard_bwd: null pointer");
+  int rc = nce_shard_check("mi_nce_bilinear_shard_bwd", b_rows, b, row_offset, d_img, d_txt, mode, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || lse_cols, "mi_nce_bilinear_shard_bwd: the symmetric mode needs lse_cols");
+  MI_CHECK_ARG((w && grad_w) || (!w && !grad_w && d_img == d_txt),
+               "mi_nce_bilinear_shard_bwd: w != NULL needs grad_w; w == NULL (S = X Y^T) needs d_img == d_txt, no grad_w");
+  Workspace ws(workspace, workspace_bytes);
+  NceShardBilinearPlan n = plan_nce_shard_bilinear(ws, b_rows, b, d_img, d_txt, precision);
+  if (!ws.ok()) {
+    set_error("mi_nce_bilinear_shard_bwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
+    return MI_EWORKSPACE;
+  }
+  return nce_shard_bwd_any(x, y, w, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, mode, precision, lse_cols,
+                           grad_out, grad_x, grad_y, grad_w, n, (hipStream_t)stream);
+}
+
+size_t mi_nce_merge_workspace_bytes(int64_t b) {
+  if (b <= 0) return 0;
+  return (size_t)(2 * b) * sizeof(float) + 256;
+}
+
+int mi_nce_merge_parts(const float* parts, int64_t n_ranks, int64_t b_rows, int64_t b, int mode, float* loss_out,
+                       float* lse_cols, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(parts && loss_out && lse_cols && workspace, "mi_nce_merge_parts: null pointer");
+  MI_CHECK_ARG(n_ranks >= 1 && b_rows >= 1 && b == n_ranks * b_rows,
+               "mi_nce_merge_parts: need b == n_ranks * b_rows >= 1 (got %lld ranks of %lld rows, b %lld)",
+               (long long)n_ranks, (long long)b_rows, (long long)b);
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || mode == MI_NCE_SYMMETRIC, "mi_nce_merge_parts: unknown mode %d", mode);
+  Workspace ws(workspace, workspace_bytes);
+  float* terms = ws.take<float>(2 * b);
+  if (!ws.ok()) {
+    set_error("mi_nce_merge_parts: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
+    return MI_EWORKSPACE;
+  }
+  return nce_merge_parts(parts, n_ranks, b_rows, b, mode, loss_out, lse_cols, terms, (hipStream_t)stream);
+}
+
+size_t mi_nce_separable_shard_workspace_bytes(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj,
+                                              int precision) {
+  if (b_rows <= 0 || b <= 0 || d_img <= 0 || d_txt <= 0 || d_proj <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_nce_shard_separable(ws, b_rows, b, d_proj, precision).bytes + 256;
+}
+
+int mi_nce_separable_shard_fwd(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid_rows,
+                               const int64_t* sid_cols, int64_t b_rows, int64_t b, int64_t row_offset, int64_t d_img,
+                               int64_t d_txt, int64_t d_proj, int mode, int precision, float* part_out, float* lse_rows,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && wg && wh && sid_rows && sid_cols && part_out && workspace,
+               "mi_nce_separable_shard_fwd: null pointer");
+  int rc = nce_shard_check("mi_nce_separable_shard_fwd", b_rows, b, row_offset, d_img, d_txt, mode, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(d_proj >= 1, "mi_nce_separable_shard_fwd: projection width must be >= 1");
+  Workspace ws(workspace, workspace_bytes);
+  NceShardSeparablePlan sp = plan_nce_shard_separable(ws, b_rows, b, d_proj, precision);
+  if (!ws.ok()) {
+    set_error("mi_nce_separable_shard_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
+    return MI_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t k = d_proj;
+  const bool bf = precision == MI_PREC_BF16;
+  rc = nce_proj_gemm(bf, make_operand(x, d_img, 1), make_operand(wg, 1, k), b_rows, k, d_img, sp.a, k, st,
+                     "nce separable A = X Wg");
+  if (rc) return rc;
+  rc = nce_proj_gemm(bf, make_operand(y, d_txt, 1), make_operand(wh, 1, k), b, k, d_txt, sp.c, k, st,
+                     "nce separable C = Y Wh");
+  if (rc) return rc;
+  return nce_shard_fwd_any(sp.a, sp.c, nullptr, sid_rows, sid_cols, b_rows, b, row_offset, k, k, precision, part_out,
+                           lse_rows, sp.n, st);
+}
+
+int mi_nce_separable_shard_bwd(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid_rows,
+                               const int64_t* sid_cols, int64_t b_rows, int64_t b, int64_t row_offset, int64_t d_img,
+                               int64_t d_txt, int64_t d_proj, int mode, int precision, const float* lse_cols,
+                               const float* grad_out, float* grad_x, float* grad_y, float* grad_wg, float* grad_wh,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && wg && wh && sid_rows && sid_cols && grad_x && grad_y && grad_wg && grad_wh && workspace,
+               "mi_nce_separable_shard_bwd: null pointer");
+  int rc = nce_shard_check("mi_nce_separable_shard_bwd", b_rows, b, row_offset, d_img, d_txt, mode, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(d_proj >= 1, "mi_nce_separable_shard_bwd: projection width must be >= 1");
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || lse_cols, "mi_nce_separable_shard_bwd: the symmetric mode needs lse_cols");
+  Workspace ws(workspace, workspace_bytes);
+  NceShardSeparablePlan sp = plan_nce_shard_separable(ws, b_rows, b, d_proj, precision);
+  if (!ws.ok()) {
+    set_error("mi_nce_separable_shard_bwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
+    return MI_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t k = d_proj;
+  const bool bf = precision == MI_PREC_BF16;
+  rc = nce_shard_bwd_any(sp.a, sp.c, nullptr, sid_rows, sid_cols, b_rows, b, row_offset, k, k, mode, precision, lse_cols,
+                         grad_out, sp.da, sp.dc, nullptr, sp.n, st);
+  if (rc) return rc;
+  // dA -> the rank's dX and its partial dWg; the rank's partial dC (all b text rows) -> partial dY and dWh
+  rc = nce_proj_gemm(bf, make_operand((const float*)sp.da, k, 1), make_operand(wg, k, 1), b_rows, d_img, k, grad_x, d_img,
+                     st, "nce separable dX = dA Wg^T");
+  if (rc) return rc;
+  rc = nce_proj_gemm(bf, make_operand(x, 1, d_img), make_operand((const float*)sp.da, 1, k), d_img, k, b_rows, grad_wg, k,
+                     st, "nce separable dWg = X^T dA");
+  if (rc) return rc;
+  rc = nce_proj_gemm(bf, make_operand((const float*)sp.dc, k, 1), make_operand(wh, k, 1), b, d_txt, k, grad_y, d_txt, st,
+                     "nce separable dY = dC Wh^T");
+  if (rc) return rc;
+  return nce_proj_gemm(bf, make_operand(y, 1, d_txt), make_operand((const float*)sp.dc, 1, k), d_txt, k, b, grad_wh, k,
+                       st, "nce separable dWh = Y^T dC");
 }
 
 size_t mi_matrix_nce_workspace_bytes(int64_t b) {

@@ -9,6 +9,11 @@
 //   nce_merge_kernel + nce_loss_kernel: the records of every tile merged in tile order -> r, c, the per-sample terms, the
 //                   loss (fixed order everywhere, no float atomics: bit-reproducible)
 //   nce_tile_grad:  one wave tile -> G = grad_out * dL/dS from r, c, the mask and the diagonal term
+// Row blocks (the sharded step): the tiles of rows [row_offset, row_offset + M) of the global B x B
+// matrix; local row i is global sample row_offset + i, so its positive is column row_offset + i.  The whole batch is
+// row_offset == 0, sid_rows == sid_cols.
+//   nce_rank_part_kernel:   a rank's records -> r (kept), one flat part (column partials, row terms, diagonal)
+//   nce_merge_parts_kernel: the parts of every rank, in rank order -> c, the per-sample terms -> nce_loss_kernel
 #pragma once
 #include "mi_common.h"
 #include "mi_gemm.h"
@@ -22,19 +27,24 @@ struct NceRec {
 };
 
 struct NceStatsOut {
-  const int64_t* sid;
-  NceRec* rowp;   // [M][n_ct]: row i over the columns of tile t
-  NceRec* colp;   // [N][n_rt]: column j over the rows of tile t
-  float* diag;    // [min(M, N)]: S[i, i]
+  const int64_t* sid_rows;  // [M]
+  const int64_t* sid_cols;  // [N]
+  int64_t row_offset;       // global index of local row 0
+  NceRec* rowp;             // [M][n_ct]: row i over the columns of tile t
+  NceRec* colp;             // [N][n_rt]: column j over the rows of tile t
+  float* diag;              // [M]: S[i, row_offset + i]
   int64_t n_ct, n_rt;
 };
 
 struct NceGradIn {
-  const int64_t* sid;
+  const int64_t* sid_rows;  // [M]
+  const int64_t* sid_cols;  // [N]
+  int64_t row_offset;
   const float* r;         // [M] row LSE
   const float* c;         // [N] column LSE
   const float* grad_out;  // [1] or null (1)
-  float wr, wc;           // weights of the row and column terms: 1/B, 0 (rowwise) or 1/(2B), 1/(2B) (symmetric)
+  float wr, wc;           // weights of the row and column terms: 1/B, 0 (rowwise) or 1/(2B), 1/(2B) (symmetric); B is
+                          // the global batch
 };
 
 template <bool FAST>
@@ -51,14 +61,16 @@ __device__ __forceinline__ void nce_tile_stats(f32x16 (&acc)[2][2], int64_t mb, 
                                                const NceStatsOut& o) {
   const int lane = threadIdx.x & 63;
   const int col_l = lane & 31, half = lane >> 5;
-  const bool dtile = mb == nb;  // 64-aligned tiles: only these hold diagonal pairs
+  const int64_t off = o.row_offset;
+  // only tiles that the diagonal crosses hold positive pairs (row_offset == 0: mb == nb; other offsets may straddle two)
+  const bool dtile = mb + off < nb + 64 && nb < mb + off + 64;
   int64_t sc[2];
   bool cok[2];
 #pragma unroll
   for (int tn = 0; tn < 2; ++tn) {
     const int64_t col = nb + tn * 32 + col_l;
     cok[tn] = col < N;
-    sc[tn] = cok[tn] ? o.sid[col] : 0;
+    sc[tn] = cok[tn] ? o.sid_cols[col] : 0;
   }
   // mask: non-candidates and elements outside M x N become -inf; the diagonal is kept (and recorded)
 #pragma unroll
@@ -67,14 +79,15 @@ __device__ __forceinline__ void nce_tile_stats(f32x16 (&acc)[2][2], int64_t mb, 
     for (int r = 0; r < 16; ++r) {
       const int64_t row = mb + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
       const bool rok = row < M;
-      const int64_t sr = rok ? o.sid[row] : 0;
+      const int64_t sr = rok ? o.sid_rows[row] : 0;
 #pragma unroll
       for (int tn = 0; tn < 2; ++tn) {
         const int64_t col = nb + tn * 32 + col_l;
         const float v = acc[tm][tn][r];
         const bool ok = rok && cok[tn];
-        if (dtile && ok && row == col) o.diag[row] = v;
-        acc[tm][tn][r] = (ok && (sr != sc[tn] || row == col)) ? v : MI_NEG_INF;
+        const bool pos = row + off == col;
+        if (dtile && ok && pos) o.diag[row] = v;
+        acc[tm][tn][r] = (ok && (sr != sc[tn] || pos)) ? v : MI_NEG_INF;
       }
     }
   // rows: each row's 64 values sit in the 32 lanes of one half (two per lane): butterfly max, then butterfly sum
@@ -121,7 +134,7 @@ __device__ __forceinline__ void nce_tile_stats(f32x16 (&acc)[2][2], int64_t mb, 
 }
 
 // acc (scores) -> G = grad_out * dL/dS:  wr 1[j in C_i] exp(S - r_i) + wc 1[j in C_i] exp(S - c_j) - (wr + wc) delta_ij
-// (j in C_i <=> i in R_j).  0 outside M x N.
+// (j in C_i <=> i in R_j; delta_ij: row_offset + i == j).  0 outside M x N.
 template <bool FAST>
 __device__ __forceinline__ void nce_tile_grad(f32x16 (&acc)[2][2], int64_t mb, int64_t nb, int64_t M, int64_t N,
                                               const NceGradIn& g) {
@@ -137,7 +150,7 @@ __device__ __forceinline__ void nce_tile_grad(f32x16 (&acc)[2][2], int64_t mb, i
   for (int tn = 0; tn < 2; ++tn) {
     const int64_t col = nb + tn * 32 + col_l;
     cok[tn] = col < N;
-    sc[tn] = cok[tn] ? g.sid[col] : 0;
+    sc[tn] = cok[tn] ? g.sid_cols[col] : 0;
     cc[tn] = cok[tn] && cols ? g.c[col] : 0.0f;
   }
 #pragma unroll
@@ -146,17 +159,18 @@ __device__ __forceinline__ void nce_tile_grad(f32x16 (&acc)[2][2], int64_t mb, i
     for (int r = 0; r < 16; ++r) {
       const int64_t row = mb + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
       const bool rok = row < M;
-      const int64_t sr = rok ? g.sid[row] : 0;
+      const int64_t sr = rok ? g.sid_rows[row] : 0;
       const float rr = rok ? g.r[row] : 0.0f;
 #pragma unroll
       for (int tn = 0; tn < 2; ++tn) {
         const int64_t col = nb + tn * 32 + col_l;
         const float v = acc[tm][tn][r];
+        const bool pos = row + g.row_offset == col;
         float gv = 0.0f;
-        if (rok && cok[tn] && (sr != sc[tn] || row == col)) {
+        if (rok && cok[tn] && (sr != sc[tn] || pos)) {
           gv = wr * nce_exp<FAST>(v - rr);
           if (cols) gv += wc * nce_exp<FAST>(v - cc[tn]);
-          if (row == col) gv -= wr + wc;
+          if (pos) gv -= wr + wc;
         }
         acc[tm][tn][r] = gv;
       }
@@ -310,6 +324,62 @@ static __global__ __launch_bounds__(256) void nce_loss_kernel(const float* __res
   }
 }
 
+// ------------------------------------------------------------------------------------------------ row blocks
+// The part of one rank (nce_part_floats(br, b) floats, gathered in rank order by the caller):
+//   [0, 2b)              column j: (m, s) of its candidates in this rank's rows, merged in row-tile order (NceRec)
+//   [2b, 2b + br)        row term r_i - S[i, row_offset + i] of local row i
+//   [2b + br, 2b + 2 br) S[i, row_offset + i]
+__host__ __device__ inline int64_t nce_part_floats(int64_t br, int64_t b) { return 2 * b + 2 * br; }
+
+// thread k < br: local row k (records merged in tile order exactly as nce_merge_kernel: the same r bits), br <= k < br + b:
+// column k - br over this rank's row tiles
+static __global__ __launch_bounds__(256) void nce_rank_part_kernel(const NceRec* __restrict__ rowp,
+                                                                   const NceRec* __restrict__ colp,
+                                                                   const float* __restrict__ diag, int64_t br, int64_t b,
+                                                                   int64_t n_ct, int64_t n_rt, float* r_ws, float* r_out,
+                                                                   float* __restrict__ part) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= br + b) return;
+  const bool is_row = k < br;
+  const int64_t i = is_row ? k : k - br;
+  const NceRec* p = is_row ? rowp + i * n_ct : colp + i * n_rt;
+  const int64_t n = is_row ? n_ct : n_rt;
+  float m = MI_NEG_INF, s = 0.0f;
+  for (int64_t t = 0; t < n; ++t) lse_merge(m, s, p[t].m, p[t].s);
+  if (!is_row) {
+    part[2 * i] = m;
+    part[2 * i + 1] = s;
+    return;
+  }
+  const float lse = s > 0.0f ? m + logf(s) : MI_NEG_INF;
+  r_ws[i] = lse;
+  if (r_out) r_out[i] = lse;
+  part[2 * b + i] = lse - diag[i];
+  part[2 * b + br + i] = diag[i];
+}
+
+// parts [n_ranks][nce_part_floats(br, b)] in rank order (rank g holds rows [g br, (g + 1) br)).  Thread k < b: the row term
+// of sample k, copied; b <= k < 2b: column j = k - b, its partials merged in rank order from an empty (-inf, 0) start --
+// exact for one rank, so one rank gives the bits of nce_merge_kernel -- then c_j and its term c_j - S[j, j] (the diagonal
+// from the part of the rank that owns row j).  Every rank runs this on the same gathered buffer: identical bits.
+static __global__ __launch_bounds__(256) void nce_merge_parts_kernel(const float* __restrict__ parts, int64_t n_ranks,
+                                                                     int64_t br, int64_t b, float* c_out,
+                                                                     float* __restrict__ terms) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= 2 * b) return;
+  const int64_t pf = nce_part_floats(br, b);
+  if (k < b) {
+    terms[k] = parts[(k / br) * pf + 2 * b + k % br];
+    return;
+  }
+  const int64_t j = k - b;
+  float m = MI_NEG_INF, s = 0.0f;
+  for (int64_t g = 0; g < n_ranks; ++g) lse_merge(m, s, parts[g * pf + 2 * j], parts[g * pf + 2 * j + 1]);
+  const float lse = s > 0.0f ? m + logf(s) : MI_NEG_INF;
+  c_out[j] = lse;
+  terms[k] = lse - parts[(j / br) * pf + 2 * b + br + j % br];
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 struct NcePlan {
   NceRec* rowp;
@@ -331,14 +401,19 @@ static inline NcePlan plan_nce(Workspace& ws, int64_t b) {
 }
 
 static inline NceStatsOut nce_stats_out(const NcePlan& q, const int64_t* sid) {
-  return NceStatsOut{sid, q.rowp, q.colp, q.diag, q.n_t, q.n_t};
+  return NceStatsOut{sid, sid, 0, q.rowp, q.colp, q.diag, q.n_t, q.n_t};
 }
 
+// b: the GLOBAL batch (the loss weights); a row block passes its own ids, the global ids and its offset
+static inline NceGradIn nce_grad_in(const int64_t* sid_rows, const int64_t* sid_cols, int64_t row_offset, const float* r,
+                                    const float* c, const float* grad_out, int64_t b, int mode) {
+  const float fb = (float)b;
+  if (mode == MI_NCE_SYMMETRIC) return NceGradIn{sid_rows, sid_cols, row_offset, r, c, grad_out, 0.5f / fb, 0.5f / fb};
+  return NceGradIn{sid_rows, sid_cols, row_offset, r, c, grad_out, 1.0f / fb, 0.0f};
+}
 static inline NceGradIn nce_grad_in(const int64_t* sid, const float* r, const float* c, const float* grad_out, int64_t b,
                                     int mode) {
-  const float fb = (float)b;
-  if (mode == MI_NCE_SYMMETRIC) return NceGradIn{sid, r, c, grad_out, 0.5f / fb, 0.5f / fb};
-  return NceGradIn{sid, r, c, grad_out, 1.0f / fb, 0.0f};
+  return nce_grad_in(sid, sid, 0, r, c, grad_out, b, mode);
 }
 
 // records -> r, c (workspace and the caller's optional copies), loss
@@ -353,6 +428,60 @@ static inline int nce_finish(const NcePlan& q, int64_t b, int mode, float* loss_
   {
     ProfScope prof_("nce_loss_kernel", st);
     hipLaunchKernelGGL(nce_loss_kernel, dim3(1), dim3(256), 0, st, q.terms, b, mode == MI_NCE_SYMMETRIC ? 1 : 0, loss_out);
+  }
+  MI_LAUNCH_CHECK("nce_loss_kernel");
+  return MI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ row blocks, host side
+// The records of one rank's row block [br] x [b] and the row LSE r: the forward writes r, the backward reads it from the
+// same workspace (the same plan gives the same offsets).
+struct NceShardPlan {
+  NceRec* rowp;  // [br][n_ct]
+  NceRec* colp;  // [b][n_rt]
+  float *diag, *r;
+  int64_t n_ct, n_rt;
+};
+
+static inline NceShardPlan plan_nce_shard(Workspace& ws, int64_t br, int64_t b) {
+  NceShardPlan q{};
+  q.n_ct = (b + 63) / 64;
+  q.n_rt = (br + 63) / 64;
+  q.rowp = ws.take<NceRec>(br * q.n_ct);
+  q.colp = ws.take<NceRec>(b * q.n_rt);
+  q.diag = ws.take<float>(br);
+  q.r = ws.take<float>(br);
+  return q;
+}
+
+static inline NceStatsOut nce_stats_out(const NceShardPlan& q, const int64_t* sid_rows, const int64_t* sid_cols,
+                                        int64_t row_offset) {
+  return NceStatsOut{sid_rows, sid_cols, row_offset, q.rowp, q.colp, q.diag, q.n_ct, q.n_rt};
+}
+
+static inline int nce_rank_part(const NceShardPlan& q, int64_t br, int64_t b, float* part_out, float* lse_rows,
+                                hipStream_t st) {
+  {
+    ProfScope prof_("nce_rank_part_kernel", st);
+    hipLaunchKernelGGL(nce_rank_part_kernel, dim3((unsigned)((br + b + 255) / 256)), dim3(256), 0, st, q.rowp, q.colp,
+                       q.diag, br, b, q.n_ct, q.n_rt, q.r, lse_rows, part_out);
+  }
+  MI_LAUNCH_CHECK("nce_rank_part_kernel");
+  return MI_OK;
+}
+
+// terms: [2b] scratch
+static inline int nce_merge_parts(const float* parts, int64_t n_ranks, int64_t br, int64_t b, int mode, float* loss_out,
+                                  float* lse_cols, float* terms, hipStream_t st) {
+  {
+    ProfScope prof_("nce_merge_parts_kernel", st);
+    hipLaunchKernelGGL(nce_merge_parts_kernel, dim3((unsigned)((2 * b + 255) / 256)), dim3(256), 0, st, parts, n_ranks, br,
+                       b, lse_cols, terms);
+  }
+  MI_LAUNCH_CHECK("nce_merge_parts_kernel");
+  {
+    ProfScope prof_("nce_loss_kernel", st);
+    hipLaunchKernelGGL(nce_loss_kernel, dim3(1), dim3(256), 0, st, terms, b, mode == MI_NCE_SYMMETRIC ? 1 : 0, loss_out);
   }
   MI_LAUNCH_CHECK("nce_loss_kernel");
   return MI_OK;

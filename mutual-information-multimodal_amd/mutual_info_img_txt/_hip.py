@@ -97,6 +97,15 @@ SIGNATURES = {
     "mi_matrix_nce_workspace_bytes": (_SZ, [_I64]),
     "mi_matrix_nce_fwd": (c_int, [_P, _P, _I64, _I, _P, _P, _P, _P, _SZ, _P]),
     "mi_matrix_nce_bwd": (c_int, [_P, _P, _I64, _I, _P, _P, _P, _P, _P]),
+    "mi_nce_part_floats": (_SZ, [_I64, _I64]),
+    "mi_nce_bilinear_shard_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I]),
+    "mi_nce_bilinear_shard_fwd": (c_int, [_P] * 5 + [_I64] * 5 + [_I, _I] + [_P] * 3 + [_SZ, _P]),
+    "mi_nce_bilinear_shard_bwd": (c_int, [_P] * 5 + [_I64] * 5 + [_I, _I] + [_P] * 6 + [_SZ, _P]),
+    "mi_nce_merge_workspace_bytes": (_SZ, [_I64]),
+    "mi_nce_merge_parts": (c_int, [_P, _I64, _I64, _I64, _I, _P, _P, _P, _SZ, _P]),
+    "mi_nce_separable_shard_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I64, _I]),
+    "mi_nce_separable_shard_fwd": (c_int, [_P] * 6 + [_I64] * 6 + [_I, _I] + [_P] * 3 + [_SZ, _P]),
+    "mi_nce_separable_shard_bwd": (c_int, [_P] * 6 + [_I64] * 6 + [_I, _I] + [_P] * 7 + [_SZ, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -125,6 +125,35 @@ class _HipOps:
         self.nce_call(x, y, params, sid, mode, precision, loss, r, c, grads, ws)()
         return loss, r, c, grads
 
+    # ---------------------------------------------- per-sample InfoNCE on a row block (distributed.GlobalBatchNceFn)
+    def nce_forward(self, x, y_all, params, sid_rows, sid_all, row_offset, mode, precision, need_grad=True):
+        """The row block's part (``mi_nce_part_floats`` floats, gathered in rank order by the caller) and its row LSEs:
+        (part, lse_rows [b_rows], saved).  ``saved`` holds the workspace the backward goes on with."""
+        br, b, dev = x.shape[0], y_all.shape[0], x.device
+        ws = _hip.workspace(self.nce_shard_workspace_bytes(br, b, x.shape[1], y_all.shape[1], params, precision), dev)
+        part = torch.empty(_hip.load().mi_nce_part_floats(br, b), dtype=torch.float32, device=dev)
+        r = torch.empty(br, dtype=torch.float32, device=dev)
+        self.nce_fwd_call(x, y_all, params, sid_rows, sid_all, row_offset, mode, precision, part, r, ws)()
+        return part, r, (x, y_all, list(params), sid_rows, sid_all, row_offset, mode, precision, ws)
+
+    @staticmethod
+    def nce_merge(parts, b_rows, mode):
+        """parts [n_ranks, P] in rank order -> (loss [1], lse_cols [b]); identical bits on every rank."""
+        dev, b = parts.device, parts.shape[0] * b_rows
+        loss, c = torch.empty(1, dtype=torch.float32, device=dev), torch.empty(b, dtype=torch.float32, device=dev)
+        ws = _hip.workspace(_hip.load().mi_nce_merge_workspace_bytes(b), dev)
+        _hip.call("mi_nce_merge_parts", dev, parts.data_ptr(), parts.shape[0], b_rows, b, mode, loss.data_ptr(),
+                  c.data_ptr(), ws.data_ptr(), ws.numel())
+        return loss, c
+
+    def nce_backward(self, saved, lse_cols, grad_out, out=None):
+        """(grad_x, grad_y partial over this row block, [grad_params...] partial) of grad_out[0] * loss."""
+        x, y_all, params = saved[:3]
+        if out is None:
+            out = (torch.empty_like(x), torch.empty_like(y_all), [torch.empty_like(p) for p in params])
+        self.nce_bwd_call(saved, lse_cols, grad_out, out)()
+        return out
+
 
 class HipBilinearOps(_HipOps):
     """S = (X W) Y^T row block; params = [W] ([] on one GPU: S = X Y^T)."""
@@ -179,6 +208,23 @@ class HipBilinearOps(_HipOps):
         return _call("mi_nce_bilinear_step", x.device, x.data_ptr(), y.data_ptr(), _p(w), sid.data_ptr(), x.shape[0],
                      x.shape[1], y.shape[1], mode, precision, None, loss.data_ptr(), r.data_ptr(), c.data_ptr(), _p(gx),
                      _p(gy), _p(gw), ws.data_ptr(), ws.numel())
+
+    @staticmethod
+    def nce_shard_workspace_bytes(br, b, dx, dy, params, precision):
+        return _hip.load().mi_nce_bilinear_shard_workspace_bytes(br, b, dx, dy, precision)
+
+    def nce_fwd_call(self, x, y, params, sid_rows, sid_all, row_offset, mode, precision, part, r, ws):
+        return _call("mi_nce_bilinear_shard_fwd", x.device, x.data_ptr(), y.data_ptr(), _p(params[0] if params else None),
+                     sid_rows.data_ptr(), sid_all.data_ptr(), x.shape[0], y.shape[0], row_offset, x.shape[1], y.shape[1],
+                     mode, precision, part.data_ptr(), _p(r), ws.data_ptr(), ws.numel())
+
+    def nce_bwd_call(self, saved, lse_cols, grad_out, out):
+        x, y, params, sid_rows, sid_all, row_offset, mode, precision, ws = saved
+        gx, gy, gp = out
+        return _call("mi_nce_bilinear_shard_bwd", x.device, x.data_ptr(), y.data_ptr(), _p(params[0] if params else None),
+                     sid_rows.data_ptr(), sid_all.data_ptr(), x.shape[0], y.shape[0], row_offset, x.shape[1], y.shape[1],
+                     mode, precision, lse_cols.data_ptr(), grad_out.data_ptr(), gx.data_ptr(), gy.data_ptr(),
+                     _p(gp[0] if gp else None), ws.data_ptr(), ws.numel())
 
     # ------------------------------------------------------------------------------------------ sharded extras
     def prep_local(self, x, params, b, precision) -> bool:
@@ -318,6 +364,24 @@ class HipSeparableOps(_HipOps):
                      sid.data_ptr(), x.shape[0], x.shape[1], y.shape[1], wg.shape[1], mode, precision, None,
                      loss.data_ptr(), r.data_ptr(), c.data_ptr(), *[_p(g) for g in grads or [None] * 4], ws.data_ptr(),
                      ws.numel())
+
+    @staticmethod
+    def nce_shard_workspace_bytes(br, b, dx, dy, params, precision):
+        return _hip.load().mi_nce_separable_shard_workspace_bytes(br, b, dx, dy, params[0].shape[1], precision)
+
+    def nce_fwd_call(self, x, y, params, sid_rows, sid_all, row_offset, mode, precision, part, r, ws):
+        wg, wh = params
+        return _call("mi_nce_separable_shard_fwd", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
+                     sid_rows.data_ptr(), sid_all.data_ptr(), x.shape[0], y.shape[0], row_offset, x.shape[1], y.shape[1],
+                     wg.shape[1], mode, precision, part.data_ptr(), _p(r), ws.data_ptr(), ws.numel())
+
+    def nce_bwd_call(self, saved, lse_cols, grad_out, out):
+        x, y, (wg, wh), sid_rows, sid_all, row_offset, mode, precision, ws = saved
+        gx, gy, (gg, gh) = out
+        return _call("mi_nce_separable_shard_bwd", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
+                     sid_rows.data_ptr(), sid_all.data_ptr(), x.shape[0], y.shape[0], row_offset, x.shape[1], y.shape[1],
+                     wg.shape[1], mode, precision, lse_cols.data_ptr(), grad_out.data_ptr(), gx.data_ptr(),
+                     gy.data_ptr(), gg.data_ptr(), gh.data_ptr(), ws.data_ptr(), ws.numel())
 
 
 class HipConcatMlpOps(_HipOps):

@@ -180,14 +180,76 @@ class GlobalBatchCriticFn(torch.autograd.Function):
         return (None, None, None, None, None, gx, gy, *gparams)
 
 
+class GlobalBatchNceFn(torch.autograd.Function):
+    """Per-sample InfoNCE over the GLOBAL batch from this rank's row block.
+    Returns (loss [1], lse_rows [b_rows], lse_cols [B]).
+
+    forward : all-gather Y and the ids; the rank's scores -> one flat part (column partials, row terms, its diagonal
+              scores); all-gather the parts; merge them in rank order -> c, loss (identical bits on every rank).
+    backward: the rank's gradients from its r and the merged c -> dX complete, dY partial (reduce-scatter), parameter
+              gradients partial (one flat all-reduce).  Five collectives per step, as GlobalBatchCriticFn's."""
+
+    @staticmethod
+    def forward(ctx, ops, group, mode: int, precision: int, sid_rows, x, y, *params):
+        world = dist.get_world_size(group)
+        rank = dist.get_rank(group)
+        br = x.shape[0]
+        x = x.contiguous()
+        params_c = [p.contiguous() for p in params]
+        y_all, work_y = _all_gather_rows(y, group, async_op=True)
+        sid_all, work_sid = _all_gather_rows(sid_rows, group, async_op=True)
+        work_y.wait()
+        work_sid.wait()
+        part, lse_rows, saved = ops.nce_forward(x, y_all, params_c, sid_rows.contiguous(), sid_all, rank * br, mode,
+                                                precision)
+        parts = _all_gather_rows(part.reshape(1, -1), group)  # [G, P], rank order
+        loss, lse_cols = ops.nce_merge(parts, br, mode)
+        ctx.ops, ctx.group, ctx.saved = ops, group, saved
+        ctx.param_like = [p.detach() for p in params]
+        ctx.save_for_backward(lse_cols)
+        ctx.mark_non_differentiable(lse_rows, lse_cols)
+        return loss, lse_rows, lse_cols
+
+    @staticmethod
+    def backward(ctx, grad_loss, _glr, _glc):
+        (lse_cols,) = ctx.saved_tensors
+        go = grad_loss.reshape(-1)[:1].to(lse_cols.dtype).contiguous()
+        flat, views = flat_views(ctx.param_like)
+        gx, gy_partial, gparams = ctx.ops.nce_backward(ctx.saved, lse_cols, go)
+        if flat is not None:
+            for v, g in zip(views, gparams):
+                v.copy_(g)
+            gparams = views
+        gy = _reduce_scatter_rows(gy_partial, ctx.group)
+        if flat is not None:
+            dist.all_reduce(flat, group=ctx.group)  # one collective for all parameter gradients
+        return (None, None, None, None, None, gx, gy, *gparams)
+
+
 def global_batch_mi_bound(embedding_img, embedding_txt, study_id_codes, critic_params: Sequence[torch.Tensor],
                           estimator: str = "infonce", precision: str = "bf16", critic: str = "bilinear", group=None,
                           ops=None, return_stats: bool = False):
     """Reference loss at B = world_size * local_batch with this rank's [B/G, d] embeddings.
     ``study_id_codes``: int64 tensor [B/G] (codes must be consistent across ranks, e.g. the integer study ids).
     Every rank returns the same loss; ``.backward()`` leaves the gradient of the global loss w.r.t. the local
-    embeddings and the (all-reduced) gradient w.r.t. the critic parameters."""
-    from .mi_critics import _estimator_code
+    embeddings and the (all-reduced) gradient w.r.t. the critic parameters.
+
+    ``estimator`` = "infonce_rowwise" / "infonce_symmetric" (critic "bilinear" or "separable"): the per-sample InfoNCE
+    normalised over the global batch (GlobalBatchNceFn), loss of shape []; ``return_stats=True`` then gives
+    ``(loss, (lse_rows [B/G], lse_cols [B]))``."""
+    from .mi_critics import NCE_ESTIMATORS, _estimator_code
+    if estimator in NCE_ESTIMATORS:
+        if critic not in ("bilinear", "separable"):
+            raise ValueError(f"mi_estimator {estimator!r} is implemented for the bilinear and separable critics only; for "
+                             "scores you compute yourself use matrix_bound_loss(scores, study_id, estimator) (one GPU)")
+        if ops is None:
+            ops = OPS[critic]()
+        prec = resolve_critic(critic, precision, embedding_img.shape[0], embedding_img.shape[1],
+                              embedding_txt.shape[1], critic_params)[2]  # the same rank-row-count rule as below
+        loss, lse_rows, lse_cols = GlobalBatchNceFn.apply(ops, group, NCE_ESTIMATORS[estimator], prec, study_id_codes,
+                                                          embedding_img, embedding_txt, *critic_params)
+        loss = loss.reshape(())
+        return (loss, (lse_rows, lse_cols)) if return_stats else loss
     if ops is None:
         ops = OPS[critic]()
     est = _estimator_code(estimator)

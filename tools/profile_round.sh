@@ -5,8 +5,10 @@
 #   <tag>_bench_line.json         the JSON line of the profiled bench.py run (eager launches: one row per kernel)
 #   <tag>_bench_kernel_stats.csv  rocprofv3 --kernel-trace --stats summary of that same run
 #   <tag>_pmc_traffic.json        HBM-side bytes per launch from FETCH_SIZE / WRITE_SIZE (separate --pmc passes)
-# rocprofv3 runs from /tmp with the program directly after `--` (profiling recipe of the GPU pool).
+# rocprofv3 runs from /tmp with the program directly after `--` (profiling recipe of the GPU pool).  Every pass runs under
+# its own time limit (PROF_TIMEOUT seconds, default 240) and the script stops at the first pass that fails.
 set -u
+T="timeout -k 10 ${PROF_TIMEOUT:-240}"
 TAG=${1:-r1_x}
 COMMIT=${2:-unknown}   # the snapshot on the GPU box has no .git: pass `git rev-parse --short HEAD` as the second argument
 REPO=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
@@ -14,16 +16,16 @@ OUT=$REPO/gpurun_out/profile_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 BENCH="python3 $REPO/bench.py --graph off --steps 20 --warmup 5 --clock-warmup-ms 0 --no-cpu-baseline --no-parity-mode --no-fp8"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o stats -- $BENCH > "$OUT/bench.log" 2>&1 || exit 1
+$T rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o stats -- $BENCH > "$OUT/bench.log" 2>&1 || exit 1
 grep "^{\"metric\"" "$OUT/bench.log" | tail -1 > "$OUT/${TAG}_bench_line.json"
 cp "$(find "$OUT/stats" -name '*kernel_stats.csv' | head -1)" "$OUT/${TAG}_bench_kernel_stats.csv"
 # (the counter passes include the fp8 leg -- B = 8192, d = 1024 -- so that fp8_mode.roofline gets its bytes too)
 SHORT="python3 $REPO/bench.py --graph off --steps 5 --warmup 2 --clock-warmup-ms 0 --profile-steps 1 --secondary-steps 2 --no-cpu-baseline --no-parity-mode --timed-iters 50"
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o fetch -- $SHORT > "$OUT/fetch.log" 2>&1 || exit 1
-rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -o write -- $SHORT > "$OUT/write.log" 2>&1 || exit 1
+$T rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o fetch -- $SHORT > "$OUT/fetch.log" 2>&1 || exit 1
+$T rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -o write -- $SHORT > "$OUT/write.log" 2>&1 || exit 1
 # matrix-pipe utilisation: SQ_VALU_MFMA_BUSY_CYCLES counts 32 per v_mfma_f32_32x32x16_bf16 (summed over all SIMDs);
 # GRBM_GUI_ACTIVE / 8 = the kernel's duration in shader cycles (sum over the 8 XCDs); 1024 SIMDs on the chip
-rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d "$OUT/sq" -o sq -- $SHORT > "$OUT/sq.log" 2>&1 || echo "SQ pass failed (kept going)"
+$T rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d "$OUT/sq" -o sq -- $SHORT > "$OUT/sq.log" 2>&1 || exit 1
 CSRC_SHA=$(python3 -c "import sys; sys.path.insert(0, '$REPO'); import bench; print(bench.csrc_sha())" 2>/dev/null | tail -1)
 python3 - "$OUT" "$TAG" "$CSRC_SHA" "$COMMIT" <<'PY'
 import csv, glob, json, sys, collections
