@@ -18,6 +18,8 @@
  *   mi_nce_*, mi_matrix_nce_* <- an extension: the per-sample (CPC / ConVIRT / CLIP) InfoNCE on the bilinear and
  *                            separable critics and on materialised scores, with the reference's masking rule
  *                            (main_utils.py:105); the reference has no such loss
+ *   mi_fdiv_*             <- an extension: the Jensen-Shannon (Deep InfoMax) and NWJ bounds on the reference's pairs
+ *                            (main_utils.py:88-110), for every critic; the reference has "dv" and "infonce" only
  *
  * Conventions
  *   - every pointer is a DEVICE pointer unless the name ends in _host; all tensors are dense row-major
@@ -355,6 +357,69 @@ int mi_nce_separable_shard_bwd(const float* x, const float* y, const float* wg, 
                                int64_t d_txt, int64_t d_proj, int mode, int precision, const float* lse_cols,
                                const float* grad_out, float* grad_x, float* grad_y, float* grad_wg, float* grad_wh,
                                void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Jensen-Shannon and NWJ bounds ------------------------------------------------------ */
+/* The reference's pairs (positives (i, i), negatives i != j with sid_i != sid_j; other pairs dropped), sp(x) = log(1 + e^x):
+ *   MI_FDIV_JSD: loss = mean_pos sp(-s) + mean_neg sp(s)                 (Deep InfoMax; -loss + 2 log 2 = JS divergence)
+ *   MI_FDIV_NWJ: loss = exp(LSE_neg - log n_neg - 1) - mean_pos s        (NWJ / f-GAN KL; -loss is the NWJ lower bound)
+ * A separate family: `mode` codes are not estimator codes.  "jsd" stays finite for any finite scores; NWJ overflows where
+ * e^s does (fp32).  No negatives: the loss is NaN.  Deterministic: partial records merged in a fixed order.
+ * Every forward writes loss_out[0] and, when terms_out != NULL, terms_out[0] = the positive-pair term and terms_out[1] =
+ * the negative-pair term (their sum is the loss):  JSD: mean_pos sp(-s), mean_neg sp(s);  NWJ: -mean_pos s,
+ * exp(LSE_neg - log n_neg - 1).  The statistics block (same struct, fields read as follows) is what the backward reads:
+ *   lse          NWJ: 1 + logf(n_neg), the normaliser of the DV-form gradient exp(s - lse); JSD: 0
+ *   pos_mean     the positive-pair term          reserved0   the negative-pair term
+ *   loss_dv, loss_infonce   both the loss        log_n_neg   logf((float)n_neg)
+ *   neg_max      NWJ: maximum negative score; JSD: 0          n_neg, n_pos   the pair counts; reserved1..3: 0
+ * Backward: grad = grad_out[0] * dloss/ds (grad_out NULL: 1), positives -sigma(-s)/n_pos (JSD) or -1/n_pos (NWJ),
+ * negatives sigma(s)/n_neg (JSD) or exp(s - lse) (NWJ), dropped pairs 0. */
+#define MI_FDIV_JSD 0
+#define MI_FDIV_NWJ 1
+/* logits[n] (the reference's [N, 1] mi_output), first pos_size rows positive, the rest negative */
+size_t mi_fdiv_bound_workspace_bytes(int64_t n);
+int mi_fdiv_bound_fwd(const float* logits, int64_t n, int64_t pos_size, int mode, float* loss_out, float* terms_out,
+                      mi_stats* stats, void* workspace, size_t workspace_bytes, void* stream);
+int mi_fdiv_bound_bwd(const float* logits, int64_t n, int64_t pos_size, int mode, const mi_stats* stats,
+                      const float* grad_out, float* grad_logits, void* stream);
+/* a caller's fp32 [b, b] score matrix with study-id masking */
+size_t mi_fdiv_matrix_workspace_bytes(int64_t b);
+int mi_fdiv_matrix_fwd(const float* scores, const int64_t* sid, int64_t b, int mode, float* loss_out, float* terms_out,
+                       mi_stats* stats, void* workspace, size_t workspace_bytes, void* stream);
+int mi_fdiv_matrix_bwd(const float* scores, const int64_t* sid, int64_t b, int mode, const mi_stats* stats,
+                       const float* grad_out, float* grad_scores, void* stream);
+/* Bilinear S = (X W) Y^T (w == NULL: X Y^T, d_img == d_txt) and separable S = (X Wg)(Y Wh)^T critics, whole batch, on the
+ * G-materialising GEMM chain (the fused B x B kernel is not used).  stats (optional) receives the block above.  All
+ * gradient pointers NULL: forward only; otherwise every one of them is written (gradients of grad_out[0] * loss).
+ * precision: MI_PREC_F32 (exact fp32 products), MI_PREC_BF16 / MI_PREC_BF16X3 (16-bit chain where b and the widths are
+ * multiples of 8, generic kernels otherwise); MI_PREC_FP8 / F16 / F16X3 are rejected (MI_EINVAL). */
+size_t mi_fdiv_bilinear_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int precision);
+int mi_fdiv_bilinear_step(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t d_img,
+                          int64_t d_txt, int mode, int precision, const float* grad_out, float* loss_out, float* terms_out,
+                          mi_stats* stats, float* grad_x, float* grad_y, float* grad_w, void* workspace,
+                          size_t workspace_bytes, void* stream);
+size_t mi_fdiv_separable_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int precision);
+int mi_fdiv_separable_step(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid,
+                           int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int mode, int precision,
+                           const float* grad_out, float* loss_out, float* terms_out, mi_stats* stats, float* grad_x,
+                           float* grad_y, float* grad_wg, float* grad_wh, void* workspace, size_t workspace_bytes,
+                           void* stream);
+/* Concat-MLP critic (make_mlp(d_img + d_txt, [h1, h2])): arguments, row block, precisions and workspace
+ * (mi_concat_mlp_workspace_bytes) as mi_concat_mlp_fwd / _bwd.  The forward writes scores_out [b_rows, b], the sign-bit
+ * images (need_grad) and *stats; the backward reads them, the same workspace and the same mode.  n_pos of the row block
+ * is b (the global batch's positives). */
+int mi_fdiv_concat_mlp_fwd(const float* x, const float* y, const float* w1, const float* b1, const float* w2,
+                           const float* b2, const float* w3, const float* b3, const int64_t* sid_rows,
+                           const int64_t* sid_cols, int64_t b_rows, int64_t b, int64_t row_offset, int64_t d_img,
+                           int64_t d_txt, int64_t h1, int64_t h2, int mode, int precision, int need_grad,
+                           float* loss_out, float* terms_out, mi_stats* stats, float* scores_out, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int mi_fdiv_concat_mlp_bwd(const float* x, const float* y, const float* w1, const float* b1, const float* w2,
+                           const float* b2, const float* w3, const float* b3, const int64_t* sid_rows,
+                           const int64_t* sid_cols, int64_t b_rows, int64_t b, int64_t row_offset, int64_t d_img,
+                           int64_t d_txt, int64_t h1, int64_t h2, int mode, int precision, const mi_stats* stats,
+                           const float* grad_out, const float* scores, float* grad_x, float* grad_y, float* grad_w1,
+                           float* grad_b1, float* grad_w2, float* grad_b2, float* grad_w3, float* grad_b3,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,7 @@
 #include "mi_bilinear_tail.h"
 #include "mi_fp8.h"
 #include "mi_nce.h"
+#include "mi_fdiv.h"
 
 namespace mi {
 
@@ -1886,6 +1887,200 @@ int mi_matrix_nce_bwd(const float* scores, const int64_t* sid, int64_t b, int mo
   }
   MI_LAUNCH_CHECK("nce_matrix_grad_kernel");
   return MI_OK;
+}
+
+}  // extern "C"
+
+// ================================================================================================ Jensen-Shannon and NWJ
+// (mi_fdiv.h)  The per-sample InfoNCE's G-materialising chain with the fdiv epilogues: one record
+// per 64 x 64 score tile -> the fixed-order finalize (loss, terms, statistics) -> [grads] G GEMM (recomputed scores ->
+// G, G^T under the mode's rule) -> the unchanged dT / dY / dW / dX launches.  The fused B x B kernel is not used.
+namespace mi {
+
+static int fdiv_check(const char* fn, int64_t b, int64_t dx, int64_t dy, int mode, int precision) {
+  MI_CHECK_ARG(b >= 1 && dx >= 1 && dy >= 1, "%s: sizes must be >= 1 (b %lld, widths %lld, %lld)", fn, (long long)b,
+               (long long)dx, (long long)dy);
+  int rc = fdiv_check_mode(fn, mode);
+  if (rc) return rc;
+  MI_CHECK_ARG(precision == MI_PREC_F32 || precision == MI_PREC_BF16 || precision == MI_PREC_BF16X3,
+               "%s: precision %d is not available for the JSD / NWJ bounds on this critic (f32, bf16, bf16x3)", fn,
+               precision);
+  return MI_OK;
+}
+
+struct FdivBilinearPlan {
+  BilinearPlan p;
+  FdivRec* rec;  // [n_t][n_t]
+  mi_stats* stats;
+  int64_t n_t;
+  size_t bytes;
+};
+static FdivBilinearPlan plan_fdiv_bilinear(Workspace& ws, int64_t b, int64_t dx, int64_t dy, int precision) {
+  FdivBilinearPlan n{};
+  n.p = plan_bilinear(ws, b, b, dx, dy, precision, true);
+  n.n_t = (b + 63) / 64;
+  n.rec = ws.take<FdivRec>(n.n_t * n.n_t);
+  n.stats = ws.take<mi_stats>(1);
+  n.bytes = ws.off;
+  return n;
+}
+
+// stats: the caller's block or the workspace's; the G epilogue reads it
+template <typename OpT, typename TG>
+static int fdiv_step_generic(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t dx,
+                             int64_t dy, int mode, const float* grad_out, float* loss_out, float* terms_out,
+                             mi_stats* stats, float* grad_x, float* grad_y, float* grad_w, const FdivBilinearPlan& n,
+                             hipStream_t st) {
+  const BilinearPlan& p = n.p;
+  int rc = MI_OK;
+  const float* t = x;  // w == nullptr: S = X Y^T
+  if (w) {
+    rc = generic_gemm_store<OpT>(make_operand(x, dx, 1), make_operand(w, 1, dy), b, dy, dx, p.t, dy, p, st,
+                                 "fdiv T = X W (generic)");
+    if (rc) return rc;
+    t = p.t;
+  }
+  rc = launch_gemm<OpT>(make_operand(t, dy, 1), make_operand(y, dy, 1), b, b, dy,
+                        EpiFdivStats{FdivStatsOut{sid, sid, 0, mode, n.rec, n.n_t}}, st, "fdiv score + records (generic)");
+  if (rc) return rc;
+  rc = launch_fdiv_finalize(n.rec, n.n_t * n.n_t, b, mode, loss_out, terms_out, stats, st);
+  if (rc || !grad_y) return rc;
+  TG* g = (TG*)p.g;
+  rc = launch_gemm<OpT>(make_operand(t, dy, 1), make_operand(y, dy, 1), b, b, dy,
+                        EpiFdivGrad<TG>{FdivGradIn{sid, sid, 0, mode, stats, grad_out}, g}, st, "fdiv G (generic)");
+  if (rc) return rc;
+  return generic_bwd_from_g<OpT, TG>(x, y, w, t, g, b, b, dx, dy, grad_x, grad_y, grad_w, p, st);
+}
+
+static int fdiv_step_fast(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t dx,
+                          int64_t dy, int mode, const float* grad_out, float* loss_out, float* terms_out, mi_stats* stats,
+                          float* grad_x, float* grad_y, float* grad_w, const FdivBilinearPlan& n, hipStream_t st) {
+  const BilinearPlan& p = n.p;
+  const int x3 = p.x3;
+  int rc = nce_prep_fast(x, y, w, sid, sid, b, b, 0, dx, dy, p, st);
+  if (rc) return rc;
+  const GemmBf16Args scores = one_problem(p.tb, x3 * dy, p.yb, x3 * dy, b, b, x3 * dy);
+  rc = launch_gemm_bf16(scores, 1, EpiFdivStats{FdivStatsOut{sid, sid, 0, mode, n.rec, n.n_t}}, st, "fdiv score + records");
+  if (rc) return rc;
+  rc = launch_fdiv_finalize(n.rec, n.n_t * n.n_t, b, mode, loss_out, terms_out, stats, st);
+  if (rc || !grad_y) return rc;
+  rc = launch_gemm_bf16(scores, 1, EpiFdivGrad2{FdivGradIn{sid, sid, 0, mode, stats, grad_out}, p.gb, p.gtb, x3 == 3 ? 1 : 0},
+                        st, "fdiv G");
+  if (rc) return rc;
+  return bilinear_bwd_from_g(b, b, dx, dy, grad_x, grad_y, grad_w, w != nullptr, p, st);
+}
+
+static int fdiv_step_any(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t dx,
+                         int64_t dy, int mode, int precision, const float* grad_out, float* loss_out, float* terms_out,
+                         mi_stats* stats, float* grad_x, float* grad_y, float* grad_w, const FdivBilinearPlan& n,
+                         hipStream_t st) {
+  if (!stats) stats = n.stats;
+  if (nce_fast_ok(b, dx, dy, precision))
+    return fdiv_step_fast(x, y, w, sid, b, dx, dy, mode, grad_out, loss_out, terms_out, stats, grad_x, grad_y, grad_w, n,
+                          st);
+  if (precision == MI_PREC_BF16)
+    return fdiv_step_generic<bf16_t, bf16_t>(x, y, w, sid, b, dx, dy, mode, grad_out, loss_out, terms_out, stats, grad_x,
+                                             grad_y, grad_w, n, st);
+  return fdiv_step_generic<float, float>(x, y, w, sid, b, dx, dy, mode, grad_out, loss_out, terms_out, stats, grad_x,
+                                         grad_y, grad_w, n, st);
+}
+
+struct FdivSeparablePlan {
+  float *a, *c, *da, *dc;
+  FdivBilinearPlan n;
+  size_t bytes;
+};
+static FdivSeparablePlan plan_fdiv_separable(Workspace& ws, int64_t b, int64_t k, int precision) {
+  FdivSeparablePlan s{};
+  s.a = ws.take<float>(b * k);
+  s.c = ws.take<float>(b * k);
+  s.da = ws.take<float>(b * k);
+  s.dc = ws.take<float>(b * k);
+  s.n = plan_fdiv_bilinear(ws, b, k, k, precision);
+  s.bytes = ws.off;
+  return s;
+}
+
+}  // namespace mi
+
+extern "C" {
+
+size_t mi_fdiv_bilinear_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int precision) {
+  if (b <= 0 || d_img <= 0 || d_txt <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_fdiv_bilinear(ws, b, d_img, d_txt, precision).bytes + 256;
+}
+
+int mi_fdiv_bilinear_step(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t d_img,
+                          int64_t d_txt, int mode, int precision, const float* grad_out, float* loss_out, float* terms_out,
+                          mi_stats* stats, float* grad_x, float* grad_y, float* grad_w, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && sid && loss_out && workspace, "mi_fdiv_bilinear_step: null pointer");
+  int rc = fdiv_check("mi_fdiv_bilinear_step", b, d_img, d_txt, mode, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(w || d_img == d_txt, "mi_fdiv_bilinear_step: w == NULL (S = X Y^T) needs d_img == d_txt");
+  const bool any_grad = grad_x || grad_y || grad_w;
+  MI_CHECK_ARG(!any_grad || (grad_x && grad_y && (w ? grad_w != nullptr : grad_w == nullptr)),
+               "mi_fdiv_bilinear_step: pass grad_x, grad_y and (with w) grad_w, or none of them");
+  Workspace ws(workspace, workspace_bytes);
+  FdivBilinearPlan n = plan_fdiv_bilinear(ws, b, d_img, d_txt, precision);
+  if (!ws.ok()) {
+    set_error("mi_fdiv_bilinear_step: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
+    return MI_EWORKSPACE;
+  }
+  return fdiv_step_any(x, y, w, sid, b, d_img, d_txt, mode, precision, grad_out, loss_out, terms_out, stats, grad_x,
+                       grad_y, grad_w, n, (hipStream_t)stream);
+}
+
+size_t mi_fdiv_separable_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int precision) {
+  if (b <= 0 || d_img <= 0 || d_txt <= 0 || d_proj <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_fdiv_separable(ws, b, d_proj, precision).bytes + 256;
+}
+
+int mi_fdiv_separable_step(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid,
+                           int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int mode, int precision,
+                           const float* grad_out, float* loss_out, float* terms_out, mi_stats* stats, float* grad_x,
+                           float* grad_y, float* grad_wg, float* grad_wh, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+  MI_CHECK_ARG(x && y && wg && wh && sid && loss_out && workspace, "mi_fdiv_separable_step: null pointer");
+  int rc = fdiv_check("mi_fdiv_separable_step", b, d_img, d_txt, mode, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(d_proj >= 1, "mi_fdiv_separable_step: projection width must be >= 1");
+  const bool any_grad = grad_x || grad_y || grad_wg || grad_wh;
+  MI_CHECK_ARG(!any_grad || (grad_x && grad_y && grad_wg && grad_wh),
+               "mi_fdiv_separable_step: pass all four gradients or none of them");
+  Workspace ws(workspace, workspace_bytes);
+  FdivSeparablePlan sp = plan_fdiv_separable(ws, b, d_proj, precision);
+  if (!ws.ok()) {
+    set_error("mi_fdiv_separable_step: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
+    return MI_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t k = d_proj;
+  // projections and their backward on the strided-operand kernels as in mi_nce_separable_step (bf16 operands in the bf16
+  // mode, exact fp32 products otherwise); the scores and their gradients on the bilinear chain with W = I
+  const bool bf = precision == MI_PREC_BF16;
+  rc = nce_proj_gemm(bf, make_operand(x, d_img, 1), make_operand(wg, 1, k), b, k, d_img, sp.a, k, st,
+                     "fdiv separable A = X Wg");
+  if (rc) return rc;
+  rc = nce_proj_gemm(bf, make_operand(y, d_txt, 1), make_operand(wh, 1, k), b, k, d_txt, sp.c, k, st,
+                     "fdiv separable C = Y Wh");
+  if (rc) return rc;
+  rc = fdiv_step_any(sp.a, sp.c, nullptr, sid, b, k, k, mode, precision, grad_out, loss_out, terms_out, stats,
+                     any_grad ? sp.da : nullptr, any_grad ? sp.dc : nullptr, nullptr, sp.n, st);
+  if (rc || !any_grad) return rc;
+  rc = nce_proj_gemm(bf, make_operand((const float*)sp.da, k, 1), make_operand(wg, k, 1), b, d_img, k, grad_x, d_img, st,
+                     "fdiv separable dX = dA Wg^T");
+  if (rc) return rc;
+  rc = nce_proj_gemm(bf, make_operand(x, 1, d_img), make_operand((const float*)sp.da, 1, k), d_img, k, b, grad_wg, k, st,
+                     "fdiv separable dWg = X^T dA");
+  if (rc) return rc;
+  rc = nce_proj_gemm(bf, make_operand((const float*)sp.dc, k, 1), make_operand(wh, k, 1), b, d_txt, k, grad_y, d_txt, st,
+                     "fdiv separable dY = dC Wh^T");
+  if (rc) return rc;
+  return nce_proj_gemm(bf, make_operand(y, 1, d_txt), make_operand((const float*)sp.dc, 1, k), d_txt, k, b, grad_wh, k, st,
+                       "fdiv separable dWh = Y^T dC");
 }
 
 }  // extern "C"

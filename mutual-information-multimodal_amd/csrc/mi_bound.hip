@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "mi_common.h"
+#include "mi_fdiv.h"
 
 namespace mi {
 
@@ -429,6 +430,83 @@ int mi_merge_partials(const float* partials, int64_t n_ranks, int64_t n_pos_glob
                        estimator, loss_out, stats);
   }
   MI_LAUNCH_CHECK("merge_records_kernel");
+  return MI_OK;
+}
+
+// ---- Jensen-Shannon and NWJ bounds (mi_fdiv.h) on logits and on a [b, b] matrix ----------------------------------------
+size_t mi_fdiv_bound_workspace_bytes(int64_t n) {
+  (void)n;
+  return align_up(sizeof(FdivRec) * kFdivMaxBlocks, 256) + 256;
+}
+
+int mi_fdiv_bound_fwd(const float* logits, int64_t n, int64_t pos_size, int mode, float* loss_out, float* terms_out,
+                      mi_stats* stats, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(logits && loss_out && stats && workspace, "mi_fdiv_bound_fwd: null pointer");
+  MI_CHECK_ARG(n >= 0 && pos_size >= 0 && pos_size <= n, "mi_fdiv_bound_fwd: need 0 <= pos_size <= n (got %lld, %lld)",
+               (long long)pos_size, (long long)n);
+  int rc = fdiv_check_mode("mi_fdiv_bound_fwd", mode);
+  if (rc) return rc;
+  Workspace ws(workspace, workspace_bytes);
+  FdivRec* recs = ws.take<FdivRec>(kFdivMaxBlocks);
+  if (!ws.ok()) {
+    set_error("mi_fdiv_bound_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
+    return MI_EWORKSPACE;
+  }
+  const int grid = grid_for(n);
+  hipStream_t st = (hipStream_t)stream;
+  {
+    ProfScope prof_("fdiv_bound_partials_kernel", st);
+    hipLaunchKernelGGL(fdiv_bound_partials_kernel, dim3(grid), dim3(kFdivBlock), 0, st, logits, n, pos_size, mode, recs);
+  }
+  MI_LAUNCH_CHECK("fdiv_bound_partials_kernel");
+  return launch_fdiv_finalize(recs, grid, pos_size, mode, loss_out, terms_out, stats, st);
+}
+
+int mi_fdiv_bound_bwd(const float* logits, int64_t n, int64_t pos_size, int mode, const mi_stats* stats,
+                      const float* grad_out, float* grad_logits, void* stream) {
+  MI_CHECK_ARG(logits && stats && grad_logits, "mi_fdiv_bound_bwd: null pointer");
+  MI_CHECK_ARG(n >= 0 && pos_size >= 0 && pos_size <= n, "mi_fdiv_bound_bwd: bad sizes");
+  int rc = fdiv_check_mode("mi_fdiv_bound_bwd", mode);
+  if (rc) return rc;
+  if (n == 0) return MI_OK;
+  {
+    ProfScope prof_("fdiv_bound_bwd_kernel", (hipStream_t)stream);
+    hipLaunchKernelGGL(fdiv_bound_bwd_kernel, dim3(grid_for(n)), dim3(kFdivBlock), 0, (hipStream_t)stream, logits, n,
+                       pos_size, mode, stats, grad_out, grad_logits);
+  }
+  MI_LAUNCH_CHECK("fdiv_bound_bwd_kernel");
+  return MI_OK;
+}
+
+size_t mi_fdiv_matrix_workspace_bytes(int64_t b) { return mi_fdiv_bound_workspace_bytes(b * b); }
+
+int mi_fdiv_matrix_fwd(const float* scores, const int64_t* sid, int64_t b, int mode, float* loss_out, float* terms_out,
+                       mi_stats* stats, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(scores && sid && loss_out && stats && workspace, "mi_fdiv_matrix_fwd: null pointer");
+  MI_CHECK_ARG(b >= 1, "mi_fdiv_matrix_fwd: b must be >= 1");
+  int rc = fdiv_check_mode("mi_fdiv_matrix_fwd", mode);
+  if (rc) return rc;
+  Workspace ws(workspace, workspace_bytes);
+  FdivRec* recs = ws.take<FdivRec>(kFdivMaxBlocks);
+  if (!ws.ok()) {
+    set_error("mi_fdiv_matrix_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
+    return MI_EWORKSPACE;
+  }
+  return fdiv_matrix_forward(scores, sid, sid, b, b, 0, b, mode, recs, loss_out, terms_out, stats, (hipStream_t)stream);
+}
+
+int mi_fdiv_matrix_bwd(const float* scores, const int64_t* sid, int64_t b, int mode, const mi_stats* stats,
+                       const float* grad_out, float* grad_scores, void* stream) {
+  MI_CHECK_ARG(scores && sid && stats && grad_scores, "mi_fdiv_matrix_bwd: null pointer");
+  MI_CHECK_ARG(b >= 1, "mi_fdiv_matrix_bwd: b must be >= 1");
+  int rc = fdiv_check_mode("mi_fdiv_matrix_bwd", mode);
+  if (rc) return rc;
+  {
+    ProfScope prof_("fdiv_matrix_bwd_kernel", (hipStream_t)stream);
+    hipLaunchKernelGGL(fdiv_matrix_bwd_kernel, dim3(grid_rows(b)), dim3(kFdivBlock), 0, (hipStream_t)stream, scores, sid,
+                       sid, b, b, (int64_t)0, mode, stats, grad_out, grad_scores);
+  }
+  MI_LAUNCH_CHECK("fdiv_matrix_bwd_kernel");
   return MI_OK;
 }
 

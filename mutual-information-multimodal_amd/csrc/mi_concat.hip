@@ -191,8 +191,9 @@ static int launch_concat_fwd(const float* u, const float* v, const OpT* w2, cons
   return MI_OK;
 }
 
-// OpT = float (exact fp32 products), bf16_t, or f16_t (mi_concat_f16.h: scaled fp16 operands, packed generation)
-template <typename OpT, bool X3 = false>
+// OpT = float (exact fp32 products), bf16_t, or f16_t (mi_concat_f16.h: scaled fp16 operands, packed generation).
+// R: gradient rule of the bound (mi_fdiv.h): kGradDV for DV / "infonce" / NWJ, kGradJSD for the Jensen-Shannon bound.
+template <typename OpT, bool X3 = false, int R = kGradDV>
 static int concat_bwd_impl(const float* x, const float* y, const float* w1, const float* w2, const float* b2,
                            const float* w3, const int64_t* sid_rows, const int64_t* sid_cols, int64_t br, int64_t b,
                            int64_t row_offset, int64_t dx, int64_t dy, int h1, int h2, const mi_stats* stats,
@@ -230,23 +231,23 @@ static int concat_bwd_impl(const float* x, const float* y, const float* w1, cons
         const dim3 grid3(xcd_grid((h1 + Duv3Smem::KC - 1) / Duv3Smem::KC, (int64_t)p.n_iblk * p.n_jsplit));
         const F16Scales* scp = kF16 ? (const F16Scales*)p.f16sc : (const F16Scales*)nullptr;
         if constexpr (X3) {
-          MI_SET_DYN_SMEM((concat_bwd_duv3_kernel<f16_t, float, true>), smem3, "hipFuncSetAttribute(concat_bwd_duv3_kernel)");
+          MI_SET_DYN_SMEM((concat_bwd_duv3_kernel<f16_t, float, true, R>), smem3, "hipFuncSetAttribute(concat_bwd_duv3_kernel)");
           ProfScope prof_("concat_bwd_duv_kernel", st);
-          hipLaunchKernelGGL((concat_bwd_duv3_kernel<f16_t, float, true>), grid3, dim3(256), smem3, st, (const float*)p.u,
+          hipLaunchKernelGGL((concat_bwd_duv3_kernel<f16_t, float, true, R>), grid3, dim3(256), smem3, st, (const float*)p.u,
                              (const float*)p.v, (const f16_t*)w2wp, (const unsigned long long*)p.bitsP, scores, sid_rows,
                              sid_cols, stats, grad_out, br, b, row_offset, h1, h2, p.cols_per_split, xcd_natural(),
                              p.du_slab, p.dv_slab, scp);
         } else if constexpr (kF16) {
-          MI_SET_DYN_SMEM((concat_bwd_duv3_kernel<f16_t, f16_t>), smem3, "hipFuncSetAttribute(concat_bwd_duv3_kernel)");
+          MI_SET_DYN_SMEM((concat_bwd_duv3_kernel<f16_t, f16_t, false, R>), smem3, "hipFuncSetAttribute(concat_bwd_duv3_kernel)");
           ProfScope prof_("concat_bwd_duv_kernel", st);
-          hipLaunchKernelGGL((concat_bwd_duv3_kernel<f16_t, f16_t>), grid3, dim3(256), smem3, st, (const f16_t*)p.uh,
+          hipLaunchKernelGGL((concat_bwd_duv3_kernel<f16_t, f16_t, false, R>), grid3, dim3(256), smem3, st, (const f16_t*)p.uh,
                              (const f16_t*)p.vh, (const f16_t*)w2wp, (const unsigned long long*)p.bitsP, scores, sid_rows,
                              sid_cols, stats, grad_out, br, b, row_offset, h1, h2, p.cols_per_split, xcd_natural(),
                              p.du_slab, p.dv_slab, scp);
         } else {
-          MI_SET_DYN_SMEM((concat_bwd_duv3_kernel<OpT, float>), smem3, "hipFuncSetAttribute(concat_bwd_duv3_kernel)");
+          MI_SET_DYN_SMEM((concat_bwd_duv3_kernel<OpT, float, false, R>), smem3, "hipFuncSetAttribute(concat_bwd_duv3_kernel)");
           ProfScope prof_("concat_bwd_duv_kernel", st);
-          hipLaunchKernelGGL((concat_bwd_duv3_kernel<OpT, float>), grid3, dim3(256), smem3, st, (const float*)p.u,
+          hipLaunchKernelGGL((concat_bwd_duv3_kernel<OpT, float, false, R>), grid3, dim3(256), smem3, st, (const float*)p.u,
                              (const float*)p.v, (const OpT*)w2wp, (const unsigned long long*)p.bitsP, scores, sid_rows,
                              sid_cols, stats, grad_out, br, b, row_offset, h1, h2, p.cols_per_split, xcd_natural(),
                              p.du_slab, p.dv_slab, scp);
@@ -256,16 +257,16 @@ static int concat_bwd_impl(const float* x, const float* y, const float* w1, cons
       }
     }
     if constexpr (kF16) {
-      MI_SET_DYN_SMEM((concat_bwd_duv_kernel<f16_t, f16_t>), smem, "hipFuncSetAttribute(concat_bwd_duv_kernel)");
+      MI_SET_DYN_SMEM((concat_bwd_duv_kernel<f16_t, f16_t, R>), smem, "hipFuncSetAttribute(concat_bwd_duv_kernel)");
       ProfScope prof_("concat_bwd_duv_kernel", st);
-      hipLaunchKernelGGL((concat_bwd_duv_kernel<f16_t, f16_t>), grid, dim3(512), smem, st, (const f16_t*)p.uh,
+      hipLaunchKernelGGL((concat_bwd_duv_kernel<f16_t, f16_t, R>), grid, dim3(512), smem, st, (const f16_t*)p.uh,
                          (const f16_t*)p.vh, (const f16_t*)w2wp, (const unsigned long long*)p.bitsP, scores, sid_rows,
                          sid_cols, stats, grad_out, br, b, row_offset, h1, h2, p.cols_per_split, xcd_natural(), p.du_slab,
                          p.dv_slab, (const F16Scales*)p.f16sc);
     } else {
-      MI_SET_DYN_SMEM((concat_bwd_duv_kernel<OpT>), smem, "hipFuncSetAttribute(concat_bwd_duv_kernel)");
+      MI_SET_DYN_SMEM((concat_bwd_duv_kernel<OpT, float, R>), smem, "hipFuncSetAttribute(concat_bwd_duv_kernel)");
       ProfScope prof_("concat_bwd_duv_kernel", st);
-      hipLaunchKernelGGL(concat_bwd_duv_kernel<OpT>, grid, dim3(512), smem, st, (const float*)p.u, (const float*)p.v,
+      hipLaunchKernelGGL((concat_bwd_duv_kernel<OpT, float, R>), grid, dim3(512), smem, st, (const float*)p.u, (const float*)p.v,
                          (const OpT*)w2wp, (const unsigned long long*)p.bitsP, scores, sid_rows, sid_cols, stats,
                          grad_out, br, b, row_offset, h1, h2, p.cols_per_split, xcd_natural(), p.du_slab, p.dv_slab,
                          (const F16Scales*)nullptr);
@@ -287,22 +288,22 @@ static int concat_bwd_impl(const float* x, const float* y, const float* w1, cons
     dim3 grid(xcd_grid(((h1 + 255) / 256) * (h2 / 256), p.n_dsplit));
     if constexpr (X3) {
       const size_t smem = (256 * 36 + kDw2IB * 32) * sizeof(float) + 256 * sizeof(bf16x8);
-      MI_SET_DYN_SMEM((concat_bwd_dw2_kernel<f16_t, true>), smem, "hipFuncSetAttribute(concat_bwd_dw2_kernel)");
+      MI_SET_DYN_SMEM((concat_bwd_dw2_kernel<f16_t, true, R>), smem, "hipFuncSetAttribute(concat_bwd_dw2_kernel)");
       ProfScope prof_("concat_bwd_dw2_kernel", st);
-      hipLaunchKernelGGL((concat_bwd_dw2_kernel<f16_t, true>), grid, dim3(512), smem, st, (const float*)p.us,
+      hipLaunchKernelGGL((concat_bwd_dw2_kernel<f16_t, true, R>), grid, dim3(512), smem, st, (const float*)p.us,
                          (const float*)p.vs, (const unsigned*)p.bitsN, scores, sid_rows, sid_cols, stats, grad_out, br, b,
                          row_offset, h1, h2, p.rows_per_dsplit, xcd_natural(), p.d_slab);
     } else if constexpr (kF16) {
-      MI_SET_DYN_SMEM(concat_bwd_dw2_f16_kernel, Dw2F16Smem::TOTAL, "hipFuncSetAttribute(concat_bwd_dw2_f16_kernel)");
+      MI_SET_DYN_SMEM((concat_bwd_dw2_f16_kernel<R>), Dw2F16Smem::TOTAL, "hipFuncSetAttribute(concat_bwd_dw2_f16_kernel)");
       ProfScope prof_("concat_bwd_dw2_kernel", st);
-      hipLaunchKernelGGL(concat_bwd_dw2_f16_kernel, grid, dim3(512), Dw2F16Smem::TOTAL, st, (const unsigned*)p.upk,
+      hipLaunchKernelGGL((concat_bwd_dw2_f16_kernel<R>), grid, dim3(512), Dw2F16Smem::TOTAL, st, (const unsigned*)p.upk,
                          (const f16_t*)p.vht, (const unsigned*)p.bitsN, scores, sid_rows, sid_cols, stats, br, b,
                          row_offset, h1, h2, p.rows_per_dsplit, xcd_natural(), p.d_slab);
     } else {
       const size_t smem = (256 * 36 + kDw2IB * 32) * sizeof(float) + 256 * sizeof(bf16x8);
-      MI_SET_DYN_SMEM((concat_bwd_dw2_kernel<OpT>), smem, "hipFuncSetAttribute(concat_bwd_dw2_kernel)");
+      MI_SET_DYN_SMEM((concat_bwd_dw2_kernel<OpT, false, R>), smem, "hipFuncSetAttribute(concat_bwd_dw2_kernel)");
       ProfScope prof_("concat_bwd_dw2_kernel", st);
-      hipLaunchKernelGGL(concat_bwd_dw2_kernel<OpT>, grid, dim3(512), smem, st, (const float*)p.u, (const float*)p.v,
+      hipLaunchKernelGGL((concat_bwd_dw2_kernel<OpT, false, R>), grid, dim3(512), smem, st, (const float*)p.u, (const float*)p.v,
                          (const unsigned*)p.bitsN, scores, sid_rows, sid_cols, stats, grad_out, br, b, row_offset, h1,
                          h2, p.rows_per_dsplit, xcd_natural(), p.d_slab);
     }
@@ -311,23 +312,23 @@ static int concat_bwd_impl(const float* x, const float* y, const float* w1, cons
     if (kF16 && !X3 && !db2_old) {
       // fp16 mode: g' as an fp16 operand, two bits per v_dot2c_f32_f16 (mi_concat_f16.h)
       const size_t smem2 = 256 * 16 + (size_t)((b + 31) / 32) * 32 * sizeof(f16_t);
-      MI_SET_DYN_SMEM((concat_bwd_db2_f16_kernel), smem2, "hipFuncSetAttribute(concat_bwd_db2_f16_kernel)");
+      MI_SET_DYN_SMEM((concat_bwd_db2_f16_kernel<R>), smem2, "hipFuncSetAttribute(concat_bwd_db2_f16_kernel)");
       ProfScope prof_("concat_bwd_db2_kernel", st);
-      hipLaunchKernelGGL(concat_bwd_db2_f16_kernel, dim3((unsigned)p.n_msplit), dim3(512), smem2, st,
+      hipLaunchKernelGGL((concat_bwd_db2_f16_kernel<R>), dim3((unsigned)p.n_msplit), dim3(512), smem2, st,
                          (const unsigned*)p.bitsN, scores, sid_rows, sid_cols, stats, grad_out, br, b, row_offset, h2,
                          p.rows_per_msplit, p.m_slab, p.g_sum);
     } else {
       const size_t smem2 = (size_t)((b + 31) / 32) * 32 * sizeof(float);
-      MI_SET_DYN_SMEM((concat_bwd_db2_kernel), smem2, "hipFuncSetAttribute(concat_bwd_db2_kernel)");
+      MI_SET_DYN_SMEM((concat_bwd_db2_kernel<R>), smem2, "hipFuncSetAttribute(concat_bwd_db2_kernel)");
       ProfScope prof_("concat_bwd_db2_kernel", st);
-      hipLaunchKernelGGL(concat_bwd_db2_kernel, dim3((unsigned)p.n_msplit), dim3(512), smem2, st,
+      hipLaunchKernelGGL((concat_bwd_db2_kernel<R>), dim3((unsigned)p.n_msplit), dim3(512), smem2, st,
                          (const unsigned*)p.bitsN, scores, sid_rows, sid_cols, stats, grad_out, br, b, row_offset, h2,
                          p.rows_per_msplit, p.m_slab, p.g_sum);
     }
     MI_LAUNCH_CHECK("concat_bwd_db2_kernel");
     {
       ProfScope prof_("concat_bwd_finish_w2_kernel", st);
-      hipLaunchKernelGGL(concat_bwd_finish_w2_kernel, dim3((unsigned)h2), dim3(256), 0, st, (const float*)p.d_slab,
+      hipLaunchKernelGGL((concat_bwd_finish_w2_kernel<R>), dim3((unsigned)h2), dim3(256), 0, st, (const float*)p.d_slab,
                          p.n_dsplit, (const float*)p.m_slab, (const float*)p.g_sum, p.n_msplit, w2, b2, w3, h1, h2,
                          grad_w2, grad_w3, grad_b2, grad_b3, kF16 ? (const F16Scales*)p.f16sc : (const F16Scales*)nullptr,
                          grad_out, stats, X3 ? 1 : 0);
@@ -373,6 +374,30 @@ static int concat_bwd_impl(const float* x, const float* y, const float* w1, cons
   return MI_OK;
 }
 
+template <int R>
+static int concat_bwd_dispatch(const float* x, const float* y, const float* w1, const float* w2, const float* b2,
+                               const float* w3, const int64_t* sid_rows, const int64_t* sid_cols, int64_t br, int64_t b,
+                               int64_t row_offset, int64_t dx, int64_t dy, int h1, int h2, int precision,
+                               const mi_stats* stats, const float* grad_out, const float* scores, float* grad_x,
+                               float* grad_y, float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2,
+                               float* grad_w3, float* grad_b3, const ConcatPlan& p, hipStream_t st) {
+  if (precision == MI_PREC_F16X3)
+    return concat_bwd_impl<f16_t, true, R>(x, y, w1, w2, b2, w3, sid_rows, sid_cols, br, b, row_offset, dx, dy, h1, h2,
+                                           stats, grad_out, scores, grad_x, grad_y, grad_w1, grad_b1, grad_w2, grad_b2,
+                                           grad_w3, grad_b3, p, st);
+  if (precision == MI_PREC_F16)
+    return concat_bwd_impl<f16_t, false, R>(x, y, w1, w2, b2, w3, sid_rows, sid_cols, br, b, row_offset, dx, dy, h1, h2,
+                                            stats, grad_out, scores, grad_x, grad_y, grad_w1, grad_b1, grad_w2, grad_b2,
+                                            grad_w3, grad_b3, p, st);
+  if (precision == MI_PREC_BF16)
+    return concat_bwd_impl<bf16_t, false, R>(x, y, w1, w2, b2, w3, sid_rows, sid_cols, br, b, row_offset, dx, dy, h1, h2,
+                                             stats, grad_out, scores, grad_x, grad_y, grad_w1, grad_b1, grad_w2, grad_b2,
+                                             grad_w3, grad_b3, p, st);
+  return concat_bwd_impl<float, false, R>(x, y, w1, w2, b2, w3, sid_rows, sid_cols, br, b, row_offset, dx, dy, h1, h2,
+                                          stats, grad_out, scores, grad_x, grad_y, grad_w1, grad_b1, grad_w2, grad_b2,
+                                          grad_w3, grad_b3, p, st);
+}
+
 }  // namespace mi
 
 using namespace mi;
@@ -386,23 +411,17 @@ size_t mi_concat_mlp_workspace_bytes(int64_t b_rows, int64_t b, int64_t d_img, i
   return plan_concat(ws, b_rows, b, h1, h2, precision, need_grad, d_img > d_txt ? d_img : d_txt).bytes + 256;
 }
 
-int mi_concat_mlp_fwd(const float* x, const float* y, const float* w1, const float* b1, const float* w2, const float* b2,
-                      const float* w3, const float* b3, const int64_t* sid_rows, const int64_t* sid_cols, int64_t b_rows,
-                      int64_t b, int64_t row_offset, int64_t d_img, int64_t d_txt, int64_t h1, int64_t h2, int estimator,
-                      int precision, int need_grad, float* loss_out, mi_stats* stats, float* partials_out,
-                      float* scores_out, void* workspace, size_t workspace_bytes, void* stream) {
-  MI_CHECK_ARG(x && y && w1 && b1 && w2 && b2 && w3 && b3 && sid_rows && sid_cols && stats && scores_out && workspace,
-               "mi_concat_mlp_fwd: null pointer");
-  int rc = check_concat_shape("mi_concat_mlp_fwd", b_rows, b, row_offset, d_img, d_txt, h1, h2, precision);
-  if (rc) return rc;
-  MI_CHECK_ARG(estimator == MI_DV || estimator == MI_INFONCE, "mi_concat_mlp_fwd: unknown estimator %d", estimator);
-  Workspace ws(workspace, workspace_bytes);
-  ConcatPlan p = plan_concat(ws, b_rows, b, h1, h2, precision, need_grad, d_img > d_txt ? d_img : d_txt);
-  if (!ws.ok()) {
-    set_error("mi_concat_mlp_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
+}  // extern "C"
+
+namespace mi {
+
+// U, V, the precision mode's operand copies, scores_out [b_rows, b] and (need_grad) the sign-bit images: everything of the
+// forward before the bound's reduction (shared by mi_concat_mlp_fwd and mi_fdiv_concat_mlp_fwd)
+static int concat_fwd_scores(const float* x, const float* y, const float* w1, const float* b1, const float* w2,
+                             const float* b2, const float* w3, const float* b3, int64_t b_rows, int64_t b, int64_t d_img,
+                             int64_t d_txt, int64_t h1, int64_t h2, int precision, int need_grad, float* scores_out,
+                             const ConcatPlan& p, hipStream_t st) {
+  int rc = MI_OK;
   const int64_t d = d_img + d_txt;
   // U = X W1x^T, V = Y W1y^T + b1: exact fp32 products (these are < 1 % of the flops)
   rc = launch_gemm<float>(make_operand(x, d_img, 1), make_operand(w1, d, 1), b_rows, h1, d_img,
@@ -480,6 +499,32 @@ int mi_concat_mlp_fwd(const float* x, const float* y, const float* w1, const flo
   } else {
     rc = launch_concat_fwd<float>(p.u, p.v, w2, b2, w3, b3, b_rows, b, (int)h1, (int)h2, scores_out, bitsP, bitsN, st);
   }
+  return rc;
+}
+
+}  // namespace mi
+
+extern "C" {
+
+int mi_concat_mlp_fwd(const float* x, const float* y, const float* w1, const float* b1, const float* w2, const float* b2,
+                      const float* w3, const float* b3, const int64_t* sid_rows, const int64_t* sid_cols, int64_t b_rows,
+                      int64_t b, int64_t row_offset, int64_t d_img, int64_t d_txt, int64_t h1, int64_t h2, int estimator,
+                      int precision, int need_grad, float* loss_out, mi_stats* stats, float* partials_out,
+                      float* scores_out, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && w1 && b1 && w2 && b2 && w3 && b3 && sid_rows && sid_cols && stats && scores_out && workspace,
+               "mi_concat_mlp_fwd: null pointer");
+  int rc = check_concat_shape("mi_concat_mlp_fwd", b_rows, b, row_offset, d_img, d_txt, h1, h2, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(estimator == MI_DV || estimator == MI_INFONCE, "mi_concat_mlp_fwd: unknown estimator %d", estimator);
+  Workspace ws(workspace, workspace_bytes);
+  ConcatPlan p = plan_concat(ws, b_rows, b, h1, h2, precision, need_grad, d_img > d_txt ? d_img : d_txt);
+  if (!ws.ok()) {
+    set_error("mi_concat_mlp_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
+    return MI_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  rc = concat_fwd_scores(x, y, w1, b1, w2, b2, w3, b3, b_rows, b, d_img, d_txt, h1, h2, precision, need_grad, scores_out, p,
+                         st);
   if (rc) return rc;
   const int grid = (int)(b_rows < kMatrixPartialBlocks ? b_rows : kMatrixPartialBlocks);
   {
@@ -512,22 +557,74 @@ int mi_concat_mlp_bwd(const float* x, const float* y, const float* w1, const flo
               workspace_bytes, ws.off);
     return MI_EWORKSPACE;
   }
+  return concat_bwd_dispatch<kGradDV>(x, y, w1, w2, b2, w3, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt,
+                                      (int)h1, (int)h2, precision, stats, grad_out, scores, grad_x, grad_y, grad_w1,
+                                      grad_b1, grad_w2, grad_b2, grad_w3, grad_b3, p, (hipStream_t)stream);
+}
+
+// ---- Jensen-Shannon and NWJ bounds (mi_fdiv.h): the same scores and sign-bit images, the fdiv reduction; the backward
+// kernels under the JSD rule, or (NWJ) the DV rule reading lse = 1 + log n_neg from the statistics block
+int mi_fdiv_concat_mlp_fwd(const float* x, const float* y, const float* w1, const float* b1, const float* w2,
+                           const float* b2, const float* w3, const float* b3, const int64_t* sid_rows,
+                           const int64_t* sid_cols, int64_t b_rows, int64_t b, int64_t row_offset, int64_t d_img,
+                           int64_t d_txt, int64_t h1, int64_t h2, int mode, int precision, int need_grad,
+                           float* loss_out, float* terms_out, mi_stats* stats, float* scores_out, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && w1 && b1 && w2 && b2 && w3 && b3 && sid_rows && sid_cols && loss_out && stats && scores_out &&
+                   workspace,
+               "mi_fdiv_concat_mlp_fwd: null pointer");
+  int rc = fdiv_check_mode("mi_fdiv_concat_mlp_fwd", mode);
+  if (rc) return rc;
+  rc = check_concat_shape("mi_fdiv_concat_mlp_fwd", b_rows, b, row_offset, d_img, d_txt, h1, h2, precision);
+  if (rc) return rc;
+  Workspace ws(workspace, workspace_bytes);
+  ConcatPlan p = plan_concat(ws, b_rows, b, h1, h2, precision, need_grad, d_img > d_txt ? d_img : d_txt);
+  if (!ws.ok()) {
+    set_error("mi_fdiv_concat_mlp_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
+    return MI_EWORKSPACE;
+  }
   hipStream_t st = (hipStream_t)stream;
-  if (precision == MI_PREC_F16X3)
-    return concat_bwd_impl<f16_t, true>(x, y, w1, w2, b2, w3, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt,
-                                        (int)h1, (int)h2, stats, grad_out, scores, grad_x, grad_y, grad_w1, grad_b1, grad_w2,
-                                        grad_b2, grad_w3, grad_b3, p, st);
-  if (precision == MI_PREC_F16)
-    return concat_bwd_impl<f16_t>(x, y, w1, w2, b2, w3, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt,
-                                  (int)h1, (int)h2, stats, grad_out, scores, grad_x, grad_y, grad_w1, grad_b1, grad_w2,
-                                  grad_b2, grad_w3, grad_b3, p, st);
-  if (precision == MI_PREC_BF16)
-    return concat_bwd_impl<bf16_t>(x, y, w1, w2, b2, w3, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt,
-                                   (int)h1, (int)h2, stats, grad_out, scores, grad_x, grad_y, grad_w1, grad_b1, grad_w2,
-                                   grad_b2, grad_w3, grad_b3, p, st);
-  return concat_bwd_impl<float>(x, y, w1, w2, b2, w3, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, (int)h1,
-                                (int)h2, stats, grad_out, scores, grad_x, grad_y, grad_w1, grad_b1, grad_w2, grad_b2,
-                                grad_w3, grad_b3, p, st);
+  rc = concat_fwd_scores(x, y, w1, b1, w2, b2, w3, b3, b_rows, b, d_img, d_txt, h1, h2, precision, need_grad, scores_out, p,
+                         st);
+  if (rc) return rc;
+  // the DV partial records' slots (kMatrixPartialBlocks x 16 bytes) hold the fdiv records
+  static_assert(sizeof(FdivRec) == sizeof(Partial) && kFdivMaxBlocks <= kMatrixPartialBlocks, "record slots");
+  return fdiv_matrix_forward(scores_out, sid_rows, sid_cols, b_rows, b, row_offset, b, mode, (FdivRec*)p.partials,
+                             loss_out, terms_out, stats, st);
+}
+
+int mi_fdiv_concat_mlp_bwd(const float* x, const float* y, const float* w1, const float* b1, const float* w2,
+                           const float* b2, const float* w3, const float* b3, const int64_t* sid_rows,
+                           const int64_t* sid_cols, int64_t b_rows, int64_t b, int64_t row_offset, int64_t d_img,
+                           int64_t d_txt, int64_t h1, int64_t h2, int mode, int precision, const mi_stats* stats,
+                           const float* grad_out, const float* scores, float* grad_x, float* grad_y, float* grad_w1,
+                           float* grad_b1, float* grad_w2, float* grad_b2, float* grad_w3, float* grad_b3,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+  (void)b1;
+  (void)b3;
+  MI_CHECK_ARG(x && y && w1 && w2 && b2 && w3 && sid_rows && sid_cols && stats && scores && grad_x && grad_y &&
+                   grad_w1 && grad_b1 && grad_w2 && grad_b2 && grad_w3 && grad_b3 && workspace,
+               "mi_fdiv_concat_mlp_bwd: null pointer");
+  int rc = fdiv_check_mode("mi_fdiv_concat_mlp_bwd", mode);
+  if (rc) return rc;
+  rc = check_concat_shape("mi_fdiv_concat_mlp_bwd", b_rows, b, row_offset, d_img, d_txt, h1, h2, precision);
+  if (rc) return rc;
+  Workspace ws(workspace, workspace_bytes);
+  ConcatPlan p = plan_concat(ws, b_rows, b, h1, h2, precision, 1, d_img > d_txt ? d_img : d_txt);
+  if (!ws.ok()) {
+    set_error("mi_fdiv_concat_mlp_bwd: workspace too small (%zu < %zu): pass the workspace of the forward call made "
+              "with need_grad = 1",
+              workspace_bytes, ws.off);
+    return MI_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (mode == MI_FDIV_JSD)
+    return concat_bwd_dispatch<kGradJSD>(x, y, w1, w2, b2, w3, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt,
+                                         (int)h1, (int)h2, precision, stats, grad_out, scores, grad_x, grad_y, grad_w1,
+                                         grad_b1, grad_w2, grad_b2, grad_w3, grad_b3, p, st);
+  return concat_bwd_dispatch<kGradDV>(x, y, w1, w2, b2, w3, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt,
+                                      (int)h1, (int)h2, precision, stats, grad_out, scores, grad_x, grad_y, grad_w1,
+                                      grad_b1, grad_w2, grad_b2, grad_w3, grad_b3, p, st);
 }
 
 }  // extern "C"

@@ -13,15 +13,34 @@
 #pragma once
 #include "mi_common.h"
 #include "mi_concat_fwd.h"
+#include "mi_fdiv.h"
 
 namespace mi {
 
-// d loss / d score of pair (global row gi, column gj) times grad_out; 0 for dropped / out-of-range pairs
+// d loss / d score of pair (global row gi, column gj) times grad_out; 0 for dropped / out-of-range pairs.  R: the gradient
+// rule (mi_fdiv.h).  kGradDV serves DV, the reference's "infonce" and NWJ (whose statistics block holds lse = 1 + log
+// n_neg); kGradJSD: gpos sigma(-s) and gneg sigma(s), gneg = go / n_neg (fdiv_gneg).
+template <int R = kGradDV>
 __device__ __forceinline__ float pair_grad(float score, int64_t gi, int64_t gj, int64_t sid_i, int64_t sid_j, float lse,
-                                           float go, float gpos) {
+                                           float go, float gpos, float gneg = 0.0f) {
   const int kind = pair_kind(gi, gj, sid_i, sid_j);
-  if (kind == 1) return gpos;
-  if (kind == 2) return go * expf(score - lse);
+  if constexpr (R == kGradJSD) {
+    (void)lse;
+    (void)go;
+    if (kind == 1) return gpos * fdiv_sigmoid(-score);
+    if (kind == 2) return gneg * fdiv_sigmoid(score);
+    return 0.0f;
+  } else {
+    (void)gneg;
+    if (kind == 1) return gpos;
+    if (kind == 2) return go * expf(score - lse);
+    return 0.0f;
+  }
+}
+// the negative-pair weight of the JSD rule for the kernel's grad_out factor go (0, unused, under the DV rule)
+template <int R>
+__device__ __forceinline__ float fdiv_gneg(const mi_stats* st, float go) {
+  if constexpr (R == kGradJSD) return go / (float)st->n_neg;
   return 0.0f;
 }
 
@@ -54,8 +73,8 @@ struct F16Scales {
 // s_g: the scale of g in the dW2 kernel's generated operand g' relu(u + v).  A power of two derived from the statistics so
 // that the LARGEST |g| of the batch -- max(exp(neg_max - lse), 1 / n_pos), grad_out left out: it is applied to the finished
 // sums -- lands in [2^lo_exp, 2^(lo_exp + 1)).  (A fixed 2^12 put the products of a 16.8 M-pair batch, g ~ 6e-8, into the
-// fp16 subnormals.)  Every kernel derives it from the same statistics block with this function.
-__device__ __forceinline__ float f16_g_scale(const mi_stats* st, int lo_exp);
+// fp16 subnormals.)  Every kernel derives it from the same statistics block with f16_g_scale<R> (below).  Under the JSD
+// rule the largest |g| is bounded by max(1 / n_pos, 1 / n_neg) (sigma < 1), and the scale comes from that bound.
 // 2^e with 2^e * a in [2^lo_exp, 2^(lo_exp + 1)) for finite a > 0; 1 otherwise.  A pure function of the bits: every
 // kernel derives the same scale from the same absmax slots.
 __device__ __forceinline__ float f16_pow2_scale(float a, int lo_exp) {
@@ -78,7 +97,10 @@ __device__ __forceinline__ F16ScaleSet f16_scales(const F16Scales* sc) {
   r.s_uv3 = f16_pow2_scale(au + av, 13);
   return r;
 }
+template <int R = kGradDV>
 __device__ __forceinline__ float f16_g_scale(const mi_stats* st, int lo_exp) {
+  if constexpr (R == kGradJSD)  // n_neg == 0: 1 / 0 = inf, scale 1
+    return f16_pow2_scale(fmaxf(1.0f / (float)st->n_pos, 1.0f / (float)st->n_neg), lo_exp);
   const float gneg = expf(st->neg_max - st->lse);  // neg_max = -inf (no negatives): 0
   const float gpos = 1.0f / (float)st->n_pos;
   return f16_pow2_scale(fmaxf(gneg, gpos), lo_exp);
@@ -124,7 +146,7 @@ constexpr int kDuvTJ = 8;   // text columns per step
 
 // UvT: element type of U / V (fp32; fp16 in the fp16 mode, where relu' of layer 1 must be decided on the very values the
 // forward added).  sc != null (fp16 mode): W2wP carries the scale s_ww, undone through g.
-template <typename OpT, typename UvT = float>
+template <typename OpT, typename UvT = float, int R = kGradDV>
 __global__ __launch_bounds__(512) void concat_bwd_duv_kernel(
     const UvT* __restrict__ U, const UvT* __restrict__ V, const OpT* __restrict__ W2wP,
     const unsigned long long* __restrict__ bitsP, const float* __restrict__ S, const int64_t* __restrict__ sid_rows,
@@ -166,6 +188,7 @@ __global__ __launch_bounds__(512) void concat_bwd_duv_kernel(
   const float go = grad_out ? grad_out[0] : 1.0f;
   const float lse = stats->lse;
   const float gpos = -go / (float)stats->n_pos;
+  const float gneg = fdiv_gneg<R>(stats, go);
   float gscale = kBf16 ? 0.5f : 1.0f;  // the 16-bit fragment table holds 2.0 for a set bit
   if (sc) gscale /= f16_scales(sc).s_ww;
 
@@ -230,7 +253,7 @@ __global__ __launch_bounds__(512) void concat_bwd_duv_kernel(
       const int64_t li = i0 + il, gj = j + jl;
       float g = 0.0f;
       if (li < b_rows && gj < jhi)
-        g = gscale * pair_grad(S[li * b + gj], row_offset + li, gj, sid_rows[li], sid_cols[gj], lse, go, gpos);
+        g = gscale * pair_grad<R>(S[li * b + gj], row_offset + li, gj, sid_rows[li], sid_cols[gj], lse, go, gpos, gneg);
       gs[il * kDuvTJ + jl] = g;
       for (int e = tid; e < kDuvTJ * KC; e += 512) {
         const int jl2 = e / KC, kk = e % KC;
@@ -356,7 +379,7 @@ constexpr int kDw2IB = 128;  // image rows per g batch
 // X3 (OpT = f16_t; MI_PREC_F16X3): U, V are the scaled copies Us, Vs; the generated operand g' relu(u + v) is formed in
 // fp32 and split into two fp16 parts, two MFMAs per product (the bit operand {0, 2} is exact); grad_out is applied by the
 // finishing kernel (the slabs hold 2 s_uv s_g D, as in the fp16 mode).
-template <typename OpT, bool X3 = false>
+template <typename OpT, bool X3 = false, int R = kGradDV>
 __global__ __launch_bounds__(512) void concat_bwd_dw2_kernel(
     const float* __restrict__ U, const float* __restrict__ V, const unsigned* __restrict__ bitsN,
     const float* __restrict__ S, const int64_t* __restrict__ sid_rows, const int64_t* __restrict__ sid_cols,
@@ -387,7 +410,8 @@ __global__ __launch_bounds__(512) void concat_bwd_dw2_kernel(
   const float go = X3 ? 1.0f : (grad_out ? grad_out[0] : 1.0f);
   const float lse = stats->lse;
   const float gpos = -go / (float)stats->n_pos;
-  const float gscale = X3 ? f16_g_scale(stats, kF16X3GLo) : (kBf16 ? 0.5f : 1.0f);
+  const float gneg = fdiv_gneg<R>(stats, go);
+  const float gscale = X3 ? f16_g_scale<R>(stats, kF16X3GLo) : (kBf16 ? 0.5f : 1.0f);
 
   if constexpr (kBf16) {
     if (tid < 256) {
@@ -426,7 +450,7 @@ __global__ __launch_bounds__(512) void concat_bwd_dw2_kernel(
         const int64_t li = ib + il, gj = j0 + jl;
         float g = 0.0f;
         if (li < ihi && gj < b)
-          g = gscale * pair_grad(S[li * b + gj], row_offset + li, gj, sid_rows[li], sid_cols[gj], lse, go, gpos);
+          g = gscale * pair_grad<R>(S[li * b + gj], row_offset + li, gj, sid_rows[li], sid_cols[gj], lse, go, gpos, gneg);
         gs[e] = g;
       }
       __syncthreads();
@@ -545,6 +569,7 @@ __global__ __launch_bounds__(512) void concat_bwd_dw2_kernel(
 // ================================================================================================= small kernels
 // m[n] partial = sum over a slice of rows of g_p M[p, n]; also the slice's sum of g_p (db3).  One workgroup per row
 // slice, one thread per hidden unit n (512 threads -> H2 <= 512 per pass over n).
+template <int R = kGradDV>
 __global__ __launch_bounds__(512) void concat_bwd_db2_kernel(const unsigned* __restrict__ bitsN,
                                                              const float* __restrict__ S,
                                                              const int64_t* __restrict__ sid_rows,
@@ -565,6 +590,7 @@ __global__ __launch_bounds__(512) void concat_bwd_db2_kernel(const unsigned* __r
   const float go = grad_out ? grad_out[0] : 1.0f;
   const float lse = stats->lse;
   const float gpos = -go / (float)stats->n_pos;
+  const float gneg = fdiv_gneg<R>(stats, go);
   float gtot = 0.0f;
   float macc[2] = {0.0f, 0.0f};  // hidden units tid and tid + 512
   for (int64_t li = ilo; li < ihi; ++li) {
@@ -572,7 +598,7 @@ __global__ __launch_bounds__(512) void concat_bwd_db2_kernel(const unsigned* __r
     const int64_t si = sid_rows[li];
     for (int64_t gj = tid; gj < JB * 32; gj += 512) {
       float g = 0.0f;
-      if (gj < b) g = pair_grad(S[li * b + gj], row_offset + li, gj, si, sid_cols[gj], lse, go, gpos);
+      if (gj < b) g = pair_grad<R>(S[li * b + gj], row_offset + li, gj, si, sid_cols[gj], lse, go, gpos, gneg);
       grow[gj] = g;
       gtot += g;
     }
@@ -606,6 +632,7 @@ __global__ __launch_bounds__(512) void concat_bwd_db2_kernel(const unsigned* __r
 }
 
 // One workgroup per hidden unit n: D[n, :] = sum of slabs (fixed order); dW2[n, :] = w3[n] D; dW3[n], db2[n]; n == 0: db3.
+template <int R = kGradDV>
 __global__ __launch_bounds__(256) void concat_bwd_finish_w2_kernel(const float* __restrict__ Dslab, int n_dsplit,
                                                                    const float* __restrict__ mslab,
                                                                    const float* __restrict__ gsum, int n_msplit,
@@ -625,7 +652,7 @@ __global__ __launch_bounds__(256) void concat_bwd_finish_w2_kernel(const float* 
   if (sc) {
     const F16ScaleSet ss = f16_scales(sc);
     dscale = (grad_out ? grad_out[0] : 1.0f) /
-             (2.0f * f16_g_scale(stats, x3 ? kF16X3GLo : kF16GLo) * (x3 ? ss.s_uv3 : ss.s_uv));
+             (2.0f * f16_g_scale<R>(stats, x3 ? kF16X3GLo : kF16GLo) * (x3 ? ss.s_uv3 : ss.s_uv));
   }
   float dot = 0.0f;
   for (int k = tid; k < H1; k += 256) {

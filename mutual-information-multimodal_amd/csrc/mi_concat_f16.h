@@ -534,6 +534,7 @@ struct Dw2F16Smem {
   static constexpr int TOTAL = VT_BYTES + GS_BYTES + LUT_BYTES;
 };
 
+template <int R = kGradDV>
 __global__ __launch_bounds__(512) void concat_bwd_dw2_f16_kernel(
     const unsigned* __restrict__ Upk, const f16_t* __restrict__ VhT, const unsigned* __restrict__ bitsN,
     const float* __restrict__ S, const int64_t* __restrict__ sid_rows, const int64_t* __restrict__ sid_cols,
@@ -560,7 +561,8 @@ __global__ __launch_bounds__(512) void concat_bwd_dw2_f16_kernel(
 
   const float lse = stats->lse;
   const float gpos = -1.0f / (float)stats->n_pos;
-  const float gscale = f16_g_scale(stats, kF16GLo);
+  const float gneg = fdiv_gneg<R>(stats, 1.0f);
+  const float gscale = f16_g_scale<R>(stats, kF16GLo);
 
   if (tid < 256) {
     f16x8 f;
@@ -613,7 +615,7 @@ __global__ __launch_bounds__(512) void concat_bwd_dw2_f16_kernel(
         const int64_t li = ib + il, gj = j0 + jl;
         float g = 0.0f;
         if (li < ihi && gj < b)
-          g = gscale * pair_grad(S[li * b + gj], row_offset + li, gj, sid_rows[li], sid_cols[gj], lse, 1.0f, gpos);
+          g = gscale * pair_grad<R>(S[li * b + gj], row_offset + li, gj, sid_rows[li], sid_cols[gj], lse, 1.0f, gpos, gneg);
         gs[e] = (f16_t)g;
       }
       __syncthreads();
@@ -708,6 +710,7 @@ namespace mi {
 // v_dot2c_f32_f16 adds two products g' * bit per instruction into an fp32 sum -- 4 table reads + 4 reads of g' + 16 dots per
 // word.  Same outputs (row-slice sums of g M per hidden unit, the slice's sum of g for db3).  The sums come out scaled by
 // s_g and without grad_out, both applied to the finished sum.
+template <int R = kGradDV>
 __global__ __launch_bounds__(512) void concat_bwd_db2_f16_kernel(const unsigned* __restrict__ bitsN, const float* __restrict__ S,
                                                                  const int64_t* __restrict__ sid_rows,
                                                                  const int64_t* __restrict__ sid_cols,
@@ -729,7 +732,8 @@ __global__ __launch_bounds__(512) void concat_bwd_db2_f16_kernel(const unsigned*
   const float go = grad_out ? grad_out[0] : 1.0f;
   const float lse = stats->lse;
   const float gpos = -1.0f / (float)stats->n_pos;
-  const float gscale = f16_g_scale(stats, kF16GLo);
+  const float gneg = fdiv_gneg<R>(stats, 1.0f);
+  const float gscale = f16_g_scale<R>(stats, kF16GLo);
   if (tid < 256) {
     f16x8v f;
 #pragma unroll
@@ -743,7 +747,7 @@ __global__ __launch_bounds__(512) void concat_bwd_db2_f16_kernel(const unsigned*
     const int64_t si = sid_rows[li];
     for (int64_t gj = tid; gj < JB * 32; gj += 512) {
       float g = 0.0f;
-      if (gj < b) g = pair_grad(S[li * b + gj], row_offset + li, gj, si, sid_cols[gj], lse, 1.0f, gpos);
+      if (gj < b) g = pair_grad<R>(S[li * b + gj], row_offset + li, gj, si, sid_cols[gj], lse, 1.0f, gpos, gneg);
       grow[gj] = (f16_t)(g * gscale);
       gtot += g;
     }
@@ -814,7 +818,7 @@ constexpr int kDuv3TJ = 4;  // text columns per step
 
 // X3 (MI_PREC_F16X3): W2wP holds TWO parts per element, [2][H1][H2] (hi, lo); the slice of both sits in LDS (one workgroup
 // per CU then) and every product is two MFMAs (the bit operand is exact).
-template <typename OpT, typename UvT, bool X3 = false>
+template <typename OpT, typename UvT, bool X3 = false, int R = kGradDV>
 __global__ __launch_bounds__(256, 2) void concat_bwd_duv3_kernel(
     const UvT* __restrict__ U, const UvT* __restrict__ V, const OpT* __restrict__ W2wP,
     const unsigned long long* __restrict__ bitsP, const float* __restrict__ S, const int64_t* __restrict__ sid_rows,
@@ -850,6 +854,7 @@ __global__ __launch_bounds__(256, 2) void concat_bwd_duv3_kernel(
   const float go = grad_out ? grad_out[0] : 1.0f;
   const float lse = stats->lse;
   const float gpos = -go / (float)stats->n_pos;
+  const float gneg = fdiv_gneg<R>(stats, go);
   float gscale = 0.5f;  // the fragment table holds 2.0 for a set bit
   if (sc) gscale /= f16_scales(sc).s_ww;
 
@@ -930,7 +935,7 @@ __global__ __launch_bounds__(256, 2) void concat_bwd_duv3_kernel(
     {
       const int64_t gj = j + (c & 3);
       float g = 0.0f;
-      if (grow_ok && gj < jhi) g = gscale * pair_grad(s_next, row_offset + grow, gj, gsid, sidc_next, lse, go, gpos);
+      if (grow_ok && gj < jhi) g = gscale * pair_grad<R>(s_next, row_offset + grow, gj, gsid, sidc_next, lse, go, gpos, gneg);
       gsw[wave * 64 + lane] = g;
       const int64_t gjn = gj + kDuv3TJ;
       if (grow_ok && gjn < jhi) {

@@ -23,6 +23,9 @@ ESTIMATORS = {"dv": MI_DV, "infonce": MI_INFONCE}
 # entry points above
 MI_NCE_ROWWISE, MI_NCE_SYMMETRIC = 0, 1
 NCE_ESTIMATORS = {"infonce_rowwise": MI_NCE_ROWWISE, "infonce_symmetric": MI_NCE_SYMMETRIC}
+# the Jensen-Shannon and NWJ bounds (mi_fdiv_*): mode codes of their own entry points, not estimator codes either
+MI_FDIV_JSD, MI_FDIV_NWJ = 0, 1
+FDIV_ESTIMATORS = {"jsd": MI_FDIV_JSD, "nwj": MI_FDIV_NWJ}
 PRECISIONS = {"f32": MI_PREC_F32, "fp32": MI_PREC_F32, "float32": MI_PREC_F32, "f32_exact": MI_PREC_F32,
               "bf16": MI_PREC_BF16, "bfloat16": MI_PREC_BF16, "bf16x3": MI_PREC_BF16X3, "fp8": MI_PREC_FP8,
               "f16": MI_PREC_F16, "fp16": MI_PREC_F16, "float16": MI_PREC_F16, "f16x3": MI_PREC_F16X3}
@@ -106,6 +109,18 @@ SIGNATURES = {
     "mi_nce_separable_shard_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I64, _I]),
     "mi_nce_separable_shard_fwd": (c_int, [_P] * 6 + [_I64] * 6 + [_I, _I] + [_P] * 3 + [_SZ, _P]),
     "mi_nce_separable_shard_bwd": (c_int, [_P] * 6 + [_I64] * 6 + [_I, _I] + [_P] * 7 + [_SZ, _P]),
+    "mi_fdiv_bound_workspace_bytes": (_SZ, [_I64]),
+    "mi_fdiv_bound_fwd": (c_int, [_P, _I64, _I64, _I, _P, _P, _P, _P, _SZ, _P]),
+    "mi_fdiv_bound_bwd": (c_int, [_P, _I64, _I64, _I, _P, _P, _P, _P]),
+    "mi_fdiv_matrix_workspace_bytes": (_SZ, [_I64]),
+    "mi_fdiv_matrix_fwd": (c_int, [_P, _P, _I64, _I, _P, _P, _P, _P, _SZ, _P]),
+    "mi_fdiv_matrix_bwd": (c_int, [_P, _P, _I64, _I, _P, _P, _P, _P]),
+    "mi_fdiv_bilinear_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I]),
+    "mi_fdiv_bilinear_step": (c_int, [_P] * 4 + [_I64] * 3 + [_I, _I] + [_P] * 8 + [_SZ, _P]),
+    "mi_fdiv_separable_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I]),
+    "mi_fdiv_separable_step": (c_int, [_P] * 5 + [_I64] * 4 + [_I, _I] + [_P] * 9 + [_SZ, _P]),
+    "mi_fdiv_concat_mlp_fwd": (c_int, [_P] * 10 + [_I64] * 7 + [_I, _I, _I] + [_P] * 5 + [_SZ, _P]),
+    "mi_fdiv_concat_mlp_bwd": (c_int, [_P] * 10 + [_I64] * 7 + [_I, _I] + [_P] * 12 + [_SZ, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -125,6 +125,17 @@ class _HipOps:
         self.nce_call(x, y, params, sid, mode, precision, loss, r, c, grads, ws)()
         return loss, r, c, grads
 
+    def fdiv_step(self, x, y, params, sid, mode, precision, need_grad):
+        """Jensen-Shannon / NWJ bound of the whole batch in one call (bilinear and separable critics), with the gradients of
+        1 * loss when ``need_grad``: (loss [1], terms [2], [grad_x, grad_y, grad_params...] or [])."""
+        b, dev = x.shape[0], x.device
+        ws = _hip.workspace(self.fdiv_workspace_bytes(b, x.shape[1], y.shape[1], params, precision), dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        terms = torch.empty(2, dtype=torch.float32, device=dev)
+        grads = [torch.empty_like(t) for t in (x, y, *params)] if need_grad else []
+        self.fdiv_call(x, y, params, sid, mode, precision, loss, terms, grads, ws)()
+        return loss, terms, grads
+
     # ---------------------------------------------- per-sample InfoNCE on a row block (distributed.GlobalBatchNceFn)
     def nce_forward(self, x, y_all, params, sid_rows, sid_all, row_offset, mode, precision, need_grad=True):
         """The row block's part (``mi_nce_part_floats`` floats, gathered in rank order by the caller) and its row LSEs:
@@ -207,6 +218,17 @@ class HipBilinearOps(_HipOps):
         gx, gy, gw = (grads + [None] * 3)[:3]
         return _call("mi_nce_bilinear_step", x.device, x.data_ptr(), y.data_ptr(), _p(w), sid.data_ptr(), x.shape[0],
                      x.shape[1], y.shape[1], mode, precision, None, loss.data_ptr(), r.data_ptr(), c.data_ptr(), _p(gx),
+                     _p(gy), _p(gw), ws.data_ptr(), ws.numel())
+
+    @staticmethod
+    def fdiv_workspace_bytes(b, dx, dy, params, precision):
+        return _hip.load().mi_fdiv_bilinear_workspace_bytes(b, dx, dy, precision)
+
+    def fdiv_call(self, x, y, params, sid, mode, precision, loss, terms, grads, ws):
+        w = params[0] if params else None
+        gx, gy, gw = (grads + [None] * 3)[:3]
+        return _call("mi_fdiv_bilinear_step", x.device, x.data_ptr(), y.data_ptr(), _p(w), sid.data_ptr(), x.shape[0],
+                     x.shape[1], y.shape[1], mode, precision, None, loss.data_ptr(), terms.data_ptr(), None, _p(gx),
                      _p(gy), _p(gw), ws.data_ptr(), ws.numel())
 
     @staticmethod
@@ -366,6 +388,17 @@ class HipSeparableOps(_HipOps):
                      ws.numel())
 
     @staticmethod
+    def fdiv_workspace_bytes(b, dx, dy, params, precision):
+        return _hip.load().mi_fdiv_separable_workspace_bytes(b, dx, dy, params[0].shape[1], precision)
+
+    def fdiv_call(self, x, y, params, sid, mode, precision, loss, terms, grads, ws):
+        wg, wh = params
+        return _call("mi_fdiv_separable_step", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
+                     sid.data_ptr(), x.shape[0], x.shape[1], y.shape[1], wg.shape[1], mode, precision, None,
+                     loss.data_ptr(), terms.data_ptr(), None, *[_p(g) for g in grads or [None] * 4], ws.data_ptr(),
+                     ws.numel())
+
+    @staticmethod
     def nce_shard_workspace_bytes(br, b, dx, dy, params, precision):
         return _hip.load().mi_nce_separable_shard_workspace_bytes(br, b, dx, dy, params[0].shape[1], precision)
 
@@ -410,6 +443,31 @@ class HipConcatMlpOps(_HipOps):
                      params[0].shape[0], params[2].shape[0], precision, stats.data_ptr(), grad_out.data_ptr(),
                      scores.data_ptr(), gx.data_ptr(), gy.data_ptr(), *[g.data_ptr() for g in gp], ws.data_ptr(),
                      ws.numel())
+
+    # ---------------------------------------------- Jensen-Shannon / NWJ bounds (mi_fdiv_concat_mlp_*)
+    def fdiv_forward(self, x, y_all, params, sid_rows, sid_all, row_offset, mode, precision, need_grad):
+        """(loss [1], terms [2], saved) of the row block; ``saved`` = (..., mode, precision, scores, stats, ws) for
+        ``fdiv_backward``."""
+        dev = x.device
+        ws = _hip.workspace(self.workspace_bytes(x.shape[0], y_all.shape[0], x.shape[1], y_all.shape[1], params,
+                                                 precision, int(bool(need_grad))), dev)
+        loss, terms = torch.empty(1, dtype=torch.float32, device=dev), torch.empty(2, dtype=torch.float32, device=dev)
+        stats, scores = _hip.new_stats(dev), self._scores(x, y_all)
+        _hip.call("mi_fdiv_concat_mlp_fwd", dev, x.data_ptr(), y_all.data_ptr(), *[p.data_ptr() for p in params],
+                  sid_rows.data_ptr(), sid_all.data_ptr(), x.shape[0], y_all.shape[0], row_offset, x.shape[1],
+                  y_all.shape[1], params[0].shape[0], params[2].shape[0], mode, precision, int(bool(need_grad)),
+                  loss.data_ptr(), terms.data_ptr(), stats.data_ptr(), scores.data_ptr(), ws.data_ptr(), ws.numel())
+        return loss, terms, (x, y_all, list(params), sid_rows, sid_all, row_offset, mode, precision, scores, stats, ws)
+
+    def fdiv_backward(self, saved, grad_out):
+        """(grad_x, grad_y, [grad_params...]) of grad_out[0] * loss from the forward's scores, statistics and workspace."""
+        x, y, params, sid_rows, sid_all, row_offset, mode, precision, scores, stats, ws = saved
+        gx, gy, gp = torch.empty_like(x), torch.empty_like(y), [torch.empty_like(p) for p in params]
+        _hip.call("mi_fdiv_concat_mlp_bwd", x.device, x.data_ptr(), y.data_ptr(), *[p.data_ptr() for p in params],
+                  sid_rows.data_ptr(), sid_all.data_ptr(), x.shape[0], y.shape[0], row_offset, x.shape[1], y.shape[1],
+                  params[0].shape[0], params[2].shape[0], mode, precision, stats.data_ptr(), grad_out.data_ptr(),
+                  scores.data_ptr(), gx.data_ptr(), gy.data_ptr(), *[g.data_ptr() for g in gp], ws.data_ptr(), ws.numel())
+        return gx, gy, gp
 
 
 OPS = {"bilinear": HipBilinearOps, "separable": HipSeparableOps, "concat_mlp": HipConcatMlpOps}

@@ -237,7 +237,10 @@ def global_batch_mi_bound(embedding_img, embedding_txt, study_id_codes, critic_p
     ``estimator`` = "infonce_rowwise" / "infonce_symmetric" (critic "bilinear" or "separable"): the per-sample InfoNCE
     normalised over the global batch (GlobalBatchNceFn), loss of shape []; ``return_stats=True`` then gives
     ``(loss, (lse_rows [B/G], lse_cols [B]))``."""
-    from .mi_critics import NCE_ESTIMATORS, _estimator_code
+    from .mi_critics import FDIV_ESTIMATORS, NCE_ESTIMATORS, _estimator_code
+    if estimator in FDIV_ESTIMATORS:
+        raise ValueError(f"mi_estimator {estimator!r}: the JSD / NWJ bounds are implemented on one GPU only "
+                         "(fused_mi_bound); the sharded global-batch step does not take them")
     if estimator in NCE_ESTIMATORS:
         if critic not in ("bilinear", "separable"):
             raise ValueError(f"mi_estimator {estimator!r} is implemented for the bilinear and separable critics only; for "
@@ -285,7 +288,10 @@ class GlobalBatchGraphStep:
 
     def __init__(self, x, y, sid, params: Sequence[torch.Tensor], estimator: str = "infonce", precision: str = "bf16",
                  critic: str = "bilinear", group=None, ops=None, capture: bool = True, overlap_reduce_scatter=None):
-        from .mi_critics import _estimator_code
+        from .mi_critics import FDIV_ESTIMATORS, _estimator_code
+        if estimator in FDIV_ESTIMATORS:
+            raise ValueError(f"mi_estimator {estimator!r}: the JSD / NWJ bounds are implemented on one GPU only "
+                             "(fused_mi_bound); the sharded graphed step does not take them")
         self.group = group
         # step_eager(): start the reduce-scatter of dY between the backward's two launches (it then runs beside dW).  OFF by
         # default: with direct calls the step is bound by the HOST (one-rank RCCL rehearsal, B = 4096: 0.196 ms per step

@@ -39,6 +39,9 @@ class GraphedMiStep:
         if self.device.type != "cuda":
             raise _hip.MiCriticError("GraphedMiStep needs a ROCm device (no CPU fallback)")
         self.lib = _hip.load()
+        if estimator in _hip.FDIV_ESTIMATORS:
+            raise ValueError(f"mi_estimator {estimator!r}: the JSD / NWJ bounds run eagerly (fused_mi_bound, "
+                             "MultiModalManager.mi_step); graph capture of them is not implemented")
         self.est = _estimator_code(estimator)
         self.estimator = estimator
         self.b, self.dx, self.dy = int(batch_size), int(d_img), int(d_txt)

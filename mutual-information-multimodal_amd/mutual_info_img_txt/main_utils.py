@@ -155,7 +155,21 @@ class MultiModalManager:
         module, bound kernel) and is only practical for small batches.  ``graph=True`` replays the fused step from
         hipGraphs (``graphed.GraphedMiStep``, built on first use for this batch shape; the training loop's setting).
         "infonce_rowwise" / "infonce_symmetric" always run eagerly through ``fused_mi_bound`` (one library call per step;
-        ``graph`` is ignored for them: GraphedMiStep captures the reference's estimators only)."""
+        ``graph`` is ignored for them: GraphedMiStep captures the reference's estimators only).  So do the Jensen-Shannon and
+        NWJ bounds "jsd" / "nwj" (every critic); ``fused=False`` runs them on ``create_mi_pairs`` output through
+        ``jsd_bound_loss`` / ``nwj_bound_loss`` for the concat critic, on the score matrix for the others."""
+        if mi_estimator in mi_critics.FDIV_ESTIMATORS:
+            mi_critics.check_estimator(mi_estimator, self.critic_kind)
+            if fused:
+                return mi_critics.fused_mi_bound(embedding_img, embedding_txt, study_id, self.mi_discriminator,
+                                                 mi_estimator, precision)
+            if self.critic_kind != "concat_mlp":
+                scores = self.mi_discriminator(embedding_img, embedding_txt)
+                return mi_critics.matrix_bound_loss(scores, study_id, mi_estimator)
+            mi_input = self.create_mi_pairs(embedding_img, embedding_txt, study_id, embedding_img.device)
+            mi_output = self.mi_discriminator(mi_input)
+            critic = {"jsd": mi_critics.jsd_bound_loss, "nwj": mi_critics.nwj_bound_loss}[mi_estimator]
+            return critic(mi_output, len(study_id), embedding_img.device)
         if mi_estimator in mi_critics.NCE_ESTIMATORS:
             mi_critics.check_estimator(mi_estimator, self.critic_kind)
             if not fused:

@@ -13,7 +13,10 @@ plus the fused entry point that replaces lines ``main_utils.py:220-224`` of the 
 Besides the reference's two estimators, ``fused_mi_bound`` (bilinear and separable critics) and ``matrix_bound_loss``
 take the per-sample InfoNCE of CPC / ConVIRT / CLIP: ``"infonce_rowwise"`` (image -> report cross-entropy) and
 ``"infonce_symmetric"`` (its mean with report -> image), with the reference's masking of equal-id pairs (DESIGN.md
-section 8).
+section 8), and every critic and ``matrix_bound_loss`` take the Jensen-Shannon bound ``"jsd"`` and the NWJ bound ``"nwj"``
+(DESIGN.md section 9), also as reference-style callables on logits:
+
+* ``jsd_bound_loss(discriminator_logits, pos_size, device)``, ``nwj_bound_loss(...)`` -- returns shape []
 
 Every function runs hand-written HIP kernels through the C ABI in ``include/mi_critic.h`` (loaded with ctypes,
 wrapped in ``torch.autograd.Function``).  There is no CPU path: CPU tensors raise.
@@ -25,13 +28,14 @@ from typing import Optional, Sequence, Union
 import torch
 
 from . import _hip
-from ._hip import ESTIMATORS, NCE_ESTIMATORS
+from ._hip import ESTIMATORS, FDIV_ESTIMATORS, NCE_ESTIMATORS
 from .critic_ops import (HipBilinearOps, HipConcatMlpOps, HipSeparableOps, _concat_params,  # noqa: F401 (re-exported)
                          _precision_code, fwd_outputs, resolve_critic)
 
 __all__ = ["dv_bound_loss", "infonce_bound_loss", "matrix_bound_loss", "fused_mi_bound", "study_id_codes",
            "BilinearCriticFn", "SeparableCriticFn", "ConcatMlpCriticFn", "NceBilinearFn", "NceSeparableFn",
-           "check_estimator"]
+           "check_estimator", "jsd_bound_loss", "nwj_bound_loss", "FdivBilinearFn", "FdivSeparableFn",
+           "FdivConcatMlpFn"]
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -55,8 +59,10 @@ def _estimator_code(estimator: str) -> int:
 
 def check_estimator(estimator: str, critic_kind: str) -> None:
     """Eager validation of an estimator name for a critic kind ("concat_mlp", "bilinear", "separable"): the reference's
-    "dv" / "infonce" for every critic, the per-sample "infonce_rowwise" / "infonce_symmetric" for the bilinear and
-    separable critics only."""
+    "dv" / "infonce" and the Jensen-Shannon / NWJ bounds "jsd" / "nwj" for every critic, the per-sample
+    "infonce_rowwise" / "infonce_symmetric" for the bilinear and separable critics only."""
+    if estimator in FDIV_ESTIMATORS:
+        return
     if estimator in NCE_ESTIMATORS:
         if critic_kind not in ("bilinear", "separable"):
             raise ValueError(f"mi_estimator {estimator!r} is implemented for the bilinear and separable critics only "
@@ -64,7 +70,7 @@ def check_estimator(estimator: str, critic_kind: str) -> None:
         return
     if estimator not in ESTIMATORS:
         raise ValueError(f"unknown mi_estimator {estimator!r}: expected one of "
-                         f"{sorted(ESTIMATORS) + sorted(NCE_ESTIMATORS)}")
+                         f"{sorted(ESTIMATORS) + sorted(NCE_ESTIMATORS) + sorted(FDIV_ESTIMATORS)}")
 
 
 def _grad_scalar(grad: torch.Tensor) -> torch.Tensor:
@@ -125,6 +131,54 @@ def infonce_bound_loss(discriminator_logits: torch.Tensor, pos_size: int, device
     return _bound(discriminator_logits, pos_size, _hip.MI_INFONCE).reshape(())
 
 
+class _FdivBoundFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits: torch.Tensor, pos_size: int, mode: int):
+        lib = _hip.load()
+        flat = _hip.f32c(logits, "discriminator_logits").reshape(-1)
+        n, dev = flat.numel(), flat.device
+        ws = _hip.workspace(lib.mi_fdiv_bound_workspace_bytes(n), dev)
+        stats = _hip.new_stats(dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        _hip.call("mi_fdiv_bound_fwd", dev, flat.data_ptr(), n, int(pos_size), mode, loss.data_ptr(), None,
+                  stats.data_ptr(), ws.data_ptr(), ws.numel())
+        ctx.save_for_backward(flat, stats)
+        ctx.pos_size, ctx.mode, ctx.in_shape = int(pos_size), mode, logits.shape
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        flat, stats = ctx.saved_tensors
+        go = _grad_scalar(grad_loss)
+        grad = torch.empty_like(flat)
+        _hip.call("mi_fdiv_bound_bwd", flat.device, flat.data_ptr(), flat.numel(), ctx.pos_size, ctx.mode,
+                  stats.data_ptr(), go.data_ptr(), grad.data_ptr())
+        return grad.reshape(ctx.in_shape), None, None
+
+
+def _fdiv_bound(discriminator_logits, pos_size, mode):
+    _hip.require_device(discriminator_logits, "discriminator_logits")
+    n = discriminator_logits.shape[0]
+    if discriminator_logits.numel() != n:
+        raise ValueError("discriminator_logits must be [N] or [N, 1] (one score per pair row)")
+    if not 0 <= int(pos_size) <= n:
+        raise ValueError(f"pos_size={pos_size} outside [0, {n}]")
+    return _FdivBoundFn.apply(discriminator_logits, int(pos_size), mode).reshape(())
+
+
+def jsd_bound_loss(discriminator_logits: torch.Tensor, pos_size: int, device=None) -> torch.Tensor:
+    """Jensen-Shannon bound (Deep InfoMax) on the reference's logits layout (the first ``pos_size`` rows positive):
+    ``mean(softplus(-logits[:pos])) + mean(softplus(logits[pos:]))``, shape [].  Finite for any finite logits.  ``device``
+    is kept for the signature of the reference's callables."""
+    return _fdiv_bound(discriminator_logits, pos_size, _hip.MI_FDIV_JSD)
+
+
+def nwj_bound_loss(discriminator_logits: torch.Tensor, pos_size: int, device=None) -> torch.Tensor:
+    """NWJ bound (f-GAN KL, "MINE-f") on the reference's logits layout: ``exp(LSE(logits[pos:]) - log(N - pos) - 1) -
+    mean(logits[:pos])``, shape []; ``-loss`` is the NWJ lower bound on the MI."""
+    return _fdiv_bound(discriminator_logits, pos_size, _hip.MI_FDIV_NWJ)
+
+
 # ----------------------------------------------------------------------------------------------------------
 # bound on a B x B score matrix with study-id masking
 # ----------------------------------------------------------------------------------------------------------
@@ -181,15 +235,47 @@ class _MatrixNceFn(torch.autograd.Function):
         return grad, None, None
 
 
+class _MatrixFdivFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores: torch.Tensor, sid: torch.Tensor, mode: int):
+        lib = _hip.load()
+        s = _hip.f32c(scores, "scores")
+        b, dev = s.shape[0], s.device
+        ws = _hip.workspace(lib.mi_fdiv_matrix_workspace_bytes(b), dev)
+        stats = _hip.new_stats(dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        _hip.call("mi_fdiv_matrix_fwd", dev, s.data_ptr(), sid.data_ptr(), b, mode, loss.data_ptr(), None,
+                  stats.data_ptr(), ws.data_ptr(), ws.numel())
+        ctx.save_for_backward(s, sid, stats)
+        ctx.mode = mode
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        s, sid, stats = ctx.saved_tensors
+        go = _grad_scalar(grad_loss)
+        grad = torch.empty_like(s)
+        _hip.call("mi_fdiv_matrix_bwd", s.device, s.data_ptr(), sid.data_ptr(), s.shape[0], ctx.mode, stats.data_ptr(),
+                  go.data_ptr(), grad.data_ptr())
+        return grad, None, None
+
+
 def matrix_bound_loss(scores: torch.Tensor, study_id, estimator: str = "dv") -> torch.Tensor:
     """The reference loss on a [B,B] score matrix S[i,j] = critic(img_i, txt_j): positives are the diagonal, negatives
     the pairs with i != j and different study ids (main_utils.py:99-108).  Shape [1] (dv) / [] (infonce).
 
     "infonce_rowwise" / "infonce_symmetric": the per-sample InfoNCE on the same scores and masking,
-    shape [], gradients to ``scores``.  The way to that loss for any critic whose scores you compute yourself."""
+    shape [], gradients to ``scores``.  The way to that loss for any critic whose scores you compute yourself.
+
+    "jsd" / "nwj": the Jensen-Shannon and NWJ bounds on the same pairs, shape []."""
     _hip.require_device(scores, "scores")
     if scores.dim() != 2 or scores.shape[0] != scores.shape[1]:
         raise ValueError("scores must be [B, B]")
+    if estimator in FDIV_ESTIMATORS:
+        sid = study_id_codes(study_id, scores.device)
+        if sid.numel() != scores.shape[0]:
+            raise ValueError("study_id length must equal B")
+        return _MatrixFdivFn.apply(scores, sid, FDIV_ESTIMATORS[estimator]).reshape(())
     if estimator in NCE_ESTIMATORS:
         sid = study_id_codes(study_id, scores.device)
         if sid.numel() != scores.shape[0]:
@@ -320,6 +406,98 @@ class NceSeparableFn(torch.autograd.Function):
         return _nce_backward(ctx, grad_loss, "NceSeparableFn")
 
 
+def _fdiv_step_forward(ctx, ops, x, y, params, sid, mode, precision, need_grad):
+    loss, terms, grads = ops.fdiv_step(x, y, params, sid, mode, precision, need_grad)
+    ctx.save_for_backward(*grads)
+    ctx.mark_non_differentiable(terms)
+    return loss, terms
+
+
+class FdivBilinearFn(torch.autograd.Function):
+    """Jensen-Shannon / NWJ bound of S = (X W) Y^T (W None: S = X Y^T) in one library call (mi_fdiv_bilinear_step); with
+    ``need_grad`` the call also writes every gradient for dL/dloss = 1, the backward scales them.  Returns (loss [1],
+    terms [2])."""
+
+    @staticmethod
+    def forward(ctx, x, y, w, sid, mode: int, precision: int, need_grad: bool):
+        x, y = _hip.f32c(x, "embedding_img"), _hip.f32c(y, "embedding_txt")
+        params = [] if w is None else [_hip.f32c(w, "bilinear weight")]
+        return _fdiv_step_forward(ctx, HipBilinearOps(), x, y, params, sid, mode, precision, need_grad)
+
+    @staticmethod
+    def backward(ctx, grad_loss, _gt):
+        return _nce_backward(ctx, grad_loss, "FdivBilinearFn")
+
+
+class FdivSeparableFn(torch.autograd.Function):
+    """Jensen-Shannon / NWJ bound of S = (X Wg)(Y Wh)^T in one library call (mi_fdiv_separable_step); see
+    FdivBilinearFn."""
+
+    @staticmethod
+    def forward(ctx, x, y, wg, wh, sid, mode: int, precision: int, need_grad: bool):
+        x, y = _hip.f32c(x, "embedding_img"), _hip.f32c(y, "embedding_txt")
+        params = [_hip.f32c(wg, "image projection"), _hip.f32c(wh, "text projection")]
+        return _fdiv_step_forward(ctx, HipSeparableOps(), x, y, params, sid, mode, precision, need_grad)
+
+    @staticmethod
+    def backward(ctx, grad_loss, _gt):
+        return _nce_backward(ctx, grad_loss, "FdivSeparableFn")
+
+
+class FdivConcatMlpFn(torch.autograd.Function):
+    """Jensen-Shannon / NWJ bound of S[i,j] = MLP([x_i ; y_j]) (make_mlp(d,[h1,h2])): the fused forward writes scores,
+    sign-bit images and statistics; the backward kernels run under the mode's gradient rule.  Returns (loss [1],
+    terms [2], scores [B, B])."""
+
+    @staticmethod
+    def forward(ctx, x, y, w1, b1, w2, b2, w3, b3, sid, mode: int, precision: int):
+        x, y = _hip.f32c(x, "embedding_img"), _hip.f32c(y, "embedding_txt")
+        params = [_hip.f32c(p, f"critic param {n}") for n, p in enumerate((w1, b1, w2, b2, w3, b3))]
+        need_grad = any(ctx.needs_input_grad)
+        loss, terms, saved = HipConcatMlpOps().fdiv_forward(x, y, params, sid, sid, 0, mode, precision, need_grad)
+        scores, stats, ws = saved[8:]
+        ctx.save_for_backward(x, y, sid, scores, stats, ws, *params)
+        ctx.mode, ctx.precision = mode, precision
+        ctx.mark_non_differentiable(terms, scores)
+        return loss, terms, scores
+
+    @staticmethod
+    def backward(ctx, grad_loss, _gt, _gs):
+        x, y, sid, scores, stats, ws, *params = ctx.saved_tensors
+        saved = (x, y, params, sid, sid, 0, ctx.mode, ctx.precision, scores, stats, ws)
+        gx, gy, gp = HipConcatMlpOps().fdiv_backward(saved, _grad_scalar(grad_loss))
+        return (gx, gy, *gp, None, None, None)
+
+
+def _fused_fdiv(x, y, study_id, critic, estimator, precision, return_scores, return_stats):
+    """fused_mi_bound for "jsd" / "nwj" (every critic)."""
+    if critic is None:
+        raise TypeError("critic must be a make_mlp critic, a BilinearCritic or a SeparableCritic")
+    sid = _batch_codes(x, y, study_id)
+    kind, params, prec = resolve_critic(critic, precision, x.shape[0], x.shape[1], y.shape[1])
+    mode = FDIV_ESTIMATORS[estimator]
+    scores = None
+    if kind == "concat_mlp":
+        w1, b1, w2, b2, w3, b3 = params
+        loss, terms, scores = FdivConcatMlpFn.apply(x, y, w1, b1, w2, b2, w3.reshape(-1), b3, sid, mode, prec)
+    else:
+        # "f32": bf16x3 on the bilinear critic where every size is a multiple of 8, exact fp32 products otherwise (the
+        # library rejects fp8 / f16 / f16x3 for these critics)
+        need_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, *params))
+        fn = FdivBilinearFn if kind == "bilinear" else FdivSeparableFn
+        loss, terms = fn.apply(x, y, *params, sid, mode, prec, need_grad)
+        if return_scores:  # diagnostic output: no gradient flows through it
+            with torch.no_grad():
+                a, c, w = (x, y, critic.weight) if kind == "bilinear" else (critic.project_img(x), critic.project_txt(y), None)
+                scores = BilinearCriticFn.apply(a, c, w, sid, _hip.MI_DV, prec, True)[2]
+    out = [loss.reshape(())]
+    if return_scores:
+        out.append(scores)
+    if return_stats:
+        out.append((terms[0], terms[1]))
+    return out[0] if len(out) == 1 else tuple(out)
+
+
 def _batch_codes(embedding_img, embedding_txt, study_id) -> torch.Tensor:
     """Shape checks of one batch; its study-id codes."""
     if embedding_img.dim() != 2 or embedding_txt.dim() != 2 or embedding_img.shape[0] != embedding_txt.shape[0]:
@@ -387,6 +565,9 @@ def fused_mi_bound(embedding_img: torch.Tensor, embedding_txt: torch.Tensor, stu
     (DESIGN.md section 8), loss of shape [], precisions "f32" / "f32_exact" / "bf16" / "bf16x3";
     ``return_stats=True`` then gives ``(lse_rows, lse_cols)``, the row and column log-sum-exps.  A make_mlp critic raises
     ValueError: apply it to the pairs yourself and call ``matrix_bound_loss(scores, study_id, estimator)``.
+
+    ``estimator`` = "jsd" / "nwj" (every critic): the Jensen-Shannon and NWJ bounds, loss of shape
+    []; ``return_stats=True`` then gives ``(positive-pair term, negative-pair term)``, two 0-d tensors whose sum is the loss.
     """
     _hip.require_device(embedding_img, "embedding_img")
     _hip.require_device(embedding_txt, "embedding_txt")
@@ -394,6 +575,9 @@ def fused_mi_bound(embedding_img: torch.Tensor, embedding_txt: torch.Tensor, stu
         embedding_img = embedding_img.float()
     if embedding_txt.dtype == torch.float64:
         embedding_txt = embedding_txt.float()
+    if estimator in FDIV_ESTIMATORS:
+        return _fused_fdiv(embedding_img, embedding_txt, study_id, critic, estimator, precision, return_scores,
+                           return_stats)
     if estimator in NCE_ESTIMATORS:
         return _fused_nce(embedding_img, embedding_txt, study_id, critic, estimator, precision, return_scores, return_stats)
     code = _estimator_code(estimator)

@@ -32,7 +32,7 @@ def construct_training_parameters(argv=None):
     return p.parse_args(argv)
 
 
-MI_ESTIMATORS = ('dv', 'infonce', 'infonce_rowwise', 'infonce_symmetric')
+MI_ESTIMATORS = ('dv', 'infonce', 'infonce_rowwise', 'infonce_symmetric', 'jsd', 'nwj')  # jsd / nwj: every critic
 PER_SAMPLE_ESTIMATORS = ('infonce_rowwise', 'infonce_symmetric')  # per-sample InfoNCE: bilinear / separable critics only
 
 
