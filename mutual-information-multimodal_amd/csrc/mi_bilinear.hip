@@ -686,10 +686,8 @@ int mi_bilinear_fwd(const float* x, const float* y, const float* w, const int64_
   MI_CHECK_ARG(estimator == MI_DV || estimator == MI_INFONCE, "mi_bilinear_fwd: unknown estimator %d", estimator);
   Workspace ws(workspace, workspace_bytes);
   BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, precision);
-  if (!ws.ok()) {
-    set_error("mi_bilinear_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  rc = ws_fits(ws, "mi_bilinear_fwd");
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (precision == MI_PREC_FP8) {
     if (!fp8_ok(b_rows, b, d_img, d_txt, precision, w != nullptr)) {
@@ -722,10 +720,8 @@ int mi_bilinear_bwd(const float* x, const float* y, const float* w, const int64_
   if (rc) return rc;
   Workspace ws(workspace, workspace_bytes);
   BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, precision);
-  if (!ws.ok()) {
-    set_error("mi_bilinear_bwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  rc = ws_fits(ws, "mi_bilinear_bwd");
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (precision == MI_PREC_FP8) {
     if (!fp8_ok(b_rows, b, d_img, d_txt, precision, w != nullptr)) {
@@ -789,10 +785,8 @@ int mi_bilinear_bwd_records(const float* x, const float* y, const float* w, cons
   if (rc) return rc;
   Workspace ws(workspace, workspace_bytes);
   BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, precision);
-  if (!ws.ok()) {
-    set_error("mi_bilinear_bwd_records: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  rc = ws_fits(ws, "mi_bilinear_bwd_records");
+  if (rc) return rc;
   if (!(fast_ok(b_rows, b, d_img, d_txt, precision, true) && p.fl.ok && p.tail)) {
     set_error("mi_bilinear_bwd_records: shape / precision outside the fused kernels (mi_bilinear_raw_records returns 0)");
     return MI_ESHAPE;
@@ -813,10 +807,8 @@ int mi_bilinear_bwd_dw(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, 
   if (rc) return rc;
   Workspace ws(workspace, workspace_bytes);
   BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, precision);
-  if (!ws.ok()) {
-    set_error("mi_bilinear_bwd_dw: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  rc = ws_fits(ws, "mi_bilinear_bwd_dw");
+  if (rc) return rc;
   if (!(fast_ok(b_rows, b, d_img, d_txt, precision, true) && p.fl.ok && p.tail)) {
     set_error("mi_bilinear_bwd_dw: shape / precision outside the fused kernels");
     return MI_ESHAPE;
@@ -835,10 +827,8 @@ int mi_bilinear_prep_local(const float* x, const float* w, int64_t b_rows, int64
   if (rc) return rc;
   Workspace ws(workspace, workspace_bytes);
   BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, precision);
-  if (!ws.ok()) {
-    set_error("mi_bilinear_prep_local: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  rc = ws_fits(ws, "mi_bilinear_prep_local");
+  if (rc) return rc;
   if (!(fast_ok(b_rows, b, d_img, d_txt, precision, true) && p.fl.ok)) {
     set_error("mi_bilinear_prep_local: shape / precision outside the fused kernels (call mi_bilinear_fwd alone)");
     return MI_ESHAPE;
@@ -864,10 +854,8 @@ int mi_bilinear_fp8_stage(const float* x, const float* y, const float* w, int64_
   }
   Workspace ws(workspace, workspace_bytes);
   BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, MI_PREC_FP8);
-  if (!ws.ok()) {
-    set_error("mi_bilinear_fp8_stage: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  rc = ws_fits(ws, "mi_bilinear_fp8_stage");
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   // non-negative floats and their bit patterns order alike: the absmax slots hold bit patterns, amax_io floats
   auto copy = [&](void* dst, const void* src, size_t n) {
@@ -907,10 +895,8 @@ int mi_bilinear_step(const float* x, const float* y, const float* w, const int64
   MI_CHECK_ARG(estimator == MI_DV || estimator == MI_INFONCE, "mi_bilinear_step: unknown estimator %d", estimator);
   Workspace ws(workspace, workspace_bytes);
   BilinearPlan p = plan_bilinear(ws, b, b, d_img, d_txt, precision);
-  if (!ws.ok()) {
-    set_error("mi_bilinear_step: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  rc = ws_fits(ws, "mi_bilinear_step");
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (fast_ok(b, b, d_img, d_txt, precision, w != nullptr) && p.fl.ok && p.tail) {
     rc = fast_prep_and_t(x, y, w, sid, sid, b, b, 0, d_img, d_txt, p, st);
@@ -944,10 +930,8 @@ int mi_bilinear_step_bf16(const void* x_bf16, const void* y_bf16, const float* w
   MI_CHECK_ARG(estimator == MI_DV || estimator == MI_INFONCE, "mi_bilinear_step_bf16: unknown estimator %d", estimator);
   Workspace ws(workspace, workspace_bytes);
   BilinearPlan p = plan_bilinear(ws, b, b, d_img, d_txt, MI_PREC_BF16);
-  if (!ws.ok()) {
-    set_error("mi_bilinear_step_bf16: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  rc = ws_fits(ws, "mi_bilinear_step_bf16");
+  if (rc) return rc;
   if (!(fast_ok(b, b, d_img, d_txt, MI_PREC_BF16, true) && p.fl.ok && p.tail) || (uintptr_t)x_bf16 % 16 != 0 ||
       (uintptr_t)y_bf16 % 16 != 0) {
     set_error("mi_bilinear_step_bf16: shape outside the fused kernels (mi_bilinear_path != MI_PATH_FUSED_TAIL) or "
@@ -1163,10 +1147,8 @@ int mi_separable_fwd(const float* x, const float* y, const float* wg, const floa
   MI_CHECK_ARG(estimator == MI_DV || estimator == MI_INFONCE, "mi_separable_fwd: unknown estimator %d", estimator);
   Workspace ws(workspace, workspace_bytes);
   SeparablePlan p = plan_separable(ws, b_rows, b, d_img, d_txt, d_proj, precision);
-  if (!ws.ok()) {
-    set_error("mi_separable_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  rc = ws_fits(ws, "mi_separable_fwd");
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (p.fast) {
     rc = separable_prep_project(x, y, wg, wh, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, d_proj, p, st);
@@ -1208,10 +1190,8 @@ int mi_separable_bwd(const float* x, const float* y, const float* wg, const floa
   if (rc) return rc;
   Workspace ws(workspace, workspace_bytes);
   SeparablePlan p = plan_separable(ws, b_rows, b, d_img, d_txt, d_proj, precision);
-  if (!ws.ok()) {
-    set_error("mi_separable_bwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  rc = ws_fits(ws, "mi_separable_bwd");
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int64_t br = b_rows, k = d_proj;
   if (p.fast) {
@@ -1317,10 +1297,8 @@ extern "C" int mi_separable_step(const float* x, const float* y, const float* wg
   MI_CHECK_ARG(estimator == MI_DV || estimator == MI_INFONCE, "mi_separable_step: unknown estimator %d", estimator);
   Workspace ws(workspace, workspace_bytes);
   SeparablePlan p = plan_separable(ws, b, b, d_img, d_txt, d_proj, precision);
-  if (!ws.ok()) {
-    set_error("mi_separable_step: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  rc = ws_fits(ws, "mi_separable_step");
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (p.fast && p.tail) {
     rc = separable_prep_project_fused(x, y, wg, wh, sid, sid, b, b, 0, d_img, d_txt, d_proj, p, st);
@@ -1370,29 +1348,209 @@ extern "C" int mi_debug_set_stamps(void* buf) {
 }
 #endif
 
-// ================================================================================================ per-sample InfoNCE
-// (mi_nce.h)  The G-materialising chain with per-row and per-column statistics instead of one
-// global scalar:
-//   16-bit chain (bf16 / bf16x3, b and widths multiples of 8):
-//     prep + T = X W -> score GEMM with the row / column record epilogue -> merge -> loss
+// ================================================================================================ the G-materialising chain
+// (mi_nce.h, mi_fdiv.h; DESIGN.md sections 8 and 9.)  The per-sample InfoNCE and the JSD / NWJ bounds on the bilinear
+// critic, one row block [br] x [b] at a time (the whole batch: br == b, row_offset == 0, sid_rows == sid_cols):
+//   16-bit chain (bf16 / bf16x3, batch sizes and widths multiples of 8):
+//     prep + T = X W -> score GEMM with the estimator's statistics epilogue
 //     [grads] G GEMM (recomputed scores -> G, G^T) -> dT = G Y | dY = G^T T -> dW = X^T dT | dX = dT W^T
 //   generic kernels (MI_PREC_F32, other shapes): the same sequence on mi_gemm.h, G in fp32 (bf16 in the bf16 mode)
-// The fused B x B kernel is not used: per-row normalisation needs r_i before any row's P tile can be weighted.
+// Between the two halves each entry point runs its estimator's finish: nce_finish (row / column statistics, loss),
+// nce_rank_part (a row block's part for the cross-rank merge) or launch_fdiv_finalize.  The fused B x B kernel is not
+// used: per-row normalisation needs r_i before any row's P tile can be weighted, and the fdiv bounds keep one record per
+// 64 x 64 score tile.  The separable critic runs the chain on its projections A = X Wg, C = Y Wh with W = I.
 namespace mi {
 
-static bool nce_fast_ok(int64_t br, int64_t b, int64_t dx, int64_t dy, int precision) {
+// Est: what an estimator puts into the chain -- the statistics epilogue of the score GEMM and the gradient epilogue of
+// the G GEMM (generic kernels' and 16-bit chain's forms), its mode check and its launch labels
+struct NceEst {
+  using StatsOut = NceStatsOut;
+  using GradIn = NceGradIn;
+  using Stats = EpiNceStats<false>;
+  using Stats16 = EpiNceStats<true>;
+  template <typename TG>
+  using Grad = EpiNceGrad<TG>;
+  using Grad16 = EpiNceGrad2;
+  static int check_mode(const char* fn, int mode) {
+    MI_CHECK_ARG(mode == MI_NCE_ROWWISE || mode == MI_NCE_SYMMETRIC, "%s: unknown mode %d", fn, mode);
+    return MI_OK;
+  }
+  static constexpr const char* kName = "the per-sample InfoNCE";
+  static constexpr const char* kT = "nce T = X W (generic)";
+  static constexpr const char* kScores = "nce score + row / column records (generic)";
+  static constexpr const char* kScores16 = "nce score + row / column records";
+  static constexpr const char* kG = "nce G (generic)";
+  static constexpr const char* kG16 = "nce G";
+  static constexpr const char* kA = "nce separable A = X Wg";
+  static constexpr const char* kC = "nce separable C = Y Wh";
+  static constexpr const char* kDX = "nce separable dX = dA Wg^T";
+  static constexpr const char* kDWg = "nce separable dWg = X^T dA";
+  static constexpr const char* kDY = "nce separable dY = dC Wh^T";
+  static constexpr const char* kDWh = "nce separable dWh = Y^T dC";
+};
+
+struct FdivEst {
+  using StatsOut = FdivStatsOut;
+  using GradIn = FdivGradIn;
+  using Stats = EpiFdivStats;
+  using Stats16 = EpiFdivStats;
+  template <typename TG>
+  using Grad = EpiFdivGrad<TG>;
+  using Grad16 = EpiFdivGrad2;
+  static int check_mode(const char* fn, int mode) { return fdiv_check_mode(fn, mode); }
+  static constexpr const char* kName = "the JSD / NWJ bounds on this critic";
+  static constexpr const char* kT = "fdiv T = X W (generic)";
+  static constexpr const char* kScores = "fdiv score + records (generic)";
+  static constexpr const char* kScores16 = "fdiv score + records";
+  static constexpr const char* kG = "fdiv G (generic)";
+  static constexpr const char* kG16 = "fdiv G";
+  static constexpr const char* kA = "fdiv separable A = X Wg";
+  static constexpr const char* kC = "fdiv separable C = Y Wh";
+  static constexpr const char* kDX = "fdiv separable dX = dA Wg^T";
+  static constexpr const char* kDWg = "fdiv separable dWg = X^T dA";
+  static constexpr const char* kDY = "fdiv separable dY = dC Wh^T";
+  static constexpr const char* kDWh = "fdiv separable dWh = Y^T dC";
+};
+
+static bool chain_16bit_ok(int64_t br, int64_t b, int64_t dx, int64_t dy, int precision) {
   return (precision == MI_PREC_BF16 || precision == MI_PREC_BF16X3) && br % 8 == 0 && b % 8 == 0 && dx % 8 == 0 &&
          dy % 8 == 0;
 }
-static bool nce_fast_ok(int64_t b, int64_t dx, int64_t dy, int precision) { return nce_fast_ok(b, b, dx, dy, precision); }
 
-static int nce_check(const char* fn, int64_t b, int64_t dx, int64_t dy, int mode, int precision) {
+// sizes, the estimator's mode, the precision, then the row block [row_offset, row_offset + br) of [0, b)
+template <typename Est>
+static int chain_check(const char* fn, int64_t br, int64_t b, int64_t row_offset, int64_t dx, int64_t dy, int mode,
+                       int precision) {
   MI_CHECK_ARG(b >= 1 && dx >= 1 && dy >= 1, "%s: sizes must be >= 1 (b %lld, widths %lld, %lld)", fn, (long long)b,
                (long long)dx, (long long)dy);
-  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || mode == MI_NCE_SYMMETRIC, "%s: unknown mode %d", fn, mode);
+  const int rc = Est::check_mode(fn, mode);
+  if (rc) return rc;
   MI_CHECK_ARG(precision == MI_PREC_F32 || precision == MI_PREC_BF16 || precision == MI_PREC_BF16X3,
-               "%s: precision %d is not available for the per-sample InfoNCE (f32, bf16, bf16x3)", fn, precision);
+               "%s: precision %d is not available for %s (f32, bf16, bf16x3)", fn, precision, Est::kName);
+  MI_CHECK_ARG(br >= 1 && br <= b, "%s: need 1 <= b_rows <= b (got %lld, %lld)", fn, (long long)br, (long long)b);
+  MI_CHECK_ARG(row_offset >= 0 && row_offset + br <= b, "%s: row block [%lld, %lld) outside [0, %lld)", fn,
+               (long long)row_offset, (long long)(row_offset + br), (long long)b);
   return MI_OK;
+}
+
+// The forward half: prep / T = X W (w == nullptr: S = X Y^T), then the score GEMM of the row block with Est's
+// statistics epilogue writing to `so`
+template <typename Est>
+static int chain_scores(const float* x, const float* y, const float* w, const int64_t* sid_rows, const int64_t* sid_cols,
+                        int64_t br, int64_t b, int64_t row_offset, int64_t dx, int64_t dy, int precision,
+                        const typename Est::StatsOut& so, const BilinearPlan& p, hipStream_t st) {
+  if (chain_16bit_ok(br, b, dx, dy, precision)) {
+    const int x3 = p.x3;
+    int rc;
+    if (w) {
+      rc = fast_prep_and_t(x, y, w, sid_rows, sid_cols, br, b, row_offset, dx, dy, p, st);  // p.fl.ok is false
+    } else {
+      // X takes the place of T (A operand of the scores, B operand of dY = G^T T)
+      const int ra = x3 == 3 ? 1 : 0, rb = x3 == 3 ? 2 : 0;
+      CvtJobs jobs{};
+      jobs.j[0] = CvtJob{x, br, dx, p.tb, p.ttb, 0, 0, nullptr, ra, rb};
+      jobs.j[1] = CvtJob{y, b, dy, p.yb, p.ytb, 0, 0, nullptr, rb, rb};
+      rc = launch_cvt_transpose3(jobs, st, "nce prep X Y");
+    }
+    if (rc) return rc;
+    return launch_gemm_bf16(one_problem(p.tb, x3 * dy, p.yb, x3 * dy, br, b, x3 * dy), 1, typename Est::Stats16{so}, st,
+                            Est::kScores16);
+  }
+  auto generic = [&](auto* op) {
+    using OpT = std::remove_pointer_t<decltype(op)>;
+    const float* t = x;
+    if (w) {
+      const int rc =
+          generic_gemm_store<OpT>(make_operand(x, dx, 1), make_operand(w, 1, dy), br, dy, dx, p.t, dy, p, st, Est::kT);
+      if (rc) return rc;
+      t = p.t;
+    }
+    return launch_gemm<OpT>(make_operand(t, dy, 1), make_operand(y, dy, 1), br, b, dy, typename Est::Stats{so}, st,
+                            Est::kScores);
+  };
+  return precision == MI_PREC_BF16 ? generic((bf16_t*)nullptr) : generic((float*)nullptr);
+}
+
+// The gradient half: the G GEMM of the row block with Est's gradient epilogue (recomputed scores; T is chain_scores' in
+// the same workspace), then dT = G Y | dY = G^T T and dW | dX.  w == nullptr: dT is grad_x and there is no grad_w.
+template <typename Est>
+static int chain_grads(const float* x, const float* y, const float* w, int64_t br, int64_t b, int64_t dx, int64_t dy,
+                       int precision, const typename Est::GradIn& gi, float* grad_x, float* grad_y, float* grad_w,
+                       const BilinearPlan& p, hipStream_t st) {
+  if (chain_16bit_ok(br, b, dx, dy, precision)) {
+    const int x3 = p.x3;
+    const int rc = launch_gemm_bf16(one_problem(p.tb, x3 * dy, p.yb, x3 * dy, br, b, x3 * dy), 1,
+                                    typename Est::Grad16{gi, p.gb, p.gtb, x3 == 3 ? 1 : 0}, st, Est::kG16);
+    if (rc) return rc;
+    return bilinear_bwd_from_g(br, b, dx, dy, grad_x, grad_y, grad_w, w != nullptr, p, st);
+  }
+  auto generic = [&](auto* op) {
+    using OpT = std::remove_pointer_t<decltype(op)>;  // G is stored in the operand type
+    const float* t = w ? p.t : x;
+    OpT* g = (OpT*)p.g;
+    const int rc = launch_gemm<OpT>(make_operand(t, dy, 1), make_operand(y, dy, 1), br, b, dy,
+                                    typename Est::template Grad<OpT>{gi, g}, st, Est::kG);
+    if (rc) return rc;
+    return generic_bwd_from_g<OpT, OpT>(x, y, w, t, g, br, b, dx, dy, grad_x, grad_y, grad_w, p, st);
+  };
+  return precision == MI_PREC_BF16 ? generic((bf16_t*)nullptr) : generic((float*)nullptr);
+}
+
+// The separable critic on the chain: A = X Wg [br][k], C = Y Wh [b][k] (a row block projects all b text rows) and
+// their gradients on the strided-operand kernels, bf16 operands in the bf16 mode (bf), exact fp32 products otherwise
+template <typename Est>
+static int separable_project(bool bf, const float* x, const float* y, const float* wg, const float* wh, int64_t br,
+                             int64_t b, int64_t dx, int64_t dy, int64_t k, float* a, float* c, hipStream_t st) {
+  auto run = [&](auto* op) {
+    using OpT = std::remove_pointer_t<decltype(op)>;
+    const int rc = launch_gemm<OpT>(make_operand(x, dx, 1), make_operand(wg, 1, k), br, k, dx,
+                                    EpiStore{a, k, nullptr, 1.0f, 0}, st, Est::kA);
+    if (rc) return rc;
+    return launch_gemm<OpT>(make_operand(y, dy, 1), make_operand(wh, 1, k), b, k, dy, EpiStore{c, k, nullptr, 1.0f, 0},
+                            st, Est::kC);
+  };
+  return bf ? run((bf16_t*)nullptr) : run((float*)nullptr);
+}
+
+// dA [br][k] -> dX = dA Wg^T and (the row block's part of) dWg = X^T dA; dC [b][k] -> (parts of) dY = dC Wh^T, dWh = Y^T dC
+template <typename Est>
+static int separable_project_back(bool bf, const float* x, const float* y, const float* wg, const float* wh, int64_t br,
+                                  int64_t b, int64_t dx, int64_t dy, int64_t k, const float* da, const float* dc,
+                                  float* grad_x, float* grad_y, float* grad_wg, float* grad_wh, hipStream_t st) {
+  auto run = [&](auto* op) {
+    using OpT = std::remove_pointer_t<decltype(op)>;
+    int rc = launch_gemm<OpT>(make_operand(da, k, 1), make_operand(wg, k, 1), br, dx, k,
+                              EpiStore{grad_x, dx, nullptr, 1.0f, 0}, st, Est::kDX);
+    if (rc) return rc;
+    rc = launch_gemm<OpT>(make_operand(x, 1, dx), make_operand(da, 1, k), dx, k, br, EpiStore{grad_wg, k, nullptr, 1.0f, 0},
+                          st, Est::kDWg);
+    if (rc) return rc;
+    rc = launch_gemm<OpT>(make_operand(dc, k, 1), make_operand(wh, k, 1), b, dy, k, EpiStore{grad_y, dy, nullptr, 1.0f, 0},
+                          st, Est::kDY);
+    if (rc) return rc;
+    return launch_gemm<OpT>(make_operand(y, 1, dy), make_operand(dc, 1, k), dy, k, b,
+                            EpiStore{grad_wh, k, nullptr, 1.0f, 0}, st, Est::kDWh);
+  };
+  return bf ? run((bf16_t*)nullptr) : run((float*)nullptr);
+}
+
+// The separable entry points' workspace: A, C, dA, dC, then the plan of the chain on (A, C)
+template <typename Inner>
+struct SeparableChainPlan {
+  float *a, *c, *da, *dc;
+  Inner n;
+  size_t bytes;
+};
+template <typename PlanInner>
+static auto plan_separable_chain(Workspace& ws, int64_t br, int64_t b, int64_t k, PlanInner plan_inner) {
+  SeparableChainPlan<decltype(plan_inner())> s{};
+  s.a = ws.take<float>(br * k);
+  s.c = ws.take<float>(b * k);
+  s.da = ws.take<float>(br * k);
+  s.dc = ws.take<float>(b * k);
+  s.n = plan_inner();
+  s.bytes = ws.off;
+  return s;
 }
 
 struct NceBilinearPlan {
@@ -1407,97 +1565,10 @@ static NceBilinearPlan plan_nce_bilinear(Workspace& ws, int64_t b, int64_t dx, i
   n.bytes = ws.off;
   return n;
 }
-
-// generic kernels: forward (T, scores -> records -> r, c, loss) and, when grad_y != nullptr, the backward
-template <typename OpT, typename TG>
-static int nce_step_generic(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t dx,
-                            int64_t dy, int mode, const float* grad_out, float* loss_out, float* lse_rows,
-                            float* lse_cols, float* grad_x, float* grad_y, float* grad_w, const NceBilinearPlan& n,
-                            hipStream_t st) {
-  const BilinearPlan& p = n.p;
-  int rc = MI_OK;
-  const float* t = x;  // w == nullptr: S = X Y^T
-  if (w) {
-    rc = generic_gemm_store<OpT>(make_operand(x, dx, 1), make_operand(w, 1, dy), b, dy, dx, p.t, dy, p, st,
-                                 "nce T = X W (generic)");
-    if (rc) return rc;
-    t = p.t;
-  }
-  rc = launch_gemm<OpT>(make_operand(t, dy, 1), make_operand(y, dy, 1), b, b, dy, EpiNceStats<false>{nce_stats_out(n.q, sid)},
-                        st, "nce score + row / column records (generic)");
-  if (rc) return rc;
-  rc = nce_finish(n.q, b, mode, loss_out, lse_rows, lse_cols, st);
-  if (rc || !grad_y) return rc;
-  TG* g = (TG*)p.g;
-  rc = launch_gemm<OpT>(make_operand(t, dy, 1), make_operand(y, dy, 1), b, b, dy,
-                        EpiNceGrad<TG>{nce_grad_in(sid, n.q.r, n.q.c, grad_out, b, mode), g}, st, "nce G (generic)");
-  if (rc) return rc;
-  return generic_bwd_from_g<OpT, TG>(x, y, w, t, g, b, b, dx, dy, grad_x, grad_y, grad_w, p, st);
+static SeparableChainPlan<NceBilinearPlan> plan_nce_separable(Workspace& ws, int64_t b, int64_t k, int precision) {
+  return plan_separable_chain(ws, b, b, k, [&] { return plan_nce_bilinear(ws, b, k, k, precision); });
 }
 
-// 16-bit chain: bf16 operand copies and T = X W of the row block [br] against all b columns
-static int nce_prep_fast(const float* x, const float* y, const float* w, const int64_t* sid_rows, const int64_t* sid_cols,
-                         int64_t br, int64_t b, int64_t row_offset, int64_t dx, int64_t dy, const BilinearPlan& p,
-                         hipStream_t st) {
-  if (w) return fast_prep_and_t(x, y, w, sid_rows, sid_cols, br, b, row_offset, dx, dy, p, st);  // p.fl.ok is false
-  // S = X Y^T: X takes the place of T (A operand of the scores, B operand of dY = G^T T)
-  const int ra = p.x3 == 3 ? 1 : 0, rb = p.x3 == 3 ? 2 : 0;
-  CvtJobs jobs{};
-  jobs.j[0] = CvtJob{x, br, dx, p.tb, p.ttb, 0, 0, nullptr, ra, rb};
-  jobs.j[1] = CvtJob{y, b, dy, p.yb, p.ytb, 0, 0, nullptr, rb, rb};
-  return launch_cvt_transpose3(jobs, st, "nce prep X Y");
-}
-
-static int nce_step_fast(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t dx,
-                         int64_t dy, int mode, const float* grad_out, float* loss_out, float* lse_rows, float* lse_cols,
-                         float* grad_x, float* grad_y, float* grad_w, const NceBilinearPlan& n, hipStream_t st) {
-  const BilinearPlan& p = n.p;
-  const int x3 = p.x3;
-  int rc = nce_prep_fast(x, y, w, sid, sid, b, b, 0, dx, dy, p, st);
-  if (rc) return rc;
-  const GemmBf16Args scores = one_problem(p.tb, x3 * dy, p.yb, x3 * dy, b, b, x3 * dy);
-  rc = launch_gemm_bf16(scores, 1, EpiNceStats<true>{nce_stats_out(n.q, sid)}, st, "nce score + row / column records");
-  if (rc) return rc;
-  rc = nce_finish(n.q, b, mode, loss_out, lse_rows, lse_cols, st);
-  if (rc || !grad_y) return rc;
-  rc = launch_gemm_bf16(scores, 1,
-                        EpiNceGrad2{nce_grad_in(sid, n.q.r, n.q.c, grad_out, b, mode), p.gb, p.gtb, x3 == 3 ? 1 : 0}, st,
-                        "nce G");
-  if (rc) return rc;
-  return bilinear_bwd_from_g(b, b, dx, dy, grad_x, grad_y, grad_w, w != nullptr, p, st);
-}
-
-static int nce_step_any(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t dx,
-                        int64_t dy, int mode, int precision, const float* grad_out, float* loss_out, float* lse_rows,
-                        float* lse_cols, float* grad_x, float* grad_y, float* grad_w, const NceBilinearPlan& n,
-                        hipStream_t st) {
-  if (nce_fast_ok(b, dx, dy, precision))
-    return nce_step_fast(x, y, w, sid, b, dx, dy, mode, grad_out, loss_out, lse_rows, lse_cols, grad_x, grad_y, grad_w, n,
-                         st);
-  if (precision == MI_PREC_BF16)
-    return nce_step_generic<bf16_t, bf16_t>(x, y, w, sid, b, dx, dy, mode, grad_out, loss_out, lse_rows, lse_cols, grad_x,
-                                            grad_y, grad_w, n, st);
-  return nce_step_generic<float, float>(x, y, w, sid, b, dx, dy, mode, grad_out, loss_out, lse_rows, lse_cols, grad_x,
-                                        grad_y, grad_w, n, st);
-}
-
-struct NceSeparablePlan {
-  float *a, *c, *da, *dc;
-  NceBilinearPlan n;
-  size_t bytes;
-};
-static NceSeparablePlan plan_nce_separable(Workspace& ws, int64_t b, int64_t k, int precision) {
-  NceSeparablePlan s{};
-  s.a = ws.take<float>(b * k);
-  s.c = ws.take<float>(b * k);
-  s.da = ws.take<float>(b * k);
-  s.dc = ws.take<float>(b * k);
-  s.n = plan_nce_bilinear(ws, b, k, k, precision);
-  s.bytes = ws.off;
-  return s;
-}
-
-// ------------------------------------------------------------------------------------------------ row blocks (sharded)
 // A rank's row block [br] x [b]: the forward leaves T / the operand copies, the records and r in
 // its workspace and writes the rank's part; the caller gathers the parts, mi_nce_merge_parts gives c and the loss; the
 // backward reads r and the operands from the same workspace and the merged c from the caller.  br == b, row_offset == 0
@@ -1515,112 +1586,36 @@ static NceShardBilinearPlan plan_nce_shard_bilinear(Workspace& ws, int64_t br, i
   n.bytes = ws.off;
   return n;
 }
-
-template <typename OpT>
-static int nce_shard_scores_generic(const float* x, const float* y, const float* w, int64_t br, int64_t b, int64_t dx,
-                                    int64_t dy, const NceStatsOut& so, const BilinearPlan& p, hipStream_t st) {
-  const float* t = x;
-  if (w) {
-    const int rc = generic_gemm_store<OpT>(make_operand(x, dx, 1), make_operand(w, 1, dy), br, dy, dx, p.t, dy, p, st,
-                                           "nce T = X W (generic)");
-    if (rc) return rc;
-    t = p.t;
-  }
-  return launch_gemm<OpT>(make_operand(t, dy, 1), make_operand(y, dy, 1), br, b, dy, EpiNceStats<false>{so}, st,
-                          "nce score + row / column records (generic)");
+static SeparableChainPlan<NceShardBilinearPlan> plan_nce_shard_separable(Workspace& ws, int64_t br, int64_t b, int64_t k,
+                                                                         int precision) {
+  return plan_separable_chain(ws, br, b, k, [&] { return plan_nce_shard_bilinear(ws, br, b, k, k, precision); });
 }
 
-static int nce_shard_fwd_any(const float* x, const float* y, const float* w, const int64_t* sid_rows,
-                             const int64_t* sid_cols, int64_t br, int64_t b, int64_t row_offset, int64_t dx, int64_t dy,
-                             int precision, float* part_out, float* lse_rows, const NceShardBilinearPlan& n,
-                             hipStream_t st) {
-  const BilinearPlan& p = n.p;
-  const NceStatsOut so = nce_stats_out(n.q, sid_rows, sid_cols, row_offset);
-  int rc = MI_OK;
-  if (nce_fast_ok(br, b, dx, dy, precision)) {
-    rc = nce_prep_fast(x, y, w, sid_rows, sid_cols, br, b, row_offset, dx, dy, p, st);
-    if (rc) return rc;
-    const int x3 = p.x3;
-    rc = launch_gemm_bf16(one_problem(p.tb, x3 * dy, p.yb, x3 * dy, br, b, x3 * dy), 1, EpiNceStats<true>{so}, st,
-                          "nce score + row / column records");
-  } else if (precision == MI_PREC_BF16) {
-    rc = nce_shard_scores_generic<bf16_t>(x, y, w, br, b, dx, dy, so, p, st);
-  } else {
-    rc = nce_shard_scores_generic<float>(x, y, w, br, b, dx, dy, so, p, st);
-  }
-  if (rc) return rc;
-  return nce_rank_part(n.q, br, b, part_out, lse_rows, st);
-}
-
-template <typename OpT, typename TG>
-static int nce_shard_bwd_generic(const float* x, const float* y, const float* w, int64_t br, int64_t b, int64_t dx,
-                                 int64_t dy, const NceGradIn& gi, float* grad_x, float* grad_y, float* grad_w,
-                                 const BilinearPlan& p, hipStream_t st) {
-  const float* t = w ? p.t : x;  // T = X W is the forward's (same workspace)
-  TG* g = (TG*)p.g;
-  const int rc = launch_gemm<OpT>(make_operand(t, dy, 1), make_operand(y, dy, 1), br, b, dy, EpiNceGrad<TG>{gi, g}, st,
-                                  "nce G (generic)");
-  if (rc) return rc;
-  return generic_bwd_from_g<OpT, TG>(x, y, w, t, g, br, b, dx, dy, grad_x, grad_y, grad_w, p, st);
-}
-
-static int nce_shard_bwd_any(const float* x, const float* y, const float* w, const int64_t* sid_rows,
-                             const int64_t* sid_cols, int64_t br, int64_t b, int64_t row_offset, int64_t dx, int64_t dy,
-                             int mode, int precision, const float* lse_cols, const float* grad_out, float* grad_x,
-                             float* grad_y, float* grad_w, const NceShardBilinearPlan& n, hipStream_t st) {
-  const BilinearPlan& p = n.p;
-  const NceGradIn gi = nce_grad_in(sid_rows, sid_cols, row_offset, n.q.r, lse_cols, grad_out, b, mode);
-  if (nce_fast_ok(br, b, dx, dy, precision)) {
-    const int x3 = p.x3;
-    const int rc = launch_gemm_bf16(one_problem(p.tb, x3 * dy, p.yb, x3 * dy, br, b, x3 * dy), 1,
-                                    EpiNceGrad2{gi, p.gb, p.gtb, x3 == 3 ? 1 : 0}, st, "nce G");
-    if (rc) return rc;
-    return bilinear_bwd_from_g(br, b, dx, dy, grad_x, grad_y, grad_w, w != nullptr, p, st);
-  }
-  if (precision == MI_PREC_BF16)
-    return nce_shard_bwd_generic<bf16_t, bf16_t>(x, y, w, br, b, dx, dy, gi, grad_x, grad_y, grad_w, p, st);
-  return nce_shard_bwd_generic<float, float>(x, y, w, br, b, dx, dy, gi, grad_x, grad_y, grad_w, p, st);
-}
-
-// separable critic: A = X Wg [br][k], C = Y Wh [b][k] (every rank projects all b text rows), the row block on (A, C)
-struct NceShardSeparablePlan {
-  float *a, *c, *da, *dc;
-  NceShardBilinearPlan n;
+struct FdivBilinearPlan {
+  BilinearPlan p;
+  FdivRec* rec;  // [n_t][n_t]
+  mi_stats* stats;
+  int64_t n_t;
   size_t bytes;
 };
-static NceShardSeparablePlan plan_nce_shard_separable(Workspace& ws, int64_t br, int64_t b, int64_t k, int precision) {
-  NceShardSeparablePlan s{};
-  s.a = ws.take<float>(br * k);
-  s.c = ws.take<float>(b * k);
-  s.da = ws.take<float>(br * k);
-  s.dc = ws.take<float>(b * k);
-  s.n = plan_nce_shard_bilinear(ws, br, b, k, k, precision);
-  s.bytes = ws.off;
-  return s;
+static FdivBilinearPlan plan_fdiv_bilinear(Workspace& ws, int64_t b, int64_t dx, int64_t dy, int precision) {
+  FdivBilinearPlan n{};
+  n.p = plan_bilinear(ws, b, b, dx, dy, precision, true);
+  n.n_t = (b + 63) / 64;
+  n.rec = ws.take<FdivRec>(n.n_t * n.n_t);
+  n.stats = ws.take<mi_stats>(1);
+  n.bytes = ws.off;
+  return n;
 }
-
-// out [M][N] = A B^T on the strided-operand kernels: bf16 operands in the bf16 mode, exact fp32 products otherwise (the
-// projections of mi_nce_separable_step)
-static int nce_proj_gemm(bool bf, const Operand<float>& A, const Operand<float>& B, int64_t M, int64_t N, int64_t K,
-                         float* out, int64_t ld, hipStream_t st, const char* what) {
-  return bf ? launch_gemm<bf16_t>(A, B, M, N, K, EpiStore{out, ld, nullptr, 1.0f, 0}, st, what)
-            : launch_gemm<float>(A, B, M, N, K, EpiStore{out, ld, nullptr, 1.0f, 0}, st, what);
-}
-
-static int nce_shard_check(const char* fn, int64_t br, int64_t b, int64_t row_offset, int64_t dx, int64_t dy, int mode,
-                           int precision) {
-  const int rc = nce_check(fn, b, dx, dy, mode, precision);
-  if (rc) return rc;
-  MI_CHECK_ARG(br >= 1 && br <= b, "%s: need 1 <= b_rows <= b (got %lld, %lld)", fn, (long long)br, (long long)b);
-  MI_CHECK_ARG(row_offset >= 0 && row_offset + br <= b, "%s: row block [%lld, %lld) outside [0, %lld)", fn,
-               (long long)row_offset, (long long)(row_offset + br), (long long)b);
-  return MI_OK;
+static SeparableChainPlan<FdivBilinearPlan> plan_fdiv_separable(Workspace& ws, int64_t b, int64_t k, int precision) {
+  return plan_separable_chain(ws, b, b, k, [&] { return plan_fdiv_bilinear(ws, b, k, k, precision); });
 }
 
 }  // namespace mi
 
 extern "C" {
 
+// ------------------------------------------------------------------------------------------------ per-sample InfoNCE
 size_t mi_nce_bilinear_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int precision) {
   if (b <= 0 || d_img <= 0 || d_txt <= 0) return 0;
   Workspace ws(nullptr, 0);
@@ -1632,20 +1627,23 @@ int mi_nce_bilinear_step(const float* x, const float* y, const float* w, const i
                          float* lse_cols, float* grad_x, float* grad_y, float* grad_w, void* workspace,
                          size_t workspace_bytes, void* stream) {
   MI_CHECK_ARG(x && y && sid && loss_out && workspace, "mi_nce_bilinear_step: null pointer");
-  int rc = nce_check("mi_nce_bilinear_step", b, d_img, d_txt, mode, precision);
+  int rc = chain_check<NceEst>("mi_nce_bilinear_step", b, b, 0, d_img, d_txt, mode, precision);
   if (rc) return rc;
   MI_CHECK_ARG(w || d_img == d_txt, "mi_nce_bilinear_step: w == NULL (S = X Y^T) needs d_img == d_txt");
   const bool any_grad = grad_x || grad_y || grad_w;
   MI_CHECK_ARG(!any_grad || (grad_x && grad_y && (w ? grad_w != nullptr : grad_w == nullptr)),
                "mi_nce_bilinear_step: pass grad_x, grad_y and (with w) grad_w, or none of them");
   Workspace ws(workspace, workspace_bytes);
-  NceBilinearPlan n = plan_nce_bilinear(ws, b, d_img, d_txt, precision);
-  if (!ws.ok()) {
-    set_error("mi_nce_bilinear_step: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
-  return nce_step_any(x, y, w, sid, b, d_img, d_txt, mode, precision, grad_out, loss_out, lse_rows, lse_cols, grad_x,
-                      grad_y, grad_w, n, (hipStream_t)stream);
+  const NceBilinearPlan n = plan_nce_bilinear(ws, b, d_img, d_txt, precision);
+  rc = ws_fits(ws, "mi_nce_bilinear_step");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  rc = chain_scores<NceEst>(x, y, w, sid, sid, b, b, 0, d_img, d_txt, precision, nce_stats_out(n.q, sid), n.p, st);
+  if (rc) return rc;
+  rc = nce_finish(n.q, b, mode, loss_out, lse_rows, lse_cols, st);
+  if (rc || !any_grad) return rc;
+  return chain_grads<NceEst>(x, y, w, b, b, d_img, d_txt, precision, nce_grad_in(sid, n.q.r, n.q.c, grad_out, b, mode),
+                             grad_x, grad_y, grad_w, n.p, st);
 }
 
 size_t mi_nce_separable_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int precision) {
@@ -1659,44 +1657,31 @@ int mi_nce_separable_step(const float* x, const float* y, const float* wg, const
                           float* loss_out, float* lse_rows, float* lse_cols, float* grad_x, float* grad_y,
                           float* grad_wg, float* grad_wh, void* workspace, size_t workspace_bytes, void* stream) {
   MI_CHECK_ARG(x && y && wg && wh && sid && loss_out && workspace, "mi_nce_separable_step: null pointer");
-  int rc = nce_check("mi_nce_separable_step", b, d_img, d_txt, mode, precision);
+  int rc = chain_check<NceEst>("mi_nce_separable_step", b, b, 0, d_img, d_txt, mode, precision);
   if (rc) return rc;
   MI_CHECK_ARG(d_proj >= 1, "mi_nce_separable_step: projection width must be >= 1");
   const bool any_grad = grad_x || grad_y || grad_wg || grad_wh;
   MI_CHECK_ARG(!any_grad || (grad_x && grad_y && grad_wg && grad_wh),
                "mi_nce_separable_step: pass all four gradients or none of them");
   Workspace ws(workspace, workspace_bytes);
-  NceSeparablePlan sp = plan_nce_separable(ws, b, d_proj, precision);
-  if (!ws.ok()) {
-    set_error("mi_nce_separable_step: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  const auto sp = plan_nce_separable(ws, b, d_proj, precision);
+  rc = ws_fits(ws, "mi_nce_separable_step");
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int64_t k = d_proj;
-  // projections and their backward on the strided-operand kernels, as the separable critic's generic path (bf16 operands
-  // in the bf16 mode, exact fp32 products otherwise); the scores and their gradients on the bilinear chain with W = I
+  const NceBilinearPlan& n = sp.n;
   const bool bf = precision == MI_PREC_BF16;
-#define MI_NCE_GEMM(A, B, M, N, K, OUT, LD, WHAT)                                                              \
-  do {                                                                                                          \
-    rc = bf ? launch_gemm<bf16_t>(A, B, M, N, K, EpiStore{OUT, LD, nullptr, 1.0f, 0}, st, WHAT)                \
-            : launch_gemm<float>(A, B, M, N, K, EpiStore{OUT, LD, nullptr, 1.0f, 0}, st, WHAT);                \
-    if (rc) return rc;                                                                                          \
-  } while (0)
-  MI_NCE_GEMM(make_operand(x, d_img, 1), make_operand(wg, 1, k), b, k, d_img, sp.a, k, "nce separable A = X Wg");
-  MI_NCE_GEMM(make_operand(y, d_txt, 1), make_operand(wh, 1, k), b, k, d_txt, sp.c, k, "nce separable C = Y Wh");
-  rc = nce_step_any(sp.a, sp.c, nullptr, sid, b, k, k, mode, precision, grad_out, loss_out, lse_rows, lse_cols,
-                    any_grad ? sp.da : nullptr, any_grad ? sp.dc : nullptr, nullptr, sp.n, st);
+  rc = separable_project<NceEst>(bf, x, y, wg, wh, b, b, d_img, d_txt, k, sp.a, sp.c, st);
+  if (rc) return rc;
+  rc = chain_scores<NceEst>(sp.a, sp.c, nullptr, sid, sid, b, b, 0, k, k, precision, nce_stats_out(n.q, sid), n.p, st);
+  if (rc) return rc;
+  rc = nce_finish(n.q, b, mode, loss_out, lse_rows, lse_cols, st);
   if (rc || !any_grad) return rc;
-  MI_NCE_GEMM(make_operand((const float*)sp.da, k, 1), make_operand(wg, k, 1), b, d_img, k, grad_x, d_img,
-              "nce separable dX = dA Wg^T");
-  MI_NCE_GEMM(make_operand(x, 1, d_img), make_operand((const float*)sp.da, 1, k), d_img, k, b, grad_wg, k,
-              "nce separable dWg = X^T dA");
-  MI_NCE_GEMM(make_operand((const float*)sp.dc, k, 1), make_operand(wh, k, 1), b, d_txt, k, grad_y, d_txt,
-              "nce separable dY = dC Wh^T");
-  MI_NCE_GEMM(make_operand(y, 1, d_txt), make_operand((const float*)sp.dc, 1, k), d_txt, k, b, grad_wh, k,
-              "nce separable dWh = Y^T dC");
-#undef MI_NCE_GEMM
-  return MI_OK;
+  rc = chain_grads<NceEst>(sp.a, sp.c, nullptr, b, b, k, k, precision, nce_grad_in(sid, n.q.r, n.q.c, grad_out, b, mode),
+                           sp.da, sp.dc, nullptr, n.p, st);
+  if (rc) return rc;
+  return separable_project_back<NceEst>(bf, x, y, wg, wh, b, b, d_img, d_txt, k, sp.da, sp.dc, grad_x, grad_y, grad_wg,
+                                        grad_wh, st);
 }
 
 /* Row blocks of a sharded batch (include/mi_critic.h): forward -> part, merge of the gathered parts -> loss and c,
@@ -1717,17 +1702,18 @@ int mi_nce_bilinear_shard_fwd(const float* x, const float* y, const float* w, co
                               int64_t d_txt, int mode, int precision, float* part_out, float* lse_rows, void* workspace,
                               size_t workspace_bytes, void* stream) {
   MI_CHECK_ARG(x && y && sid_rows && sid_cols && part_out && workspace, "mi_nce_bilinear_shard_fwd: null pointer");
-  int rc = nce_shard_check("mi_nce_bilinear_shard_fwd", b_rows, b, row_offset, d_img, d_txt, mode, precision);
+  int rc = chain_check<NceEst>("mi_nce_bilinear_shard_fwd", b_rows, b, row_offset, d_img, d_txt, mode, precision);
   if (rc) return rc;
   MI_CHECK_ARG(w || d_img == d_txt, "mi_nce_bilinear_shard_fwd: w == NULL (S = X Y^T) needs d_img == d_txt");
   Workspace ws(workspace, workspace_bytes);
-  NceShardBilinearPlan n = plan_nce_shard_bilinear(ws, b_rows, b, d_img, d_txt, precision);
-  if (!ws.ok()) {
-    set_error("mi_nce_bilinear_shard_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
-  return nce_shard_fwd_any(x, y, w, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, precision, part_out,
-                           lse_rows, n, (hipStream_t)stream);
+  const NceShardBilinearPlan n = plan_nce_shard_bilinear(ws, b_rows, b, d_img, d_txt, precision);
+  rc = ws_fits(ws, "mi_nce_bilinear_shard_fwd");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  rc = chain_scores<NceEst>(x, y, w, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, precision,
+                            nce_stats_out(n.q, sid_rows, sid_cols, row_offset), n.p, st);
+  if (rc) return rc;
+  return nce_rank_part(n.q, b_rows, b, part_out, lse_rows, st);
 }
 
 int mi_nce_bilinear_shard_bwd(const float* x, const float* y, const float* w, const int64_t* sid_rows,
@@ -1736,19 +1722,18 @@ int mi_nce_bilinear_shard_bwd(const float* x, const float* y, const float* w, co
                               float* grad_x, float* grad_y, float* grad_w, void* workspace, size_t workspace_bytes,
                               void* stream) {
   MI_CHECK_ARG(x && y && sid_rows && sid_cols && grad_x && grad_y && workspace, "mi_nce_bilinear_shard_bwd: null pointer");
-  int rc = nce_shard_check("mi_nce_bilinear_shard_bwd", b_rows, b, row_offset, d_img, d_txt, mode, precision);
+  int rc = chain_check<NceEst>("mi_nce_bilinear_shard_bwd", b_rows, b, row_offset, d_img, d_txt, mode, precision);
   if (rc) return rc;
   MI_CHECK_ARG(mode == MI_NCE_ROWWISE || lse_cols, "mi_nce_bilinear_shard_bwd: the symmetric mode needs lse_cols");
   MI_CHECK_ARG((w && grad_w) || (!w && !grad_w && d_img == d_txt),
                "mi_nce_bilinear_shard_bwd: w != NULL needs grad_w; w == NULL (S = X Y^T) needs d_img == d_txt, no grad_w");
   Workspace ws(workspace, workspace_bytes);
-  NceShardBilinearPlan n = plan_nce_shard_bilinear(ws, b_rows, b, d_img, d_txt, precision);
-  if (!ws.ok()) {
-    set_error("mi_nce_bilinear_shard_bwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
-  return nce_shard_bwd_any(x, y, w, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, mode, precision, lse_cols,
-                           grad_out, grad_x, grad_y, grad_w, n, (hipStream_t)stream);
+  const NceShardBilinearPlan n = plan_nce_shard_bilinear(ws, b_rows, b, d_img, d_txt, precision);
+  rc = ws_fits(ws, "mi_nce_bilinear_shard_bwd");
+  if (rc) return rc;
+  return chain_grads<NceEst>(x, y, w, b_rows, b, d_img, d_txt, precision,
+                             nce_grad_in(sid_rows, sid_cols, row_offset, n.q.r, lse_cols, grad_out, b, mode), grad_x,
+                             grad_y, grad_w, n.p, (hipStream_t)stream);
 }
 
 size_t mi_nce_merge_workspace_bytes(int64_t b) {
@@ -1765,10 +1750,8 @@ int mi_nce_merge_parts(const float* parts, int64_t n_ranks, int64_t b_rows, int6
   MI_CHECK_ARG(mode == MI_NCE_ROWWISE || mode == MI_NCE_SYMMETRIC, "mi_nce_merge_parts: unknown mode %d", mode);
   Workspace ws(workspace, workspace_bytes);
   float* terms = ws.take<float>(2 * b);
-  if (!ws.ok()) {
-    set_error("mi_nce_merge_parts: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  const int rc = ws_fits(ws, "mi_nce_merge_parts");
+  if (rc) return rc;
   return nce_merge_parts(parts, n_ranks, b_rows, b, mode, loss_out, lse_cols, terms, (hipStream_t)stream);
 }
 
@@ -1785,26 +1768,21 @@ int mi_nce_separable_shard_fwd(const float* x, const float* y, const float* wg, 
                                void* workspace, size_t workspace_bytes, void* stream) {
   MI_CHECK_ARG(x && y && wg && wh && sid_rows && sid_cols && part_out && workspace,
                "mi_nce_separable_shard_fwd: null pointer");
-  int rc = nce_shard_check("mi_nce_separable_shard_fwd", b_rows, b, row_offset, d_img, d_txt, mode, precision);
+  int rc = chain_check<NceEst>("mi_nce_separable_shard_fwd", b_rows, b, row_offset, d_img, d_txt, mode, precision);
   if (rc) return rc;
   MI_CHECK_ARG(d_proj >= 1, "mi_nce_separable_shard_fwd: projection width must be >= 1");
   Workspace ws(workspace, workspace_bytes);
-  NceShardSeparablePlan sp = plan_nce_shard_separable(ws, b_rows, b, d_proj, precision);
-  if (!ws.ok()) {
-    set_error("mi_nce_separable_shard_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  const auto sp = plan_nce_shard_separable(ws, b_rows, b, d_proj, precision);
+  rc = ws_fits(ws, "mi_nce_separable_shard_fwd");
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int64_t k = d_proj;
-  const bool bf = precision == MI_PREC_BF16;
-  rc = nce_proj_gemm(bf, make_operand(x, d_img, 1), make_operand(wg, 1, k), b_rows, k, d_img, sp.a, k, st,
-                     "nce separable A = X Wg");
+  rc = separable_project<NceEst>(precision == MI_PREC_BF16, x, y, wg, wh, b_rows, b, d_img, d_txt, k, sp.a, sp.c, st);
   if (rc) return rc;
-  rc = nce_proj_gemm(bf, make_operand(y, d_txt, 1), make_operand(wh, 1, k), b, k, d_txt, sp.c, k, st,
-                     "nce separable C = Y Wh");
+  rc = chain_scores<NceEst>(sp.a, sp.c, nullptr, sid_rows, sid_cols, b_rows, b, row_offset, k, k, precision,
+                            nce_stats_out(sp.n.q, sid_rows, sid_cols, row_offset), sp.n.p, st);
   if (rc) return rc;
-  return nce_shard_fwd_any(sp.a, sp.c, nullptr, sid_rows, sid_cols, b_rows, b, row_offset, k, k, precision, part_out,
-                           lse_rows, sp.n, st);
+  return nce_rank_part(sp.n.q, b_rows, b, part_out, lse_rows, st);
 }
 
 int mi_nce_separable_shard_bwd(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid_rows,
@@ -1814,34 +1792,23 @@ int mi_nce_separable_shard_bwd(const float* x, const float* y, const float* wg, 
                                void* workspace, size_t workspace_bytes, void* stream) {
   MI_CHECK_ARG(x && y && wg && wh && sid_rows && sid_cols && grad_x && grad_y && grad_wg && grad_wh && workspace,
                "mi_nce_separable_shard_bwd: null pointer");
-  int rc = nce_shard_check("mi_nce_separable_shard_bwd", b_rows, b, row_offset, d_img, d_txt, mode, precision);
+  int rc = chain_check<NceEst>("mi_nce_separable_shard_bwd", b_rows, b, row_offset, d_img, d_txt, mode, precision);
   if (rc) return rc;
   MI_CHECK_ARG(d_proj >= 1, "mi_nce_separable_shard_bwd: projection width must be >= 1");
   MI_CHECK_ARG(mode == MI_NCE_ROWWISE || lse_cols, "mi_nce_separable_shard_bwd: the symmetric mode needs lse_cols");
   Workspace ws(workspace, workspace_bytes);
-  NceShardSeparablePlan sp = plan_nce_shard_separable(ws, b_rows, b, d_proj, precision);
-  if (!ws.ok()) {
-    set_error("mi_nce_separable_shard_bwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  const auto sp = plan_nce_shard_separable(ws, b_rows, b, d_proj, precision);
+  rc = ws_fits(ws, "mi_nce_separable_shard_bwd");
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int64_t k = d_proj;
-  const bool bf = precision == MI_PREC_BF16;
-  rc = nce_shard_bwd_any(sp.a, sp.c, nullptr, sid_rows, sid_cols, b_rows, b, row_offset, k, k, mode, precision, lse_cols,
-                         grad_out, sp.da, sp.dc, nullptr, sp.n, st);
+  rc = chain_grads<NceEst>(sp.a, sp.c, nullptr, b_rows, b, k, k, precision,
+                           nce_grad_in(sid_rows, sid_cols, row_offset, sp.n.q.r, lse_cols, grad_out, b, mode), sp.da,
+                           sp.dc, nullptr, sp.n.p, st);
   if (rc) return rc;
   // dA -> the rank's dX and its partial dWg; the rank's partial dC (all b text rows) -> partial dY and dWh
-  rc = nce_proj_gemm(bf, make_operand((const float*)sp.da, k, 1), make_operand(wg, k, 1), b_rows, d_img, k, grad_x, d_img,
-                     st, "nce separable dX = dA Wg^T");
-  if (rc) return rc;
-  rc = nce_proj_gemm(bf, make_operand(x, 1, d_img), make_operand((const float*)sp.da, 1, k), d_img, k, b_rows, grad_wg, k,
-                     st, "nce separable dWg = X^T dA");
-  if (rc) return rc;
-  rc = nce_proj_gemm(bf, make_operand((const float*)sp.dc, k, 1), make_operand(wh, k, 1), b, d_txt, k, grad_y, d_txt, st,
-                     "nce separable dY = dC Wh^T");
-  if (rc) return rc;
-  return nce_proj_gemm(bf, make_operand(y, 1, d_txt), make_operand((const float*)sp.dc, 1, k), d_txt, k, b, grad_wh, k,
-                       st, "nce separable dWh = Y^T dC");
+  return separable_project_back<NceEst>(precision == MI_PREC_BF16, x, y, wg, wh, b_rows, b, d_img, d_txt, k, sp.da, sp.dc,
+                                        grad_x, grad_y, grad_wg, grad_wh, st);
 }
 
 size_t mi_matrix_nce_workspace_bytes(int64_t b) {
@@ -1858,10 +1825,8 @@ int mi_matrix_nce_fwd(const float* scores, const int64_t* sid, int64_t b, int mo
   MI_CHECK_ARG(mode == MI_NCE_ROWWISE || mode == MI_NCE_SYMMETRIC, "mi_matrix_nce_fwd: unknown mode %d", mode);
   Workspace ws(workspace, workspace_bytes);
   const NcePlan q = plan_nce(ws, b);
-  if (!ws.ok()) {
-    set_error("mi_matrix_nce_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  const int rc = ws_fits(ws, "mi_matrix_nce_fwd");
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   {
     ProfScope prof_("nce_matrix_stats_kernel", st);
@@ -1889,122 +1854,7 @@ int mi_matrix_nce_bwd(const float* scores, const int64_t* sid, int64_t b, int mo
   return MI_OK;
 }
 
-}  // extern "C"
-
-// ================================================================================================ Jensen-Shannon and NWJ
-// (mi_fdiv.h)  The per-sample InfoNCE's G-materialising chain with the fdiv epilogues: one record
-// per 64 x 64 score tile -> the fixed-order finalize (loss, terms, statistics) -> [grads] G GEMM (recomputed scores ->
-// G, G^T under the mode's rule) -> the unchanged dT / dY / dW / dX launches.  The fused B x B kernel is not used.
-namespace mi {
-
-static int fdiv_check(const char* fn, int64_t b, int64_t dx, int64_t dy, int mode, int precision) {
-  MI_CHECK_ARG(b >= 1 && dx >= 1 && dy >= 1, "%s: sizes must be >= 1 (b %lld, widths %lld, %lld)", fn, (long long)b,
-               (long long)dx, (long long)dy);
-  int rc = fdiv_check_mode(fn, mode);
-  if (rc) return rc;
-  MI_CHECK_ARG(precision == MI_PREC_F32 || precision == MI_PREC_BF16 || precision == MI_PREC_BF16X3,
-               "%s: precision %d is not available for the JSD / NWJ bounds on this critic (f32, bf16, bf16x3)", fn,
-               precision);
-  return MI_OK;
-}
-
-struct FdivBilinearPlan {
-  BilinearPlan p;
-  FdivRec* rec;  // [n_t][n_t]
-  mi_stats* stats;
-  int64_t n_t;
-  size_t bytes;
-};
-static FdivBilinearPlan plan_fdiv_bilinear(Workspace& ws, int64_t b, int64_t dx, int64_t dy, int precision) {
-  FdivBilinearPlan n{};
-  n.p = plan_bilinear(ws, b, b, dx, dy, precision, true);
-  n.n_t = (b + 63) / 64;
-  n.rec = ws.take<FdivRec>(n.n_t * n.n_t);
-  n.stats = ws.take<mi_stats>(1);
-  n.bytes = ws.off;
-  return n;
-}
-
-// stats: the caller's block or the workspace's; the G epilogue reads it
-template <typename OpT, typename TG>
-static int fdiv_step_generic(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t dx,
-                             int64_t dy, int mode, const float* grad_out, float* loss_out, float* terms_out,
-                             mi_stats* stats, float* grad_x, float* grad_y, float* grad_w, const FdivBilinearPlan& n,
-                             hipStream_t st) {
-  const BilinearPlan& p = n.p;
-  int rc = MI_OK;
-  const float* t = x;  // w == nullptr: S = X Y^T
-  if (w) {
-    rc = generic_gemm_store<OpT>(make_operand(x, dx, 1), make_operand(w, 1, dy), b, dy, dx, p.t, dy, p, st,
-                                 "fdiv T = X W (generic)");
-    if (rc) return rc;
-    t = p.t;
-  }
-  rc = launch_gemm<OpT>(make_operand(t, dy, 1), make_operand(y, dy, 1), b, b, dy,
-                        EpiFdivStats{FdivStatsOut{sid, sid, 0, mode, n.rec, n.n_t}}, st, "fdiv score + records (generic)");
-  if (rc) return rc;
-  rc = launch_fdiv_finalize(n.rec, n.n_t * n.n_t, b, mode, loss_out, terms_out, stats, st);
-  if (rc || !grad_y) return rc;
-  TG* g = (TG*)p.g;
-  rc = launch_gemm<OpT>(make_operand(t, dy, 1), make_operand(y, dy, 1), b, b, dy,
-                        EpiFdivGrad<TG>{FdivGradIn{sid, sid, 0, mode, stats, grad_out}, g}, st, "fdiv G (generic)");
-  if (rc) return rc;
-  return generic_bwd_from_g<OpT, TG>(x, y, w, t, g, b, b, dx, dy, grad_x, grad_y, grad_w, p, st);
-}
-
-static int fdiv_step_fast(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t dx,
-                          int64_t dy, int mode, const float* grad_out, float* loss_out, float* terms_out, mi_stats* stats,
-                          float* grad_x, float* grad_y, float* grad_w, const FdivBilinearPlan& n, hipStream_t st) {
-  const BilinearPlan& p = n.p;
-  const int x3 = p.x3;
-  int rc = nce_prep_fast(x, y, w, sid, sid, b, b, 0, dx, dy, p, st);
-  if (rc) return rc;
-  const GemmBf16Args scores = one_problem(p.tb, x3 * dy, p.yb, x3 * dy, b, b, x3 * dy);
-  rc = launch_gemm_bf16(scores, 1, EpiFdivStats{FdivStatsOut{sid, sid, 0, mode, n.rec, n.n_t}}, st, "fdiv score + records");
-  if (rc) return rc;
-  rc = launch_fdiv_finalize(n.rec, n.n_t * n.n_t, b, mode, loss_out, terms_out, stats, st);
-  if (rc || !grad_y) return rc;
-  rc = launch_gemm_bf16(scores, 1, EpiFdivGrad2{FdivGradIn{sid, sid, 0, mode, stats, grad_out}, p.gb, p.gtb, x3 == 3 ? 1 : 0},
-                        st, "fdiv G");
-  if (rc) return rc;
-  return bilinear_bwd_from_g(b, b, dx, dy, grad_x, grad_y, grad_w, w != nullptr, p, st);
-}
-
-static int fdiv_step_any(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t dx,
-                         int64_t dy, int mode, int precision, const float* grad_out, float* loss_out, float* terms_out,
-                         mi_stats* stats, float* grad_x, float* grad_y, float* grad_w, const FdivBilinearPlan& n,
-                         hipStream_t st) {
-  if (!stats) stats = n.stats;
-  if (nce_fast_ok(b, dx, dy, precision))
-    return fdiv_step_fast(x, y, w, sid, b, dx, dy, mode, grad_out, loss_out, terms_out, stats, grad_x, grad_y, grad_w, n,
-                          st);
-  if (precision == MI_PREC_BF16)
-    return fdiv_step_generic<bf16_t, bf16_t>(x, y, w, sid, b, dx, dy, mode, grad_out, loss_out, terms_out, stats, grad_x,
-                                             grad_y, grad_w, n, st);
-  return fdiv_step_generic<float, float>(x, y, w, sid, b, dx, dy, mode, grad_out, loss_out, terms_out, stats, grad_x,
-                                         grad_y, grad_w, n, st);
-}
-
-struct FdivSeparablePlan {
-  float *a, *c, *da, *dc;
-  FdivBilinearPlan n;
-  size_t bytes;
-};
-static FdivSeparablePlan plan_fdiv_separable(Workspace& ws, int64_t b, int64_t k, int precision) {
-  FdivSeparablePlan s{};
-  s.a = ws.take<float>(b * k);
-  s.c = ws.take<float>(b * k);
-  s.da = ws.take<float>(b * k);
-  s.dc = ws.take<float>(b * k);
-  s.n = plan_fdiv_bilinear(ws, b, k, k, precision);
-  s.bytes = ws.off;
-  return s;
-}
-
-}  // namespace mi
-
-extern "C" {
-
+// ------------------------------------------------------------------------------------------------ Jensen-Shannon and NWJ
 size_t mi_fdiv_bilinear_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int precision) {
   if (b <= 0 || d_img <= 0 || d_txt <= 0) return 0;
   Workspace ws(nullptr, 0);
@@ -2016,20 +1866,25 @@ int mi_fdiv_bilinear_step(const float* x, const float* y, const float* w, const 
                           mi_stats* stats, float* grad_x, float* grad_y, float* grad_w, void* workspace,
                           size_t workspace_bytes, void* stream) {
   MI_CHECK_ARG(x && y && sid && loss_out && workspace, "mi_fdiv_bilinear_step: null pointer");
-  int rc = fdiv_check("mi_fdiv_bilinear_step", b, d_img, d_txt, mode, precision);
+  int rc = chain_check<FdivEst>("mi_fdiv_bilinear_step", b, b, 0, d_img, d_txt, mode, precision);
   if (rc) return rc;
   MI_CHECK_ARG(w || d_img == d_txt, "mi_fdiv_bilinear_step: w == NULL (S = X Y^T) needs d_img == d_txt");
   const bool any_grad = grad_x || grad_y || grad_w;
   MI_CHECK_ARG(!any_grad || (grad_x && grad_y && (w ? grad_w != nullptr : grad_w == nullptr)),
                "mi_fdiv_bilinear_step: pass grad_x, grad_y and (with w) grad_w, or none of them");
   Workspace ws(workspace, workspace_bytes);
-  FdivBilinearPlan n = plan_fdiv_bilinear(ws, b, d_img, d_txt, precision);
-  if (!ws.ok()) {
-    set_error("mi_fdiv_bilinear_step: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
-  return fdiv_step_any(x, y, w, sid, b, d_img, d_txt, mode, precision, grad_out, loss_out, terms_out, stats, grad_x,
-                       grad_y, grad_w, n, (hipStream_t)stream);
+  const FdivBilinearPlan n = plan_fdiv_bilinear(ws, b, d_img, d_txt, precision);
+  rc = ws_fits(ws, "mi_fdiv_bilinear_step");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (!stats) stats = n.stats;  // the G epilogue reads the statistics: the caller's block or the workspace's
+  rc = chain_scores<FdivEst>(x, y, w, sid, sid, b, b, 0, d_img, d_txt, precision,
+                             FdivStatsOut{sid, sid, 0, mode, n.rec, n.n_t}, n.p, st);
+  if (rc) return rc;
+  rc = launch_fdiv_finalize(n.rec, n.n_t * n.n_t, b, mode, loss_out, terms_out, stats, st);
+  if (rc || !any_grad) return rc;
+  return chain_grads<FdivEst>(x, y, w, b, b, d_img, d_txt, precision, FdivGradIn{sid, sid, 0, mode, stats, grad_out},
+                              grad_x, grad_y, grad_w, n.p, st);
 }
 
 size_t mi_fdiv_separable_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int precision) {
@@ -2044,43 +1899,33 @@ int mi_fdiv_separable_step(const float* x, const float* y, const float* wg, cons
                            float* grad_y, float* grad_wg, float* grad_wh, void* workspace, size_t workspace_bytes,
                            void* stream) {
   MI_CHECK_ARG(x && y && wg && wh && sid && loss_out && workspace, "mi_fdiv_separable_step: null pointer");
-  int rc = fdiv_check("mi_fdiv_separable_step", b, d_img, d_txt, mode, precision);
+  int rc = chain_check<FdivEst>("mi_fdiv_separable_step", b, b, 0, d_img, d_txt, mode, precision);
   if (rc) return rc;
   MI_CHECK_ARG(d_proj >= 1, "mi_fdiv_separable_step: projection width must be >= 1");
   const bool any_grad = grad_x || grad_y || grad_wg || grad_wh;
   MI_CHECK_ARG(!any_grad || (grad_x && grad_y && grad_wg && grad_wh),
                "mi_fdiv_separable_step: pass all four gradients or none of them");
   Workspace ws(workspace, workspace_bytes);
-  FdivSeparablePlan sp = plan_fdiv_separable(ws, b, d_proj, precision);
-  if (!ws.ok()) {
-    set_error("mi_fdiv_separable_step: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  const auto sp = plan_fdiv_separable(ws, b, d_proj, precision);
+  rc = ws_fits(ws, "mi_fdiv_separable_step");
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int64_t k = d_proj;
-  // projections and their backward on the strided-operand kernels as in mi_nce_separable_step (bf16 operands in the bf16
-  // mode, exact fp32 products otherwise); the scores and their gradients on the bilinear chain with W = I
+  const FdivBilinearPlan& n = sp.n;
   const bool bf = precision == MI_PREC_BF16;
-  rc = nce_proj_gemm(bf, make_operand(x, d_img, 1), make_operand(wg, 1, k), b, k, d_img, sp.a, k, st,
-                     "fdiv separable A = X Wg");
+  if (!stats) stats = n.stats;
+  rc = separable_project<FdivEst>(bf, x, y, wg, wh, b, b, d_img, d_txt, k, sp.a, sp.c, st);
   if (rc) return rc;
-  rc = nce_proj_gemm(bf, make_operand(y, d_txt, 1), make_operand(wh, 1, k), b, k, d_txt, sp.c, k, st,
-                     "fdiv separable C = Y Wh");
+  rc = chain_scores<FdivEst>(sp.a, sp.c, nullptr, sid, sid, b, b, 0, k, k, precision,
+                             FdivStatsOut{sid, sid, 0, mode, n.rec, n.n_t}, n.p, st);
   if (rc) return rc;
-  rc = fdiv_step_any(sp.a, sp.c, nullptr, sid, b, k, k, mode, precision, grad_out, loss_out, terms_out, stats,
-                     any_grad ? sp.da : nullptr, any_grad ? sp.dc : nullptr, nullptr, sp.n, st);
+  rc = launch_fdiv_finalize(n.rec, n.n_t * n.n_t, b, mode, loss_out, terms_out, stats, st);
   if (rc || !any_grad) return rc;
-  rc = nce_proj_gemm(bf, make_operand((const float*)sp.da, k, 1), make_operand(wg, k, 1), b, d_img, k, grad_x, d_img, st,
-                     "fdiv separable dX = dA Wg^T");
+  rc = chain_grads<FdivEst>(sp.a, sp.c, nullptr, b, b, k, k, precision, FdivGradIn{sid, sid, 0, mode, stats, grad_out},
+                            sp.da, sp.dc, nullptr, n.p, st);
   if (rc) return rc;
-  rc = nce_proj_gemm(bf, make_operand(x, 1, d_img), make_operand((const float*)sp.da, 1, k), d_img, k, b, grad_wg, k, st,
-                     "fdiv separable dWg = X^T dA");
-  if (rc) return rc;
-  rc = nce_proj_gemm(bf, make_operand((const float*)sp.dc, k, 1), make_operand(wh, k, 1), b, d_txt, k, grad_y, d_txt, st,
-                     "fdiv separable dY = dC Wh^T");
-  if (rc) return rc;
-  return nce_proj_gemm(bf, make_operand(y, 1, d_txt), make_operand((const float*)sp.dc, 1, k), d_txt, k, b, grad_wh, k, st,
-                       "fdiv separable dWh = Y^T dC");
+  return separable_project_back<FdivEst>(bf, x, y, wg, wh, b, b, d_img, d_txt, k, sp.da, sp.dc, grad_x, grad_y, grad_wg,
+                                         grad_wh, st);
 }
 
 }  // extern "C"

@@ -354,10 +354,8 @@ int mi_bound_fwd(const float* logits, int64_t n, int64_t pos_size, int estimator
   MI_CHECK_ARG(estimator == MI_DV || estimator == MI_INFONCE, "mi_bound_fwd: unknown estimator %d", estimator);
   Workspace ws(workspace, workspace_bytes);
   Partial* partials = ws.take<Partial>(kMaxPartialBlocks);
-  if (!ws.ok()) {
-    set_error("mi_bound_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  int rc = ws_fits(ws, "mi_bound_fwd");
+  if (rc) return rc;
   const int grid = grid_for(n);
   hipStream_t st = (hipStream_t)stream;
   {
@@ -391,10 +389,8 @@ int mi_matrix_bound_fwd(const float* scores, const int64_t* sid, int64_t b, int 
   MI_CHECK_ARG(estimator == MI_DV || estimator == MI_INFONCE, "mi_matrix_bound_fwd: unknown estimator %d", estimator);
   Workspace ws(workspace, workspace_bytes);
   Partial* partials = ws.take<Partial>(kMaxPartialBlocks);
-  if (!ws.ok()) {
-    set_error("mi_matrix_bound_fwd: workspace too small");
-    return MI_EWORKSPACE;
-  }
+  const int rc = ws_fits(ws, "mi_matrix_bound_fwd");
+  if (rc) return rc;
   const int grid = grid_rows(b);
   hipStream_t st = (hipStream_t)stream;
   {
@@ -448,10 +444,8 @@ int mi_fdiv_bound_fwd(const float* logits, int64_t n, int64_t pos_size, int mode
   if (rc) return rc;
   Workspace ws(workspace, workspace_bytes);
   FdivRec* recs = ws.take<FdivRec>(kFdivMaxBlocks);
-  if (!ws.ok()) {
-    set_error("mi_fdiv_bound_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  rc = ws_fits(ws, "mi_fdiv_bound_fwd");
+  if (rc) return rc;
   const int grid = grid_for(n);
   hipStream_t st = (hipStream_t)stream;
   {
@@ -488,10 +482,8 @@ int mi_fdiv_matrix_fwd(const float* scores, const int64_t* sid, int64_t b, int m
   if (rc) return rc;
   Workspace ws(workspace, workspace_bytes);
   FdivRec* recs = ws.take<FdivRec>(kFdivMaxBlocks);
-  if (!ws.ok()) {
-    set_error("mi_fdiv_matrix_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  rc = ws_fits(ws, "mi_fdiv_matrix_fwd");
+  if (rc) return rc;
   return fdiv_matrix_forward(scores, sid, sid, b, b, 0, b, mode, recs, loss_out, terms_out, stats, (hipStream_t)stream);
 }
 

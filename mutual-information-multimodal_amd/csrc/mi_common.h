@@ -87,6 +87,13 @@ struct Workspace {
   }
   bool ok() const { return off <= size && (base != nullptr || off == 0); }
 };
+// MI_OK when everything taken fits the caller's workspace, else "<fn>: workspace too small (given < needed)<hint>" and
+// MI_EWORKSPACE
+static inline int ws_fits(const Workspace& ws, const char* fn, const char* hint = "") {
+  if (ws.ok()) return MI_OK;
+  set_error("%s: workspace too small (%zu < %zu)%s", fn, ws.size, ws.off, hint);
+  return MI_EWORKSPACE;
+}
 
 // ------------------------------------------------------------------------------------------------ types
 typedef __bf16 bf16_t;

@@ -518,10 +518,8 @@ int mi_concat_mlp_fwd(const float* x, const float* y, const float* w1, const flo
   MI_CHECK_ARG(estimator == MI_DV || estimator == MI_INFONCE, "mi_concat_mlp_fwd: unknown estimator %d", estimator);
   Workspace ws(workspace, workspace_bytes);
   ConcatPlan p = plan_concat(ws, b_rows, b, h1, h2, precision, need_grad, d_img > d_txt ? d_img : d_txt);
-  if (!ws.ok()) {
-    set_error("mi_concat_mlp_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  rc = ws_fits(ws, "mi_concat_mlp_fwd");
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   rc = concat_fwd_scores(x, y, w1, b1, w2, b2, w3, b3, b_rows, b, d_img, d_txt, h1, h2, precision, need_grad, scores_out, p,
                          st);
@@ -551,12 +549,8 @@ int mi_concat_mlp_bwd(const float* x, const float* y, const float* w1, const flo
   if (rc) return rc;
   Workspace ws(workspace, workspace_bytes);
   ConcatPlan p = plan_concat(ws, b_rows, b, h1, h2, precision, 1, d_img > d_txt ? d_img : d_txt);
-  if (!ws.ok()) {
-    set_error("mi_concat_mlp_bwd: workspace too small (%zu < %zu): pass the workspace of the forward call made with "
-              "need_grad = 1",
-              workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  rc = ws_fits(ws, "mi_concat_mlp_bwd", ": pass the workspace of the forward call made with need_grad = 1");
+  if (rc) return rc;
   return concat_bwd_dispatch<kGradDV>(x, y, w1, w2, b2, w3, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt,
                                       (int)h1, (int)h2, precision, stats, grad_out, scores, grad_x, grad_y, grad_w1,
                                       grad_b1, grad_w2, grad_b2, grad_w3, grad_b3, p, (hipStream_t)stream);
@@ -579,10 +573,8 @@ int mi_fdiv_concat_mlp_fwd(const float* x, const float* y, const float* w1, cons
   if (rc) return rc;
   Workspace ws(workspace, workspace_bytes);
   ConcatPlan p = plan_concat(ws, b_rows, b, h1, h2, precision, need_grad, d_img > d_txt ? d_img : d_txt);
-  if (!ws.ok()) {
-    set_error("mi_fdiv_concat_mlp_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  rc = ws_fits(ws, "mi_fdiv_concat_mlp_fwd");
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   rc = concat_fwd_scores(x, y, w1, b1, w2, b2, w3, b3, b_rows, b, d_img, d_txt, h1, h2, precision, need_grad, scores_out, p,
                          st);
@@ -611,12 +603,8 @@ int mi_fdiv_concat_mlp_bwd(const float* x, const float* y, const float* w1, cons
   if (rc) return rc;
   Workspace ws(workspace, workspace_bytes);
   ConcatPlan p = plan_concat(ws, b_rows, b, h1, h2, precision, 1, d_img > d_txt ? d_img : d_txt);
-  if (!ws.ok()) {
-    set_error("mi_fdiv_concat_mlp_bwd: workspace too small (%zu < %zu): pass the workspace of the forward call made "
-              "with need_grad = 1",
-              workspace_bytes, ws.off);
-    return MI_EWORKSPACE;
-  }
+  rc = ws_fits(ws, "mi_fdiv_concat_mlp_bwd", ": pass the workspace of the forward call made with need_grad = 1");
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (mode == MI_FDIV_JSD)
     return concat_bwd_dispatch<kGradJSD>(x, y, w1, w2, b2, w3, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt,

@@ -194,10 +194,8 @@ static int run_count_scan(const int64_t* sid, int64_t b, Workspace& ws, int** co
   int* counts = ws.take<int>(n_chunks + 1);
   int64_t* offsets = ws.take<int64_t>(n_chunks + 1);
   int64_t* nrows = ws.take<int64_t>(1);
-  if (!ws.ok()) {
-    set_error("pair index: workspace too small (%zu needed)", ws.off);
-    return MI_EWORKSPACE;
-  }
+  const int rc = ws_fits(ws, "pair index");
+  if (rc) return rc;
   if (n_chunks > 0) {
     {
       ProfScope prof_("pairs_count_kernel", st);
