@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the MI-critic hot path: one critic forward + backward over a synthetic batch per step.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
       N > 1: either launched by torch.distributed.run (one rank per GPU; RANK / LOCAL_RANK / WORLD_SIZE from the
       environment) or, when WORLD_SIZE is not set, bench.py starts the N ranks itself as child processes and relays
       rank 0's line; --gpus must equal the number of ranks, anything else is an error
       --dump-outputs DIR: after the K timed steps of the headline, what its last step handed back (loss, dX, dY and the
       critic's parameter gradients) goes to DIR/<name>.npy, so that two builds can be compared output for output on the
       same seeded inputs
+      --full: everything else the benchmark measures (see below); without it a run does only what the headline needs
 
 Headline workload (BASELINE.json configs[3], the configuration its metric is quoted on; it fits one GPU):
   global-batch "InfoNCE" (reference semantics, mi_critics.py:14-23), bilinear critic S = (X W) Y^T, B_global = 4096,
@@ -22,12 +23,17 @@ Before the W warm-up steps the GPU is brought to the clocks of a sustained run b
 (`--clock-warmup-ms`, 0 = off; reported in `timing.clock_warmup`): 20 timed steps that start cold take ~5 % longer each
 than the same steps inside a long run.
 
-One JSON line on stdout (rank 0): the driver's contract (`value` from exactly K steps between barriers / synchronize),
-plus `separable_mode` (BASELINE configs[1]), `timing` (median / p10 / p90 of >= 50 individually hipEvent-timed steps, graph and eager), `roofline` (dominant
-kernel, HIP-event timed through the library's profiling hook; measured HBM bytes and matrix-pipe busy fraction from the
-newest committed PMC pass of the SAME kernel sources), `parity_mode` (the same step in the modes held to fp32 tolerances:
-"f32_exact" and "bf16x3"), `fp8_mode` (BASELINE configs[4] on one GPU: B = 8192, d = 1024), `secondary` (the reference's own
-critic, make_mlp(2d,[1024,512])) and `cpu_baseline` (the oracle timed on this box's host cores, rank 0, N = 1 only).
+One JSON line on stdout (rank 0): the driver's contract (`value` from exactly K steps between barriers / synchronize).
+A plain run sets up, probes the launch mode, warms the clocks, takes the W + K steps, writes --dump-outputs and prints the
+line; nothing else.  With `--full` the line also carries `cold_ms_per_step` (the same W + K steps taken first, before the
+clock warm-up), `timing` (median / p10 / p90 of >= 50 individually hipEvent-timed steps, graph and eager), `roofline`
+(dominant kernel, HIP-event timed through the library's profiling hook; measured HBM bytes and matrix-pipe busy fraction
+from the newest committed PMC pass of the SAME kernel sources) and `kernels_us`, and the legs that take runs of their own:
+`other_boundary` (the headline step through the other dtype boundary), `parity_mode` (the same step in the modes held to
+fp32 tolerances: "f32_exact" and "bf16x3"), `fp8_mode` (BASELINE configs[4] on one GPU: B = 8192, d = 1024),
+`separable_mode` (BASELINE configs[1]), `secondary` (the reference's own critic, make_mlp(2d,[1024,512])) and
+`cpu_baseline` (the oracle timed on this box's host cores, rank 0, N = 1 only).  --timed-iters, --profile-steps, the
+--no-* switches, --secondary-steps and --cpu-seconds shape those extras and matter only with `--full`.
 """
 import argparse
 import glob
@@ -107,6 +113,9 @@ def parse_args():
                         "grad_y (whole global batch) and grad_param<i> (the critic's parameters in C-ABI order); beyond "
                         f"{DUMP_BYTES // 10**6} MB in all, every array keeps the same share of its rows, picked by a "
                         "fixed seed")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: cold_ms_per_step, event-timed statistics, per-kernel "
+                        "times and roofline, the other boundary, parity, fp8, separable and secondary legs, CPU baselines")
     args = p.parse_args()
     if args.steps < 1 or args.warmup < 0:
         p.error("--steps must be >= 1 and --warmup >= 0")
@@ -650,18 +659,17 @@ def main():
         elapsed = timed_run(st, steps, warmup, world)
         st.outputs = st.host_outputs() if keep_outputs else None  # (after the timed region: the later steps overwrite them)
         timing = timing_summary(st, timed_iters) if timed_iters else None
-        kernels = profile_kernels(st, args.profile_steps)
+        kernels = profile_kernels(st, args.profile_steps) if args.full else {}
         return st, elapsed, kernels, timing
 
     # the bf16 boundary exists for the bilinear critic in bf16 precision on one GPU (sharded runs gather fp32 rows)
     boundary = args.boundary if (args.critic == "bilinear" and args.precision == "bf16" and world == 1 and
                                  not os.environ.get("MI_BENCH_FORCE_DIST")) else "f32"
-    st, elapsed, kernels, timing = run(args.critic, args.steps, args.warmup, timed_iters=args.timed_iters, cold_first=True,
-                                       boundary=boundary, keep_outputs=bool(args.dump_outputs))
+    st, elapsed, kernels, timing = run(args.critic, args.steps, args.warmup, timed_iters=args.timed_iters if args.full else 0,
+                                       cold_first=args.full, boundary=boundary, keep_outputs=bool(args.dump_outputs))
     if args.dump_outputs and rank == 0:
         dump_outputs(st.outputs, args.dump_outputs)
     ms = elapsed / args.steps * 1e3
-    cold_ms = st.cold_elapsed / args.steps * 1e3
     flops = algorithmic_flops(args.critic, b, d, d)
     graph_mode = "none (direct C-ABI calls)" if st.use_eager else \
         ("one graph: kernels + the five RCCL collectives" if st.dist_mode and args.graph == "full" else
@@ -674,7 +682,6 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(ms, 5),
-        "cold_ms_per_step": round(cold_ms, 5),
         "warmup_effective_steps": args.warmup + st.clock_warmup_steps,
         "higher_is_better": True,
         "scaling": "strong",
@@ -692,16 +699,19 @@ def main():
         "timing": dict(timing or {}, clock_warmup={"budget_ms": args.clock_warmup_ms, "untimed_steps": st.clock_warmup_steps,
                                                    "note": "`ms_per_step`: untimed steps for budget_ms before the W warm-up "
                                                            "steps (sustained-run clocks; the same budget for every leg of "
-                                                           "this line); `cold_ms_per_step`: the same W + K steps taken "
-                                                           "first, without them"}),
+                                                           "this line)" + ("; `cold_ms_per_step`: the same W + K steps "
+                                                                           "taken first, without them" if args.full else "")}),
         "step_algorithmic_tflops": round(flops / (ms * 1e-3) / 1e12, 2),
         "step_frac_of_peak": round(flops / (ms * 1e-3) / 1e12 / (PEAK_TFLOPS[args.precision] * world), 5),
-        "roofline": roofline_of(kernels, br, b, d, args.precision),
-        "kernels_us": {k: round(v["ms_avg"] * 1e3, 2) for k, v in sorted(kernels.items(), key=lambda kv: -kv[1]["ms_total"])},
     }
+    if args.full:
+        out["cold_ms_per_step"] = round(st.cold_elapsed / args.steps * 1e3, 5)
+        out["roofline"] = roofline_of(kernels, br, b, d, args.precision)
+        out["kernels_us"] = {k: round(v["ms_avg"] * 1e3, 2) for k, v in sorted(kernels.items(), key=lambda kv: -kv[1]["ms_total"])}
     del st
     torch.cuda.empty_cache()
-    if args.critic == "bilinear" and args.precision == "bf16" and world == 1 and not os.environ.get("MI_BENCH_FORCE_DIST"):
+    if args.full and args.critic == "bilinear" and args.precision == "bf16" and world == 1 and \
+            not os.environ.get("MI_BENCH_FORCE_DIST"):
         # the same step on the same values through the other boundary (measured round 4: the bf16 boundary moves 25 MB less
         # per step and is NOT faster -- the conversion launch is bound by its chain of dependent k-steps, not by bytes)
         other = "f32" if boundary == "bf16" else "bf16"
@@ -721,7 +731,7 @@ def main():
         except Exception as e:
             out["other_boundary"] = {"error": f"{type(e).__name__}: {e}"}
         torch.cuda.empty_cache()
-    if not args.no_parity_mode and args.precision not in ("f32", "f32_exact"):
+    if args.full and not args.no_parity_mode and args.precision not in ("f32", "f32_exact"):
         # the same step in the mode whose results match the fp32 reference
         out["parity_mode"] = {}
         exact = "f32_exact" if args.critic == "bilinear" else "f32"  # "f32" on the bilinear critic resolves to bf16x3
@@ -744,7 +754,7 @@ def main():
                 out["parity_mode"][mode] = {"error": f"{type(e).__name__}: {e}"}
             torch.cuda.empty_cache()
         torch.cuda.empty_cache()
-    if not args.no_fp8 and args.critic == "bilinear" and world == 1:
+    if args.full and not args.no_fp8 and args.critic == "bilinear" and world == 1:
         # BASELINE configs[4] on ONE GPU (the whole 8192 x 8192 score matrix, not a rank's 1024-row share)
         try:
             b8, d8, n8 = 8192, 1024, max(3, args.steps // 10)
@@ -763,7 +773,7 @@ def main():
         except Exception as e:
             out["fp8_mode"] = {"error": f"{type(e).__name__}: {e}"}
         torch.cuda.empty_cache()
-    if not args.no_fp8 and args.critic == "bilinear" and world == 1:
+    if args.full and not args.no_fp8 and args.critic == "bilinear" and world == 1:
         # BASELINE configs[1]: InfoNCE separable critic S = (X Wg)(Y Wh)^T, 256-d, batch 256, bf16, one GPU
         try:
             bs, ds, ns = 256, 256, max(20, args.steps)
@@ -781,7 +791,7 @@ def main():
         except Exception as e:
             out["separable_mode"] = {"error": f"{type(e).__name__}: {e}"}
         torch.cuda.empty_cache()
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         other = "concat_mlp" if args.critic == "bilinear" else "bilinear"
         # the concat-MLP leg runs at the reference's own embedding width (768 per modality)
         d2 = 768 if other == "concat_mlp" else d
@@ -822,7 +832,7 @@ def main():
                         out["secondary"]["parity_mode"][mode] = {"error": f"{type(e).__name__}: {e}"}
         except Exception as e:
             out["secondary"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.critic, args)
         if "secondary" in out and "error" not in out["secondary"]:
             other = "concat_mlp" if args.critic == "bilinear" else "bilinear"

@@ -110,3 +110,12 @@ def test_steps_must_be_positive(monkeypatch):
     monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "7", "--warmup", "0", "--dump-outputs", "out"])
     args = bench.parse_args()
     assert args.steps == 7 and args.dump_outputs == "out"
+
+
+def test_full_is_opt_in(monkeypatch):
+    """A plain run measures the headline only; the other legs, baselines and per-kernel figures need `--full`."""
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert bench.parse_args().full is False
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "5", "--full", "--no-cpu-baseline"])
+    args = bench.parse_args()
+    assert args.full is True and args.no_cpu_baseline and args.steps == 5
