@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes
 import os
 from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
-from typing import Optional
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -18,14 +18,73 @@ LIB_PATH = os.environ.get("MI_CRITIC_LIB", os.path.join(_PKG_ROOT, "lib", "libmi
 
 MI_DV, MI_INFONCE = 0, 1
 MI_PREC_F32, MI_PREC_BF16, MI_PREC_BF16X3, MI_PREC_FP8, MI_PREC_F16, MI_PREC_F16X3 = 0, 1, 2, 3, 4, 5
-ESTIMATORS = {"dv": MI_DV, "infonce": MI_INFONCE}
 # the per-sample InfoNCE (mi_nce_* / mi_matrix_nce_*): mode codes of their own entry points, NOT estimator codes of the
-# entry points above
+# DV entry points
 MI_NCE_ROWWISE, MI_NCE_SYMMETRIC = 0, 1
-NCE_ESTIMATORS = {"infonce_rowwise": MI_NCE_ROWWISE, "infonce_symmetric": MI_NCE_SYMMETRIC}
 # the Jensen-Shannon and NWJ bounds (mi_fdiv_*): mode codes of their own entry points, not estimator codes either
 MI_FDIV_JSD, MI_FDIV_NWJ = 0, 1
-FDIV_ESTIMATORS = {"jsd": MI_FDIV_JSD, "nwj": MI_FDIV_NWJ}
+
+
+class Estimator(NamedTuple):
+    """How every entry point of the package runs one MI estimator."""
+    family: str                          # "dv" (the reference's bounds), "nce" (per-sample InfoNCE), "fdiv" (JSD / NWJ)
+    code: int                            # the estimator code (family "dv") or mode code of the family's entry points
+    critics: Optional[Tuple[str, ...]]   # critic kinds of fused_mi_bound and the sharded step; None: every critic
+    graphed: bool                        # GraphedMiStep and GlobalBatchGraphStep capture it
+    sharded: bool                        # the sharded global-batch step takes it
+    loss_shape: Tuple[int, ...]          # (1,) for "dv" as the reference, () for the rest
+    stats: str                           # what return_stats=True gives
+    logits: Optional[str]                # the reference-style callable of mi_critics on materialised logits
+    bound_entry: Optional[str]           # entry-point prefix of the bound on logits ...
+    matrix_entry: str                    # ... on a [B, B] score matrix ...
+    chain_entry: Optional[str]           # ... and of the one-call step of the bilinear and separable critics
+
+    def shape_loss(self, loss: torch.Tensor) -> torch.Tensor:
+        """The [1] loss of an entry point in this estimator's shape."""
+        return loss if loss.shape == self.loss_shape else loss.reshape(self.loss_shape)
+
+
+_DV = dict(family="dv", critics=None, graphed=True, sharded=True, stats="the statistics block (stats_dict)",
+           bound_entry="mi_bound", matrix_entry="mi_matrix_bound", chain_entry=None)
+_NCE = dict(family="nce", critics=("bilinear", "separable"), graphed=False, sharded=True, loss_shape=(),
+            stats="(lse_rows, lse_cols)", logits=None, bound_entry=None, matrix_entry="mi_matrix_nce", chain_entry="mi_nce")
+_FDIV = dict(family="fdiv", critics=None, graphed=False, sharded=False, loss_shape=(),
+             stats="(positive-pair term, negative-pair term)", bound_entry="mi_fdiv_bound", matrix_entry="mi_fdiv_matrix",
+             chain_entry="mi_fdiv")
+ESTIMATOR_TABLE = {
+    "dv": Estimator(code=MI_DV, loss_shape=(1,), logits="dv_bound_loss", **_DV),
+    "infonce": Estimator(code=MI_INFONCE, loss_shape=(), logits="infonce_bound_loss", **_DV),
+    "infonce_rowwise": Estimator(code=MI_NCE_ROWWISE, **_NCE),
+    "infonce_symmetric": Estimator(code=MI_NCE_SYMMETRIC, **_NCE),
+    "jsd": Estimator(code=MI_FDIV_JSD, logits="jsd_bound_loss", **_FDIV),
+    "nwj": Estimator(code=MI_FDIV_NWJ, logits="nwj_bound_loss", **_FDIV),
+}
+# name -> code views of one family each
+ESTIMATORS, NCE_ESTIMATORS, FDIV_ESTIMATORS = ({n: e.code for n, e in ESTIMATOR_TABLE.items() if e.family == f}
+                                               for f in ("dv", "nce", "fdiv"))
+
+
+def check_estimator(name: str, critic_kind: Optional[str] = None, where: str = "eager") -> Estimator:
+    """The record of an estimator name, validated for a critic kind ("concat_mlp", "bilinear", "separable"; None: any)
+    and for where it runs: "eager" (fused_mi_bound, matrix_bound_loss, MultiModalManager), "graphed" (GraphedMiStep),
+    "sharded" (global_batch_mi_bound) or "sharded graphed" (GlobalBatchGraphStep).  Raises ValueError otherwise."""
+    est = ESTIMATOR_TABLE.get(name)
+    if est is None:
+        # the reference leaves mi_critic unbound for an unknown estimator (main_utils.py:141-144, UnboundLocalError
+        # at :224); here it is rejected eagerly
+        raise ValueError(f"unknown mi_estimator {name!r}: expected one of {sorted(ESTIMATOR_TABLE)}")
+    if critic_kind is not None and est.critics is not None and critic_kind not in est.critics:
+        raise ValueError(f"mi_estimator {name!r} is implemented for the {' and '.join(est.critics)} critics only (got "
+                         f"{critic_kind!r}); for scores you compute yourself (e.g. a make_mlp critic applied to every "
+                         "pair) use matrix_bound_loss(scores, study_id, estimator)")
+    if "sharded" in where and not est.sharded:
+        raise ValueError(f"mi_estimator {name!r} is implemented on one GPU only (fused_mi_bound); the sharded "
+                         "global-batch step does not take it")
+    if "graphed" in where and not est.graphed:
+        raise ValueError(f"mi_estimator {name!r} runs eagerly: graph capture of it is not implemented")
+    return est
+
+
 PRECISIONS = {"f32": MI_PREC_F32, "fp32": MI_PREC_F32, "float32": MI_PREC_F32, "f32_exact": MI_PREC_F32,
               "bf16": MI_PREC_BF16, "bfloat16": MI_PREC_BF16, "bf16x3": MI_PREC_BF16X3, "fp8": MI_PREC_FP8,
               "f16": MI_PREC_F16, "fp16": MI_PREC_F16, "float16": MI_PREC_F16, "f16x3": MI_PREC_F16X3}

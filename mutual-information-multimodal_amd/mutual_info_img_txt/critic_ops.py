@@ -1,5 +1,5 @@
-"""The one binding of the critic entry points of the C ABI (mi_bilinear_*, mi_separable_*, mi_concat_mlp_*, mi_nce_*),
-shared by ``mi_critics`` (eager autograd), ``graphed`` (hipGraph step) and ``distributed`` (sharded step).
+"""The one binding of the critic entry points of the C ABI (mi_bilinear_*, mi_separable_*, mi_concat_mlp_*, mi_nce_*,
+mi_fdiv_*), shared by ``mi_critics`` (eager autograd), ``graphed`` (hipGraph step) and ``distributed`` (sharded step).
 
 An ops object scores the row block ``x`` [b_rows, d_img] (starting at ``row_offset``) against all of ``y_all``
 [b, d_txt]; a whole batch is ``b_rows == b``, ``row_offset == 0``.  Each ``*_call`` method writes one entry point's
@@ -114,27 +114,24 @@ class _HipOps:
                   stats.data_ptr())
         return loss, stats
 
-    def nce_step(self, x, y, params, sid, mode, precision, need_grad):
-        """Per-sample InfoNCE of the whole batch in one call, with the gradients of 1 * loss when ``need_grad``:
-        (loss [1], lse_rows [B], lse_cols [B], [grad_x, grad_y, grad_params...] or [])."""
+    def chain_step(self, entry, x, y, params, sid, mode, precision, need_grad):
+        """The whole batch in one call of ``{entry}_<critic>_step`` (bilinear and separable critics), with the gradients of
+        1 * loss when ``need_grad``: (loss [1], a, b, [grad_x, grad_y, grad_params...] or []).  ``entry`` "mi_nce"
+        (per-sample InfoNCE): a, b = lse_rows [B], lse_cols [B]; "mi_fdiv" (Jensen-Shannon / NWJ): a = terms [2], b = None."""
         b, dev = x.shape[0], x.device
-        ws = _hip.workspace(self.nce_workspace_bytes(b, x.shape[1], y.shape[1], params, precision), dev)
+        ws = _hip.workspace(self.chain_workspace_bytes(entry, b, x.shape[1], y.shape[1], params, precision), dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        r, c = torch.empty(b, dtype=torch.float32, device=dev), torch.empty(b, dtype=torch.float32, device=dev)
+        if entry == "mi_nce":
+            r, c = torch.empty(b, dtype=torch.float32, device=dev), torch.empty(b, dtype=torch.float32, device=dev)
+        else:
+            r, c = torch.empty(2, dtype=torch.float32, device=dev), None
         grads = [torch.empty_like(t) for t in (x, y, *params)] if need_grad else []
-        self.nce_call(x, y, params, sid, mode, precision, loss, r, c, grads, ws)()
+        self.chain_call(entry, x, y, params, sid, mode, precision, loss, r, c, grads, ws)()
         return loss, r, c, grads
 
-    def fdiv_step(self, x, y, params, sid, mode, precision, need_grad):
-        """Jensen-Shannon / NWJ bound of the whole batch in one call (bilinear and separable critics), with the gradients of
-        1 * loss when ``need_grad``: (loss [1], terms [2], [grad_x, grad_y, grad_params...] or [])."""
-        b, dev = x.shape[0], x.device
-        ws = _hip.workspace(self.fdiv_workspace_bytes(b, x.shape[1], y.shape[1], params, precision), dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        terms = torch.empty(2, dtype=torch.float32, device=dev)
-        grads = [torch.empty_like(t) for t in (x, y, *params)] if need_grad else []
-        self.fdiv_call(x, y, params, sid, mode, precision, loss, terms, grads, ws)()
-        return loss, terms, grads
+    def nce_step(self, x, y, params, sid, mode, precision, need_grad):
+        """``chain_step("mi_nce", ...)``: the one-call reference the row-block protocol below is checked against."""
+        return self.chain_step("mi_nce", x, y, params, sid, mode, precision, need_grad)
 
     # ---------------------------------------------- per-sample InfoNCE on a row block (distributed.GlobalBatchNceFn)
     def nce_forward(self, x, y_all, params, sid_rows, sid_all, row_offset, mode, precision, need_grad=True):
@@ -210,25 +207,14 @@ class HipBilinearOps(_HipOps):
                      gx.data_ptr(), gy.data_ptr(), _p(gw), ws.data_ptr(), ws.numel())
 
     @staticmethod
-    def nce_workspace_bytes(b, dx, dy, params, precision):
-        return _hip.load().mi_nce_bilinear_workspace_bytes(b, dx, dy, precision)
+    def chain_workspace_bytes(entry, b, dx, dy, params, precision):
+        return getattr(_hip.load(), f"{entry}_bilinear_workspace_bytes")(b, dx, dy, precision)
 
-    def nce_call(self, x, y, params, sid, mode, precision, loss, r, c, grads, ws):
+    def chain_call(self, entry, x, y, params, sid, mode, precision, loss, r, c, grads, ws):
         w = params[0] if params else None
         gx, gy, gw = (grads + [None] * 3)[:3]
-        return _call("mi_nce_bilinear_step", x.device, x.data_ptr(), y.data_ptr(), _p(w), sid.data_ptr(), x.shape[0],
-                     x.shape[1], y.shape[1], mode, precision, None, loss.data_ptr(), r.data_ptr(), c.data_ptr(), _p(gx),
-                     _p(gy), _p(gw), ws.data_ptr(), ws.numel())
-
-    @staticmethod
-    def fdiv_workspace_bytes(b, dx, dy, params, precision):
-        return _hip.load().mi_fdiv_bilinear_workspace_bytes(b, dx, dy, precision)
-
-    def fdiv_call(self, x, y, params, sid, mode, precision, loss, terms, grads, ws):
-        w = params[0] if params else None
-        gx, gy, gw = (grads + [None] * 3)[:3]
-        return _call("mi_fdiv_bilinear_step", x.device, x.data_ptr(), y.data_ptr(), _p(w), sid.data_ptr(), x.shape[0],
-                     x.shape[1], y.shape[1], mode, precision, None, loss.data_ptr(), terms.data_ptr(), None, _p(gx),
+        return _call(f"{entry}_bilinear_step", x.device, x.data_ptr(), y.data_ptr(), _p(w), sid.data_ptr(), x.shape[0],
+                     x.shape[1], y.shape[1], mode, precision, None, loss.data_ptr(), r.data_ptr(), _p(c), _p(gx),
                      _p(gy), _p(gw), ws.data_ptr(), ws.numel())
 
     @staticmethod
@@ -377,25 +363,14 @@ class HipSeparableOps(_HipOps):
                      gy.data_ptr(), gg.data_ptr(), gh.data_ptr(), ws.data_ptr(), ws.numel())
 
     @staticmethod
-    def nce_workspace_bytes(b, dx, dy, params, precision):
-        return _hip.load().mi_nce_separable_workspace_bytes(b, dx, dy, params[0].shape[1], precision)
+    def chain_workspace_bytes(entry, b, dx, dy, params, precision):
+        return getattr(_hip.load(), f"{entry}_separable_workspace_bytes")(b, dx, dy, params[0].shape[1], precision)
 
-    def nce_call(self, x, y, params, sid, mode, precision, loss, r, c, grads, ws):
+    def chain_call(self, entry, x, y, params, sid, mode, precision, loss, r, c, grads, ws):
         wg, wh = params
-        return _call("mi_nce_separable_step", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
+        return _call(f"{entry}_separable_step", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
                      sid.data_ptr(), x.shape[0], x.shape[1], y.shape[1], wg.shape[1], mode, precision, None,
-                     loss.data_ptr(), r.data_ptr(), c.data_ptr(), *[_p(g) for g in grads or [None] * 4], ws.data_ptr(),
-                     ws.numel())
-
-    @staticmethod
-    def fdiv_workspace_bytes(b, dx, dy, params, precision):
-        return _hip.load().mi_fdiv_separable_workspace_bytes(b, dx, dy, params[0].shape[1], precision)
-
-    def fdiv_call(self, x, y, params, sid, mode, precision, loss, terms, grads, ws):
-        wg, wh = params
-        return _call("mi_fdiv_separable_step", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
-                     sid.data_ptr(), x.shape[0], x.shape[1], y.shape[1], wg.shape[1], mode, precision, None,
-                     loss.data_ptr(), terms.data_ptr(), None, *[_p(g) for g in grads or [None] * 4], ws.data_ptr(),
+                     loss.data_ptr(), r.data_ptr(), _p(c), *[_p(g) for g in grads or [None] * 4], ws.data_ptr(),
                      ws.numel())
 
     @staticmethod

@@ -237,33 +237,18 @@ def global_batch_mi_bound(embedding_img, embedding_txt, study_id_codes, critic_p
     ``estimator`` = "infonce_rowwise" / "infonce_symmetric" (critic "bilinear" or "separable"): the per-sample InfoNCE
     normalised over the global batch (GlobalBatchNceFn), loss of shape []; ``return_stats=True`` then gives
     ``(loss, (lse_rows [B/G], lse_cols [B]))``."""
-    from .mi_critics import FDIV_ESTIMATORS, NCE_ESTIMATORS, _estimator_code
-    if estimator in FDIV_ESTIMATORS:
-        raise ValueError(f"mi_estimator {estimator!r}: the JSD / NWJ bounds are implemented on one GPU only "
-                         "(fused_mi_bound); the sharded global-batch step does not take them")
-    if estimator in NCE_ESTIMATORS:
-        if critic not in ("bilinear", "separable"):
-            raise ValueError(f"mi_estimator {estimator!r} is implemented for the bilinear and separable critics only; for "
-                             "scores you compute yourself use matrix_bound_loss(scores, study_id, estimator) (one GPU)")
-        if ops is None:
-            ops = OPS[critic]()
-        prec = resolve_critic(critic, precision, embedding_img.shape[0], embedding_img.shape[1],
-                              embedding_txt.shape[1], critic_params)[2]  # the same rank-row-count rule as below
-        loss, lse_rows, lse_cols = GlobalBatchNceFn.apply(ops, group, NCE_ESTIMATORS[estimator], prec, study_id_codes,
-                                                          embedding_img, embedding_txt, *critic_params)
-        loss = loss.reshape(())
-        return (loss, (lse_rows, lse_cols)) if return_stats else loss
+    est = _hip.check_estimator(estimator, critic, "sharded")
     if ops is None:
         ops = OPS[critic]()
-    est = _estimator_code(estimator)
     # the same name -> code resolution as on one GPU, except that the bf16x3 condition looks at this rank's row count
     # rather than at the global batch (kept as it is; tests/test_critic_resolution.py pins it)
     prec = resolve_critic(critic, precision, embedding_img.shape[0], embedding_img.shape[1], embedding_txt.shape[1],
                           critic_params)[2]
-    loss, stats = GlobalBatchCriticFn.apply(ops, group, est, prec, study_id_codes, embedding_img, embedding_txt,
-                                            *critic_params)
-    loss = loss if estimator == "dv" else loss.reshape(())
-    return (loss, stats) if return_stats else loss
+    fn = GlobalBatchNceFn if est.family == "nce" else GlobalBatchCriticFn
+    loss, *stats = fn.apply(ops, group, est.code, prec, study_id_codes, embedding_img, embedding_txt, *critic_params)
+    loss = est.shape_loss(loss)
+    # stats: GlobalBatchCriticFn's statistics block, or GlobalBatchNceFn's (lse_rows, lse_cols)
+    return (loss, stats[0] if len(stats) == 1 else tuple(stats)) if return_stats else loss
 
 
 class GlobalBatchGraphStep:
@@ -288,10 +273,7 @@ class GlobalBatchGraphStep:
 
     def __init__(self, x, y, sid, params: Sequence[torch.Tensor], estimator: str = "infonce", precision: str = "bf16",
                  critic: str = "bilinear", group=None, ops=None, capture: bool = True, overlap_reduce_scatter=None):
-        from .mi_critics import FDIV_ESTIMATORS, _estimator_code
-        if estimator in FDIV_ESTIMATORS:
-            raise ValueError(f"mi_estimator {estimator!r}: the JSD / NWJ bounds are implemented on one GPU only "
-                             "(fused_mi_bound); the sharded graphed step does not take them")
+        self.est = _hip.check_estimator(estimator, critic, "sharded graphed").code
         self.group = group
         # step_eager(): start the reduce-scatter of dY between the backward's two launches (it then runs beside dW).  OFF by
         # default: with direct calls the step is bound by the HOST (one-rank RCCL rehearsal, B = 4096: 0.196 ms per step
@@ -302,7 +284,6 @@ class GlobalBatchGraphStep:
         self.world = dist.get_world_size(group)
         self.rank = dist.get_rank(group)
         self.ops = ops if ops is not None else OPS[critic]()
-        self.est = _estimator_code(estimator)
         self.prec = resolve_critic(critic, precision, x.shape[0], x.shape[1], y.shape[1], params)[2]  # as above
         self.x, self.y, self.sid = x.detach(), y.detach(), sid
         self.params = [p.detach() for p in params]

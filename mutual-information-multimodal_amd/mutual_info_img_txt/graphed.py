@@ -25,7 +25,6 @@ import torch
 
 from . import _hip, mi_critics
 from .critic_ops import OPS, resolve_critic
-from .mi_critics import _estimator_code
 
 
 class GraphedMiStep:
@@ -39,10 +38,8 @@ class GraphedMiStep:
         if self.device.type != "cuda":
             raise _hip.MiCriticError("GraphedMiStep needs a ROCm device (no CPU fallback)")
         self.lib = _hip.load()
-        if estimator in _hip.FDIV_ESTIMATORS:
-            raise ValueError(f"mi_estimator {estimator!r}: the JSD / NWJ bounds run eagerly (fused_mi_bound, "
-                             "MultiModalManager.mi_step); graph capture of them is not implemented")
-        self.est = _estimator_code(estimator)
+        est = _hip.check_estimator(estimator, where="graphed")
+        self.est, self.shape_loss = est.code, est.shape_loss
         self.estimator = estimator
         self.b, self.dx, self.dy = int(batch_size), int(d_img), int(d_txt)
         dev = self.device
@@ -191,8 +188,7 @@ class GraphedMiStep:
             raise ValueError(f"GraphedMiStep was built for [{self.b},{self.dx}] / [{self.b},{self.dy}] embeddings")
         if study_id is not None:
             self.sid.copy_(mi_critics.study_id_codes(study_id, self.device))
-        out = _GraphedFn.apply(self, embedding_img, embedding_txt, *self.params)
-        return out if self.estimator == "dv" else out.reshape(())
+        return self.shape_loss(_GraphedFn.apply(self, embedding_img, embedding_txt, *self.params))
 
 
 class _GraphedFn(torch.autograd.Function):

@@ -152,32 +152,14 @@ class MultiModalManager:
     def mi_step(self, embedding_img, embedding_txt, study_id, mi_estimator: str = "dv", precision: str = "f32",
                 fused: bool = True, graph: bool = False):
         """Reference main_utils.py:220-224.  ``fused=False`` runs the literal three-call sequence (pair kernel, critic
-        module, bound kernel) and is only practical for small batches.  ``graph=True`` replays the fused step from
-        hipGraphs (``graphed.GraphedMiStep``, built on first use for this batch shape; the training loop's setting).
-        "infonce_rowwise" / "infonce_symmetric" always run eagerly through ``fused_mi_bound`` (one library call per step;
-        ``graph`` is ignored for them: GraphedMiStep captures the reference's estimators only).  So do the Jensen-Shannon and
-        NWJ bounds "jsd" / "nwj" (every critic); ``fused=False`` runs them on ``create_mi_pairs`` output through
-        ``jsd_bound_loss`` / ``nwj_bound_loss`` for the concat critic, on the score matrix for the others."""
-        if mi_estimator in mi_critics.FDIV_ESTIMATORS:
-            mi_critics.check_estimator(mi_estimator, self.critic_kind)
-            if fused:
-                return mi_critics.fused_mi_bound(embedding_img, embedding_txt, study_id, self.mi_discriminator,
-                                                 mi_estimator, precision)
-            if self.critic_kind != "concat_mlp":
-                scores = self.mi_discriminator(embedding_img, embedding_txt)
-                return mi_critics.matrix_bound_loss(scores, study_id, mi_estimator)
-            mi_input = self.create_mi_pairs(embedding_img, embedding_txt, study_id, embedding_img.device)
-            mi_output = self.mi_discriminator(mi_input)
-            critic = {"jsd": mi_critics.jsd_bound_loss, "nwj": mi_critics.nwj_bound_loss}[mi_estimator]
-            return critic(mi_output, len(study_id), embedding_img.device)
-        if mi_estimator in mi_critics.NCE_ESTIMATORS:
-            mi_critics.check_estimator(mi_estimator, self.critic_kind)
-            if not fused:
-                scores = self.mi_discriminator(embedding_img, embedding_txt)
-                return mi_critics.matrix_bound_loss(scores, study_id, mi_estimator)
-            return mi_critics.fused_mi_bound(embedding_img, embedding_txt, study_id, self.mi_discriminator,
-                                             mi_estimator, precision)
-        if fused and graph and self.critic_kind != "separable":
+        module, bound kernel: ``dv_bound_loss`` / ``infonce_bound_loss`` / ``jsd_bound_loss`` / ``nwj_bound_loss``) for
+        the concat critic and the critic module + ``matrix_bound_loss`` for the others; it is only practical for small
+        batches.  ``graph=True`` replays the fused step from hipGraphs (``graphed.GraphedMiStep``, built on first use for
+        this batch shape; the training loop's setting) for the estimators that GraphedMiStep captures ("dv", "infonce");
+        the others ("infonce_rowwise" / "infonce_symmetric", "jsd" / "nwj") always run eagerly through
+        ``fused_mi_bound``, and so does the separable critic."""
+        est = mi_critics.check_estimator(mi_estimator, self.critic_kind)
+        if fused and graph and est.graphed and self.critic_kind != "separable":
             g = self._graphed
             key = (tuple(embedding_img.shape), tuple(embedding_txt.shape), mi_estimator, precision)
             if g is None or g.key != key:
@@ -195,8 +177,7 @@ class MultiModalManager:
             return mi_critics.matrix_bound_loss(scores, study_id, mi_estimator)
         mi_input = self.create_mi_pairs(embedding_img, embedding_txt, study_id, embedding_img.device)
         mi_output = self.mi_discriminator(mi_input)
-        critic = {"dv": mi_critics.dv_bound_loss, "infonce": mi_critics.infonce_bound_loss}[mi_estimator]
-        return critic(mi_output, len(study_id), embedding_img.device)
+        return getattr(mi_critics, est.logits)(mi_output, len(study_id), embedding_img.device)
 
     # ------------------------------------------------------------------------------------------ batches
     def _build_loader(self, text_token_features, args):

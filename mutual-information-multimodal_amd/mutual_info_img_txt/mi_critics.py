@@ -23,19 +23,17 @@ wrapped in ``torch.autograd.Function``).  There is no CPU path: CPU tensors rais
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence, Union
+from typing import Sequence, Union
 
 import torch
 
 from . import _hip
-from ._hip import ESTIMATORS, FDIV_ESTIMATORS, NCE_ESTIMATORS
-from .critic_ops import (HipBilinearOps, HipConcatMlpOps, HipSeparableOps, _concat_params,  # noqa: F401 (re-exported)
+from ._hip import ESTIMATOR_TABLE, ESTIMATORS, check_estimator  # noqa: F401 (check_estimator: re-exported)
+from .critic_ops import (OPS, HipBilinearOps, HipConcatMlpOps, HipSeparableOps, _concat_params,  # noqa: F401 (re-exported)
                          _precision_code, fwd_outputs, resolve_critic)
 
 __all__ = ["dv_bound_loss", "infonce_bound_loss", "matrix_bound_loss", "fused_mi_bound", "study_id_codes",
-           "BilinearCriticFn", "SeparableCriticFn", "ConcatMlpCriticFn", "NceBilinearFn", "NceSeparableFn",
-           "check_estimator", "jsd_bound_loss", "nwj_bound_loss", "FdivBilinearFn", "FdivSeparableFn",
-           "FdivConcatMlpFn"]
+           "check_estimator", "jsd_bound_loss", "nwj_bound_loss"]
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -50,27 +48,10 @@ def study_id_codes(study_id: Union[Sequence, torch.Tensor], device) -> torch.Ten
 
 
 def _estimator_code(estimator: str) -> int:
+    """The estimator code of the DV entry points; ValueError for the names of the other families and unknown names."""
     if estimator not in ESTIMATORS:
-        # the reference leaves mi_critic unbound for an unknown estimator (main_utils.py:141-144, UnboundLocalError
-        # at :224); here it is rejected eagerly
         raise ValueError(f"unknown mi_estimator {estimator!r}: expected one of {sorted(ESTIMATORS)}")
     return ESTIMATORS[estimator]
-
-
-def check_estimator(estimator: str, critic_kind: str) -> None:
-    """Eager validation of an estimator name for a critic kind ("concat_mlp", "bilinear", "separable"): the reference's
-    "dv" / "infonce" and the Jensen-Shannon / NWJ bounds "jsd" / "nwj" for every critic, the per-sample
-    "infonce_rowwise" / "infonce_symmetric" for the bilinear and separable critics only."""
-    if estimator in FDIV_ESTIMATORS:
-        return
-    if estimator in NCE_ESTIMATORS:
-        if critic_kind not in ("bilinear", "separable"):
-            raise ValueError(f"mi_estimator {estimator!r} is implemented for the bilinear and separable critics only "
-                             f"(got critic {critic_kind!r})")
-        return
-    if estimator not in ESTIMATORS:
-        raise ValueError(f"unknown mi_estimator {estimator!r}: expected one of "
-                         f"{sorted(ESTIMATORS) + sorted(NCE_ESTIMATORS) + sorted(FDIV_ESTIMATORS)}")
 
 
 def _grad_scalar(grad: torch.Tensor) -> torch.Tensor:
@@ -78,186 +59,81 @@ def _grad_scalar(grad: torch.Tensor) -> torch.Tensor:
 
 
 # ----------------------------------------------------------------------------------------------------------
-# a3 / a4: bound on materialised logits
+# bound on scores computed elsewhere: the reference's logits layout, or a B x B score matrix with study-id masking
 # ----------------------------------------------------------------------------------------------------------
 class _BoundFn(torch.autograd.Function):
+    """loss [1] of the estimator ``est`` on logits [N] whose first ``pos_size`` rows are the positive pairs (``sid``
+    None; ``est.bound_entry``) or on a [B, B] score matrix with its study-id codes (``est.matrix_entry``).  For the
+    backward the forward keeps the statistics block (families "dv" and "fdiv"; "fdiv" leaves its terms pointer NULL) or
+    the row and column log-sum-exps ("nce")."""
+
     @staticmethod
-    def forward(ctx, logits: torch.Tensor, pos_size: int, estimator: int):
+    def forward(ctx, scores: torch.Tensor, sid, pos_size: int, est):
         lib = _hip.load()
-        flat = _hip.f32c(logits, "discriminator_logits").reshape(-1)
-        n = flat.numel()
-        dev = flat.device
-        ws = _hip.workspace(lib.mi_bound_workspace_bytes(n), dev)
-        stats = _hip.new_stats(dev)
+        if sid is None:
+            s = _hip.f32c(scores, "discriminator_logits").reshape(-1)
+            entry, head = est.bound_entry, (s.numel(), pos_size)
+        else:
+            s = _hip.f32c(scores, "scores")
+            entry, head = est.matrix_entry, (sid.data_ptr(), s.shape[0])
+        dev = s.device
+        ws = _hip.workspace(getattr(lib, f"{entry}_workspace_bytes")(s.shape[0]), dev)
+        if est.family == "nce":
+            kept = [torch.empty(s.shape[0], dtype=torch.float32, device=dev) for _ in range(2)]
+        else:
+            kept = [_hip.new_stats(dev)]
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        _hip.call("mi_bound_fwd", dev, flat.data_ptr(), n, int(pos_size), estimator, loss.data_ptr(), stats.data_ptr(),
-                                    ws.data_ptr(), ws.numel())
-        ctx.save_for_backward(flat, stats)
-        ctx.pos_size = int(pos_size)
-        ctx.in_shape = logits.shape
+        outs = [None] * (est.family == "fdiv") + [t.data_ptr() for t in kept]
+        _hip.call(f"{entry}_fwd", dev, s.data_ptr(), *head, est.code, loss.data_ptr(), *outs, ws.data_ptr(), ws.numel())
+        ctx.save_for_backward(s, sid, *kept)
+        ctx.entry, ctx.head, ctx.est, ctx.in_shape = entry, head, est, scores.shape
         return loss
 
     @staticmethod
     def backward(ctx, grad_loss):
-        lib = _hip.load()
-        flat, stats = ctx.saved_tensors
+        s, _sid, *kept = ctx.saved_tensors  # (sid saved: ctx.head holds its address)
         go = _grad_scalar(grad_loss)
-        grad = torch.empty_like(flat)
-        _hip.call("mi_bound_bwd", flat.device, flat.data_ptr(), flat.numel(), ctx.pos_size, stats.data_ptr(), go.data_ptr(),
-                                    grad.data_ptr())
-        return grad.reshape(ctx.in_shape), None, None
+        grad = torch.empty_like(s)
+        mode = [ctx.est.code] * (ctx.est.family != "dv")  # the DV backward takes the estimator from the statistics
+        _hip.call(f"{ctx.entry}_bwd", s.device, s.data_ptr(), *ctx.head, *mode, *[t.data_ptr() for t in kept],
+                  go.data_ptr(), grad.data_ptr())
+        return grad.reshape(ctx.in_shape), None, None, None
 
 
-def _bound(discriminator_logits, pos_size, estimator):
+def _bound(discriminator_logits, pos_size, est):
     _hip.require_device(discriminator_logits, "discriminator_logits")
     n = discriminator_logits.shape[0]
     if discriminator_logits.numel() != n:
         raise ValueError("discriminator_logits must be [N] or [N, 1] (one score per pair row)")
     if not 0 <= int(pos_size) <= n:
         raise ValueError(f"pos_size={pos_size} outside [0, {n}]")
-    return _BoundFn.apply(discriminator_logits, int(pos_size), estimator)
+    return _BoundFn.apply(discriminator_logits, None, int(pos_size), est)
 
 
 def dv_bound_loss(discriminator_logits: torch.Tensor, pos_size: int, device=None) -> torch.Tensor:
     """Donsker-Varadhan bound, reference mi_critics.py:3-12: ``LSE(logits[pos:]) - log(N - pos) - mean(logits[:pos])``.
     ``device`` is kept for signature compatibility (the reference only uses it for the log-N constant)."""
-    loss = _bound(discriminator_logits, pos_size, _hip.MI_DV)
+    loss = _bound(discriminator_logits, pos_size, ESTIMATOR_TABLE["dv"])
     return loss.reshape(discriminator_logits.shape[1:])  # [N,1] -> [1] as in the reference
 
 
 def infonce_bound_loss(discriminator_logits: torch.Tensor, pos_size: int, device=None) -> torch.Tensor:
     """The reference's "InfoNCE" bound, mi_critics.py:14-23: ``LSE(logits[pos:]) - mean(logits[:pos])`` (no log-N term;
     not a row-wise softmax cross-entropy).  Returns shape []."""
-    return _bound(discriminator_logits, pos_size, _hip.MI_INFONCE).reshape(())
-
-
-class _FdivBoundFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits: torch.Tensor, pos_size: int, mode: int):
-        lib = _hip.load()
-        flat = _hip.f32c(logits, "discriminator_logits").reshape(-1)
-        n, dev = flat.numel(), flat.device
-        ws = _hip.workspace(lib.mi_fdiv_bound_workspace_bytes(n), dev)
-        stats = _hip.new_stats(dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        _hip.call("mi_fdiv_bound_fwd", dev, flat.data_ptr(), n, int(pos_size), mode, loss.data_ptr(), None,
-                  stats.data_ptr(), ws.data_ptr(), ws.numel())
-        ctx.save_for_backward(flat, stats)
-        ctx.pos_size, ctx.mode, ctx.in_shape = int(pos_size), mode, logits.shape
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        flat, stats = ctx.saved_tensors
-        go = _grad_scalar(grad_loss)
-        grad = torch.empty_like(flat)
-        _hip.call("mi_fdiv_bound_bwd", flat.device, flat.data_ptr(), flat.numel(), ctx.pos_size, ctx.mode,
-                  stats.data_ptr(), go.data_ptr(), grad.data_ptr())
-        return grad.reshape(ctx.in_shape), None, None
-
-
-def _fdiv_bound(discriminator_logits, pos_size, mode):
-    _hip.require_device(discriminator_logits, "discriminator_logits")
-    n = discriminator_logits.shape[0]
-    if discriminator_logits.numel() != n:
-        raise ValueError("discriminator_logits must be [N] or [N, 1] (one score per pair row)")
-    if not 0 <= int(pos_size) <= n:
-        raise ValueError(f"pos_size={pos_size} outside [0, {n}]")
-    return _FdivBoundFn.apply(discriminator_logits, int(pos_size), mode).reshape(())
+    return _bound(discriminator_logits, pos_size, ESTIMATOR_TABLE["infonce"]).reshape(())
 
 
 def jsd_bound_loss(discriminator_logits: torch.Tensor, pos_size: int, device=None) -> torch.Tensor:
     """Jensen-Shannon bound (Deep InfoMax) on the reference's logits layout (the first ``pos_size`` rows positive):
     ``mean(softplus(-logits[:pos])) + mean(softplus(logits[pos:]))``, shape [].  Finite for any finite logits.  ``device``
     is kept for the signature of the reference's callables."""
-    return _fdiv_bound(discriminator_logits, pos_size, _hip.MI_FDIV_JSD)
+    return _bound(discriminator_logits, pos_size, ESTIMATOR_TABLE["jsd"]).reshape(())
 
 
 def nwj_bound_loss(discriminator_logits: torch.Tensor, pos_size: int, device=None) -> torch.Tensor:
     """NWJ bound (f-GAN KL, "MINE-f") on the reference's logits layout: ``exp(LSE(logits[pos:]) - log(N - pos) - 1) -
     mean(logits[:pos])``, shape []; ``-loss`` is the NWJ lower bound on the MI."""
-    return _fdiv_bound(discriminator_logits, pos_size, _hip.MI_FDIV_NWJ)
-
-
-# ----------------------------------------------------------------------------------------------------------
-# bound on a B x B score matrix with study-id masking
-# ----------------------------------------------------------------------------------------------------------
-class _MatrixBoundFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, scores: torch.Tensor, sid: torch.Tensor, estimator: int):
-        lib = _hip.load()
-        s = _hip.f32c(scores, "scores")
-        b = s.shape[0]
-        dev = s.device
-        ws = _hip.workspace(lib.mi_matrix_bound_workspace_bytes(b), dev)
-        stats = _hip.new_stats(dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        _hip.call("mi_matrix_bound_fwd", dev, s.data_ptr(), sid.data_ptr(), b, estimator, loss.data_ptr(),
-                                           stats.data_ptr(), ws.data_ptr(), ws.numel())
-        ctx.save_for_backward(s, sid, stats)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        lib = _hip.load()
-        s, sid, stats = ctx.saved_tensors
-        go = _grad_scalar(grad_loss)
-        grad = torch.empty_like(s)
-        _hip.call("mi_matrix_bound_bwd", s.device, s.data_ptr(), sid.data_ptr(), s.shape[0], stats.data_ptr(), go.data_ptr(),
-                                           grad.data_ptr())
-        return grad, None, None
-
-
-class _MatrixNceFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, scores: torch.Tensor, sid: torch.Tensor, mode: int):
-        lib = _hip.load()
-        s = _hip.f32c(scores, "scores")
-        b = s.shape[0]
-        dev = s.device
-        ws = _hip.workspace(lib.mi_matrix_nce_workspace_bytes(b), dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        r = torch.empty(b, dtype=torch.float32, device=dev)
-        c = torch.empty(b, dtype=torch.float32, device=dev)
-        _hip.call("mi_matrix_nce_fwd", dev, s.data_ptr(), sid.data_ptr(), b, mode, loss.data_ptr(), r.data_ptr(),
-                  c.data_ptr(), ws.data_ptr(), ws.numel())
-        ctx.save_for_backward(s, sid, r, c)
-        ctx.mode = mode
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        s, sid, r, c = ctx.saved_tensors
-        go = _grad_scalar(grad_loss)
-        grad = torch.empty_like(s)
-        _hip.call("mi_matrix_nce_bwd", s.device, s.data_ptr(), sid.data_ptr(), s.shape[0], ctx.mode, r.data_ptr(),
-                  c.data_ptr(), go.data_ptr(), grad.data_ptr())
-        return grad, None, None
-
-
-class _MatrixFdivFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, scores: torch.Tensor, sid: torch.Tensor, mode: int):
-        lib = _hip.load()
-        s = _hip.f32c(scores, "scores")
-        b, dev = s.shape[0], s.device
-        ws = _hip.workspace(lib.mi_fdiv_matrix_workspace_bytes(b), dev)
-        stats = _hip.new_stats(dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        _hip.call("mi_fdiv_matrix_fwd", dev, s.data_ptr(), sid.data_ptr(), b, mode, loss.data_ptr(), None,
-                  stats.data_ptr(), ws.data_ptr(), ws.numel())
-        ctx.save_for_backward(s, sid, stats)
-        ctx.mode = mode
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        s, sid, stats = ctx.saved_tensors
-        go = _grad_scalar(grad_loss)
-        grad = torch.empty_like(s)
-        _hip.call("mi_fdiv_matrix_bwd", s.device, s.data_ptr(), sid.data_ptr(), s.shape[0], ctx.mode, stats.data_ptr(),
-                  go.data_ptr(), grad.data_ptr())
-        return grad, None, None
+    return _bound(discriminator_logits, pos_size, ESTIMATOR_TABLE["nwj"]).reshape(())
 
 
 def matrix_bound_loss(scores: torch.Tensor, study_id, estimator: str = "dv") -> torch.Tensor:
@@ -271,188 +147,84 @@ def matrix_bound_loss(scores: torch.Tensor, study_id, estimator: str = "dv") -> 
     _hip.require_device(scores, "scores")
     if scores.dim() != 2 or scores.shape[0] != scores.shape[1]:
         raise ValueError("scores must be [B, B]")
-    if estimator in FDIV_ESTIMATORS:
-        sid = study_id_codes(study_id, scores.device)
-        if sid.numel() != scores.shape[0]:
-            raise ValueError("study_id length must equal B")
-        return _MatrixFdivFn.apply(scores, sid, FDIV_ESTIMATORS[estimator]).reshape(())
-    if estimator in NCE_ESTIMATORS:
-        sid = study_id_codes(study_id, scores.device)
-        if sid.numel() != scores.shape[0]:
-            raise ValueError("study_id length must equal B")
-        return _MatrixNceFn.apply(scores, sid, NCE_ESTIMATORS[estimator]).reshape(())
-    code = _estimator_code(estimator)
+    est = check_estimator(estimator)
     sid = study_id_codes(study_id, scores.device)
     if sid.numel() != scores.shape[0]:
         raise ValueError("study_id length must equal B")
-    loss = _MatrixBoundFn.apply(scores, sid, code)
-    return loss if estimator == "dv" else loss.reshape(())
+    return est.shape_loss(_BoundFn.apply(scores, sid, 0, est))
 
 
 # ----------------------------------------------------------------------------------------------------------
 # fused critics: thin autograd Functions over the ops objects of critic_ops (whole batch: b_rows = b, row_offset = 0)
 # ----------------------------------------------------------------------------------------------------------
-def _critic_forward(ctx, ops, x, y, params, sid, estimator, precision, scores):
-    loss, stats, _, scores = out = fwd_outputs(x.device, scores)
-    _, saved = ops.forward(x, y, params, sid, sid, 0, estimator, precision, any(ctx.needs_input_grad), out=out)
-    ctx.save_for_backward(x, y, sid, stats, scores, saved[-1], *params)
-    ctx.ops, ctx.precision = ops, precision
-    ctx.mark_non_differentiable(*[t for t in (stats, scores) if t is not None])
-    return loss, stats, scores
+def _f32_inputs(x, y, params):
+    return (_hip.f32c(x, "embedding_img"), _hip.f32c(y, "embedding_txt"),
+            [_hip.f32c(p, f"critic param {n}") for n, p in enumerate(params)])
 
 
-def _critic_backward(ctx, grad_loss):
-    """(grad_x, grad_y, [grad_params...]) of grad_loss * loss."""
-    x, y, sid, stats, scores, ws, *params = ctx.saved_tensors
-    return ctx.ops.backward((x, y, params, sid, sid, 0, ctx.precision, scores, ws), stats, _grad_scalar(grad_loss))
-
-
-class BilinearCriticFn(torch.autograd.Function):
-    """loss = bound(S), S = (X W) Y^T (W None: X Y^T) with study-id masking; all gradients by the HIP backward."""
+class _CriticFn(torch.autograd.Function):
+    """loss = bound(S) of the DV entry points with study-id masking, S from the critic ``kind`` of critic_ops: (X W) Y^T
+    (no params: X Y^T), (X Wg)(Y Wh)^T or MLP([x_i ; y_j]) of make_mlp(d,[h1,h2]) (model.py:18-32); forward and all
+    gradients by the HIP library.  Returns (loss [1], statistics, scores [B, B] or None)."""
 
     @staticmethod
-    def forward(ctx, x, y, w, sid, estimator: int, precision: int, want_scores: bool):
-        x, y = _hip.f32c(x, "embedding_img"), _hip.f32c(y, "embedding_txt")
-        params = [] if w is None else [_hip.f32c(w, "bilinear weight")]
+    def forward(ctx, kind: str, sid, estimator: int, precision: int, want_scores: bool, x, y, *params):
+        x, y, params = _f32_inputs(x, y, params)
         b = x.shape[0]
-        if params:
+        if kind == "bilinear" and params:
             _hip.note_path("bilinear", (b, b, x.shape[1], y.shape[1]), precision)
-        scores = torch.empty(b, b, dtype=torch.float32, device=x.device) if want_scores else None
-        return _critic_forward(ctx, HipBilinearOps(), x, y, params, sid, estimator, precision, scores)
+        elif kind == "separable":
+            _hip.note_path("separable", (b, b, x.shape[1], y.shape[1], params[0].shape[1]), precision)
+        scores = None
+        if want_scores or kind == "concat_mlp":  # the concat-MLP backward reads them
+            scores = torch.empty(b, b, dtype=torch.float32, device=x.device)
+        ops = OPS[kind]()
+        loss, stats, _, scores = out = fwd_outputs(x.device, scores)
+        _, saved = ops.forward(x, y, params, sid, sid, 0, estimator, precision, any(ctx.needs_input_grad), out=out)
+        ctx.save_for_backward(x, y, sid, stats, scores, saved[-1], *params)
+        ctx.ops, ctx.precision = ops, precision
+        ctx.mark_non_differentiable(*[t for t in (stats, scores) if t is not None])
+        return loss, stats, scores
 
     @staticmethod
     def backward(ctx, grad_loss, _gs, _gsc):
-        gx, gy, gp = _critic_backward(ctx, grad_loss)
-        return gx, gy, (gp[0] if gp else None), None, None, None, None
+        x, y, sid, stats, scores, ws, *params = ctx.saved_tensors
+        gx, gy, gp = ctx.ops.backward((x, y, params, sid, sid, 0, ctx.precision, scores, ws), stats,
+                                      _grad_scalar(grad_loss))
+        return (None,) * 5 + (gx, gy, *gp)
 
 
-class SeparableCriticFn(torch.autograd.Function):
-    """loss = bound(S), S = (X Wg)(Y Wh)^T with study-id masking; projections, fused B x B stage and all gradients by
-    the HIP library (BASELINE.json configs[1]).  Projection shapes are checked by ``resolve_critic``."""
-
-    @staticmethod
-    def forward(ctx, x, y, wg, wh, sid, estimator: int, precision: int):
-        x, y = _hip.f32c(x, "embedding_img"), _hip.f32c(y, "embedding_txt")
-        params = [_hip.f32c(wg, "image projection"), _hip.f32c(wh, "text projection")]
-        b = x.shape[0]
-        _hip.note_path("separable", (b, b, x.shape[1], y.shape[1], wg.shape[1]), precision)
-        return _critic_forward(ctx, HipSeparableOps(), x, y, params, sid, estimator, precision, None)
+class _ChainFn(torch.autograd.Function):
+    """The per-sample InfoNCE ("mi_nce") or the Jensen-Shannon / NWJ bound ("mi_fdiv") of the bilinear or separable
+    critic in one library call (``ops.chain_step``).  With ``need_grad`` the call also writes every gradient for
+    dL/dloss = 1; the backward only scales them by grad_loss.  Returns (loss [1], lse_rows [B], lse_cols [B]) or
+    (loss [1], terms [2], None)."""
 
     @staticmethod
-    def backward(ctx, grad_loss, _gs, _gsc):
-        gx, gy, gp = _critic_backward(ctx, grad_loss)
-        return (gx, gy, *gp, None, None, None)
-
-
-class ConcatMlpCriticFn(torch.autograd.Function):
-    """loss = bound(S), S[i,j] = MLP([x_i ; y_j]) with the reference critic make_mlp(d,[h1,h2]) (model.py:18-32)."""
-
-    @staticmethod
-    def forward(ctx, x, y, w1, b1, w2, b2, w3, b3, sid, estimator: int, precision: int, want_scores: bool):
-        x, y = _hip.f32c(x, "embedding_img"), _hip.f32c(y, "embedding_txt")
-        params = [_hip.f32c(p, f"critic param {n}") for n, p in enumerate((w1, b1, w2, b2, w3, b3))]
-        scores = torch.empty(x.shape[0], x.shape[0], dtype=torch.float32, device=x.device)  # the backward reads them
-        return _critic_forward(ctx, HipConcatMlpOps(), x, y, params, sid, estimator, precision, scores)
+    def forward(ctx, kind: str, entry: str, sid, mode: int, precision: int, need_grad: bool, x, y, *params):
+        x, y, params = _f32_inputs(x, y, params)
+        loss, a, b, grads = OPS[kind]().chain_step(entry, x, y, params, sid, mode, precision, need_grad)
+        ctx.save_for_backward(*grads)
+        ctx.mark_non_differentiable(*[t for t in (a, b) if t is not None])
+        return loss, a, b
 
     @staticmethod
-    def backward(ctx, grad_loss, _gs, _gsc):
-        gx, gy, gp = _critic_backward(ctx, grad_loss)
-        return (gx, gy, *gp, None, None, None, None)
+    def backward(ctx, grad_loss, _ga, _gb):
+        saved = ctx.saved_tensors
+        if not saved:
+            raise RuntimeError("_ChainFn: the forward ran without gradients (need_grad=False)")
+        go = grad_loss.reshape(-1)[:1].to(torch.float32)
+        return (None,) * 6 + tuple(g * go for g in saved)
 
 
-def _nce_forward(ctx, ops, x, y, params, sid, mode, precision, need_grad):
-    loss, r, c, grads = ops.nce_step(x, y, params, sid, mode, precision, need_grad)
-    ctx.save_for_backward(*grads)
-    ctx.mark_non_differentiable(r, c)
-    return loss, r, c
-
-
-def _nce_backward(ctx, grad_loss, name):
-    """The gradients the forward call wrote for dL/dloss = 1, scaled by grad_loss."""
-    saved = ctx.saved_tensors
-    if not saved:
-        raise RuntimeError(f"{name}: the forward ran without gradients (need_grad=False)")
-    go = grad_loss.reshape(-1)[:1].to(torch.float32)
-    return (*(g * go for g in saved), *[None] * (len(ctx.needs_input_grad) - len(saved)))
-
-
-class NceBilinearFn(torch.autograd.Function):
-    """Per-sample InfoNCE of S = (X W) Y^T (W None: S = X Y^T) in one library call (mi_nce_bilinear_step).  With
-    ``need_grad`` the call also writes every gradient for dL/dloss = 1; the backward only scales them by grad_loss.
-    Returns (loss [1], lse_rows [B], lse_cols [B])."""
-
-    @staticmethod
-    def forward(ctx, x, y, w, sid, mode: int, precision: int, need_grad: bool):
-        x, y = _hip.f32c(x, "embedding_img"), _hip.f32c(y, "embedding_txt")
-        params = [] if w is None else [_hip.f32c(w, "bilinear weight")]
-        return _nce_forward(ctx, HipBilinearOps(), x, y, params, sid, mode, precision, need_grad)
-
-    @staticmethod
-    def backward(ctx, grad_loss, _gr, _gc):
-        return _nce_backward(ctx, grad_loss, "NceBilinearFn")
-
-
-class NceSeparableFn(torch.autograd.Function):
-    """Per-sample InfoNCE of S = (X Wg)(Y Wh)^T in one library call (mi_nce_separable_step); see NceBilinearFn."""
-
-    @staticmethod
-    def forward(ctx, x, y, wg, wh, sid, mode: int, precision: int, need_grad: bool):
-        x, y = _hip.f32c(x, "embedding_img"), _hip.f32c(y, "embedding_txt")
-        params = [_hip.f32c(wg, "image projection"), _hip.f32c(wh, "text projection")]
-        return _nce_forward(ctx, HipSeparableOps(), x, y, params, sid, mode, precision, need_grad)
-
-    @staticmethod
-    def backward(ctx, grad_loss, _gr, _gc):
-        return _nce_backward(ctx, grad_loss, "NceSeparableFn")
-
-
-def _fdiv_step_forward(ctx, ops, x, y, params, sid, mode, precision, need_grad):
-    loss, terms, grads = ops.fdiv_step(x, y, params, sid, mode, precision, need_grad)
-    ctx.save_for_backward(*grads)
-    ctx.mark_non_differentiable(terms)
-    return loss, terms
-
-
-class FdivBilinearFn(torch.autograd.Function):
-    """Jensen-Shannon / NWJ bound of S = (X W) Y^T (W None: S = X Y^T) in one library call (mi_fdiv_bilinear_step); with
-    ``need_grad`` the call also writes every gradient for dL/dloss = 1, the backward scales them.  Returns (loss [1],
-    terms [2])."""
-
-    @staticmethod
-    def forward(ctx, x, y, w, sid, mode: int, precision: int, need_grad: bool):
-        x, y = _hip.f32c(x, "embedding_img"), _hip.f32c(y, "embedding_txt")
-        params = [] if w is None else [_hip.f32c(w, "bilinear weight")]
-        return _fdiv_step_forward(ctx, HipBilinearOps(), x, y, params, sid, mode, precision, need_grad)
-
-    @staticmethod
-    def backward(ctx, grad_loss, _gt):
-        return _nce_backward(ctx, grad_loss, "FdivBilinearFn")
-
-
-class FdivSeparableFn(torch.autograd.Function):
-    """Jensen-Shannon / NWJ bound of S = (X Wg)(Y Wh)^T in one library call (mi_fdiv_separable_step); see
-    FdivBilinearFn."""
-
-    @staticmethod
-    def forward(ctx, x, y, wg, wh, sid, mode: int, precision: int, need_grad: bool):
-        x, y = _hip.f32c(x, "embedding_img"), _hip.f32c(y, "embedding_txt")
-        params = [_hip.f32c(wg, "image projection"), _hip.f32c(wh, "text projection")]
-        return _fdiv_step_forward(ctx, HipSeparableOps(), x, y, params, sid, mode, precision, need_grad)
-
-    @staticmethod
-    def backward(ctx, grad_loss, _gt):
-        return _nce_backward(ctx, grad_loss, "FdivSeparableFn")
-
-
-class FdivConcatMlpFn(torch.autograd.Function):
+class _FdivConcatFn(torch.autograd.Function):
     """Jensen-Shannon / NWJ bound of S[i,j] = MLP([x_i ; y_j]) (make_mlp(d,[h1,h2])): the fused forward writes scores,
     sign-bit images and statistics; the backward kernels run under the mode's gradient rule.  Returns (loss [1],
     terms [2], scores [B, B])."""
 
     @staticmethod
-    def forward(ctx, x, y, w1, b1, w2, b2, w3, b3, sid, mode: int, precision: int):
-        x, y = _hip.f32c(x, "embedding_img"), _hip.f32c(y, "embedding_txt")
-        params = [_hip.f32c(p, f"critic param {n}") for n, p in enumerate((w1, b1, w2, b2, w3, b3))]
+    def forward(ctx, sid, mode: int, precision: int, x, y, *params):
+        x, y, params = _f32_inputs(x, y, params)
         need_grad = any(ctx.needs_input_grad)
         loss, terms, saved = HipConcatMlpOps().fdiv_forward(x, y, params, sid, sid, 0, mode, precision, need_grad)
         scores, stats, ws = saved[8:]
@@ -466,36 +238,7 @@ class FdivConcatMlpFn(torch.autograd.Function):
         x, y, sid, scores, stats, ws, *params = ctx.saved_tensors
         saved = (x, y, params, sid, sid, 0, ctx.mode, ctx.precision, scores, stats, ws)
         gx, gy, gp = HipConcatMlpOps().fdiv_backward(saved, _grad_scalar(grad_loss))
-        return (gx, gy, *gp, None, None, None)
-
-
-def _fused_fdiv(x, y, study_id, critic, estimator, precision, return_scores, return_stats):
-    """fused_mi_bound for "jsd" / "nwj" (every critic)."""
-    if critic is None:
-        raise TypeError("critic must be a make_mlp critic, a BilinearCritic or a SeparableCritic")
-    sid = _batch_codes(x, y, study_id)
-    kind, params, prec = resolve_critic(critic, precision, x.shape[0], x.shape[1], y.shape[1])
-    mode = FDIV_ESTIMATORS[estimator]
-    scores = None
-    if kind == "concat_mlp":
-        w1, b1, w2, b2, w3, b3 = params
-        loss, terms, scores = FdivConcatMlpFn.apply(x, y, w1, b1, w2, b2, w3.reshape(-1), b3, sid, mode, prec)
-    else:
-        # "f32": bf16x3 on the bilinear critic where every size is a multiple of 8, exact fp32 products otherwise (the
-        # library rejects fp8 / f16 / f16x3 for these critics)
-        need_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, *params))
-        fn = FdivBilinearFn if kind == "bilinear" else FdivSeparableFn
-        loss, terms = fn.apply(x, y, *params, sid, mode, prec, need_grad)
-        if return_scores:  # diagnostic output: no gradient flows through it
-            with torch.no_grad():
-                a, c, w = (x, y, critic.weight) if kind == "bilinear" else (critic.project_img(x), critic.project_txt(y), None)
-                scores = BilinearCriticFn.apply(a, c, w, sid, _hip.MI_DV, prec, True)[2]
-    out = [loss.reshape(())]
-    if return_scores:
-        out.append(scores)
-    if return_stats:
-        out.append((terms[0], terms[1]))
-    return out[0] if len(out) == 1 else tuple(out)
+        return (None,) * 3 + (gx, gy, *gp)
 
 
 def _batch_codes(embedding_img, embedding_txt, study_id) -> torch.Tensor:
@@ -508,33 +251,16 @@ def _batch_codes(embedding_img, embedding_txt, study_id) -> torch.Tensor:
     return sid
 
 
-def _fused_nce(x, y, study_id, critic, estimator, precision, return_scores, return_stats):
-    """fused_mi_bound for "infonce_rowwise" / "infonce_symmetric"."""
+def _critic_kind(critic):
+    """The critic kind a critic is checked as: anything but a BilinearCritic or a SeparableCritic -- None included, which
+    fused_mi_bound then rejects for the estimators of every critic -- is taken for a make_mlp critic (resolve_critic then
+    checks that it is one)."""
     from . import model as _model
-
-    if not isinstance(critic, (_model.BilinearCritic, _model.SeparableCritic)):
-        raise ValueError(f"mi_estimator {estimator!r} is implemented for BilinearCritic and SeparableCritic only; for "
-                         "scores you compute yourself (e.g. a make_mlp critic applied to every pair) use "
-                         "matrix_bound_loss(scores, study_id, estimator)")
-    sid = _batch_codes(x, y, study_id)
-    # "f32": bf16x3 on the bilinear critic where every size is a multiple of 8, exact fp32 products otherwise (the library
-    # rejects fp8 / f16 / f16x3 for this loss)
-    kind, params, prec = resolve_critic(critic, precision, x.shape[0], x.shape[1], y.shape[1])
-    need_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, *params))
-    fn = NceBilinearFn if kind == "bilinear" else NceSeparableFn
-    loss, r, c = fn.apply(x, y, *params, sid, NCE_ESTIMATORS[estimator], prec, need_grad)
-    out = [loss.reshape(())]
-    if return_scores:  # diagnostic output, as for the reference's estimators: no gradient flows through it
-        with torch.no_grad():
-            if kind == "bilinear":
-                s = BilinearCriticFn.apply(x, y, critic.weight, sid, _hip.MI_DV, prec, True)[2]
-            else:
-                s = BilinearCriticFn.apply(critic.project_img(x), critic.project_txt(y), None, sid, _hip.MI_DV, prec,
-                                           True)[2]
-        out.append(s)
-    if return_stats:
-        out.append((r, c))
-    return out[0] if len(out) == 1 else tuple(out)
+    if isinstance(critic, _model.BilinearCritic):
+        return "bilinear"
+    if isinstance(critic, _model.SeparableCritic):
+        return "separable"
+    return "concat_mlp"
 
 
 def fused_mi_bound(embedding_img: torch.Tensor, embedding_txt: torch.Tensor, study_id, critic, estimator: str = "dv",
@@ -575,36 +301,37 @@ def fused_mi_bound(embedding_img: torch.Tensor, embedding_txt: torch.Tensor, stu
         embedding_img = embedding_img.float()
     if embedding_txt.dtype == torch.float64:
         embedding_txt = embedding_txt.float()
-    if estimator in FDIV_ESTIMATORS:
-        return _fused_fdiv(embedding_img, embedding_txt, study_id, critic, estimator, precision, return_scores,
-                           return_stats)
-    if estimator in NCE_ESTIMATORS:
-        return _fused_nce(embedding_img, embedding_txt, study_id, critic, estimator, precision, return_scores, return_stats)
-    code = _estimator_code(estimator)
+    x, y = embedding_img, embedding_txt
+    est = check_estimator(estimator, _critic_kind(critic))
     if critic is None:
         raise TypeError("critic must be a make_mlp critic, a BilinearCritic or a SeparableCritic")
-    sid = _batch_codes(embedding_img, embedding_txt, study_id)
-    kind, params, prec = resolve_critic(critic, precision, embedding_img.shape[0], embedding_img.shape[1],
-                                        embedding_txt.shape[1])
-    if prec in (_hip.MI_PREC_BF16X3, _hip.MI_PREC_FP8) and kind != "bilinear":
-        raise ValueError(f'precision="{precision}" is implemented for BilinearCritic only')
-    if prec in (_hip.MI_PREC_F16, _hip.MI_PREC_F16X3) and kind != "concat_mlp":
-        raise ValueError(f'precision="{precision}" is the fp16-operand mode of the make_mlp critic (its generated operand '
-                         'relu(U_i + V_j) is formed by packed fp16 arithmetic); use "bf16" for this critic')
-    if kind == "bilinear":
-        loss, stats, scores = BilinearCriticFn.apply(embedding_img, embedding_txt, *params, sid, code, prec,
-                                                     bool(return_scores))
-    elif kind == "separable" and return_scores:  # per-pair scores are a diagnostic output: eager projections + the
-        a, c = critic.project_img(embedding_img), critic.project_txt(embedding_txt)
-        loss, stats, scores = BilinearCriticFn.apply(a, c, None, sid, code, prec, True)  # bilinear form with W = None
-    elif kind == "separable":
-        loss, stats, scores = SeparableCriticFn.apply(embedding_img, embedding_txt, *params, sid, code, prec)
+    sid = _batch_codes(x, y, study_id)
+    kind, params, prec = resolve_critic(critic, precision, x.shape[0], x.shape[1], y.shape[1])
+    scores = None
+    if est.family == "dv":
+        if prec in (_hip.MI_PREC_BF16X3, _hip.MI_PREC_FP8) and kind != "bilinear":
+            raise ValueError(f'precision="{precision}" is implemented for BilinearCritic only')
+        if prec in (_hip.MI_PREC_F16, _hip.MI_PREC_F16X3) and kind != "concat_mlp":
+            raise ValueError(f'precision="{precision}" is the fp16-operand mode of the make_mlp critic (its generated '
+                             'operand relu(U_i + V_j) is formed by packed fp16 arithmetic); use "bf16" for this critic')
+        if kind == "separable" and return_scores:  # per-pair scores are a diagnostic output: eager projections + the
+            kind, x, y, params = "bilinear", critic.project_img(x), critic.project_txt(y), []  # bilinear form, W = None
+        loss, stats, scores = _CriticFn.apply(kind, sid, est.code, prec, bool(return_scores), x, y, *params)
+    elif kind == "concat_mlp":
+        loss, terms, scores = _FdivConcatFn.apply(sid, est.code, prec, x, y, *params)
+        stats = (terms[0], terms[1])
     else:
-        w1, b1, w2, b2, w3, b3 = params
-        loss, stats, scores = ConcatMlpCriticFn.apply(embedding_img, embedding_txt, w1, b1, w2, b2, w3.reshape(-1), b3,
-                                                      sid, code, prec, bool(return_scores))
-    loss = loss if estimator == "dv" else loss.reshape(())
-    out = [loss]
+        # "f32": bf16x3 on the bilinear critic where every size is a multiple of 8, exact fp32 products otherwise (the
+        # library rejects fp8 / f16 / f16x3 for these critics)
+        need_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, *params))
+        loss, a, b = _ChainFn.apply(kind, est.chain_entry, sid, est.code, prec, need_grad, x, y, *params)
+        stats = (a, b) if b is not None else (a[0], a[1])
+        if return_scores:  # diagnostic output: no gradient flows through it
+            with torch.no_grad():
+                a, c, w = ((x, y, [critic.weight]) if kind == "bilinear" else
+                           (critic.project_img(x), critic.project_txt(y), []))  # the projections, as for "dv"
+                scores = _CriticFn.apply("bilinear", sid, _hip.MI_DV, prec, True, a, c, *w)[2]
+    out = [est.shape_loss(loss)]
     if return_scores:
         out.append(scores)
     if return_stats:

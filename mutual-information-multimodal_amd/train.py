@@ -7,6 +7,7 @@ import os
 import torch
 
 from multi_modal import train_mutual_information
+from mutual_info_img_txt._hip import check_estimator
 
 
 def construct_training_parameters(argv=None):
@@ -32,16 +33,9 @@ def construct_training_parameters(argv=None):
     return p.parse_args(argv)
 
 
-MI_ESTIMATORS = ('dv', 'infonce', 'infonce_rowwise', 'infonce_symmetric', 'jsd', 'nwj')  # jsd / nwj: every critic
-PER_SAMPLE_ESTIMATORS = ('infonce_rowwise', 'infonce_symmetric')  # per-sample InfoNCE: bilinear / separable critics only
-
-
 def check_training_parameters(args):
     """Eager validation of the flags that the reference only trips over inside the training step."""
-    if args.mi_estimator not in MI_ESTIMATORS:
-        raise ValueError(f"unknown --mi_estimator {args.mi_estimator!r}: expected one of {MI_ESTIMATORS}")
-    if args.mi_estimator in PER_SAMPLE_ESTIMATORS and args.critic == 'concat_mlp':
-        raise ValueError(f"--mi_estimator {args.mi_estimator} needs --critic bilinear or --critic separable")
+    check_estimator(args.mi_estimator, args.critic)
     return args
 
 
