@@ -1346,6 +1346,11 @@ extern "C" int mi_debug_set_stamps(void* buf) {
   mi::g_stamp_buf = (unsigned long long*)buf;
   return 0;
 }
+// ... and their wall-clock stamps (mi_common.h, WallScope): 4 launches x kWallMaxWg workgroups x 2 x 2 words; null: off
+extern "C" int mi_debug_set_wall(void* buf) {
+  unsigned long long* p = (unsigned long long*)buf;
+  return hipMemcpyToSymbol(HIP_SYMBOL(mi::g_wall), &p, sizeof(p)) == hipSuccess ? 0 : -1;
+}
 #endif
 
 // ================================================================================================ the G-materialising chain

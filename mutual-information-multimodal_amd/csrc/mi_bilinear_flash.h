@@ -489,6 +489,7 @@ __global__ __launch_bounds__(256, 1) void bilinear_flash_kernel(FlashArgs args) 
   const int64_t m_wave = (int64_t)rb * kFlRows + wave * 32;  // first stationary row of this wave
   const bool wave_active = m_wave < P.m;                      // P.m % 32 == 0: a wave is all in or all out
   const int64_t gi = wave_active ? m_wave + r32 : r32;  // an idle wave re-reads rows 0..31; its outputs are dropped
+  MI_WALL_SCOPE(kWallFlash);
   MI_FL_STAMP(0);
 
   // ---- stationary rows as B fragments: lane (n = r32, half) holds Q[gi][16 kk + 8 half .. + 7].  Issued first: these
@@ -955,7 +956,7 @@ __global__ __launch_bounds__(256, 1) void bilinear_flash_kernel(FlashArgs args) 
   }
   MI_FL_STAMP(9);
 
-  // ---- records and partial sums
+  // ---- records and partial sums: seam stores (kSeam_FLASH, mi_common.h) -- the tail launch reads them, nobody here does
   // (the clamped pieces of the last iterations may still be in flight: nobody reads them, and s_endpgm waits for every
   // counter before the workgroup's LDS is released)
   fl_v_opaque(lsum);
@@ -964,7 +965,7 @@ __global__ __launch_bounds__(256, 1) void bilinear_flash_kernel(FlashArgs args) 
   if (lane == 0) {
     Partial rec{mref, lsum, pos, cnt};
     if (!wave_active) rec = Partial{MI_NEG_INF, 0.0f, 0.0f, 0u};
-    P.rec[((int64_t)split * P.n_rb + rb) * 4 + wave] = rec;
+    seam_store<kSeam_FLASH>(&P.rec[((int64_t)split * P.n_rb + rb) * 4 + wave], rec);
   }
   if constexpr (GRAD) {
     fl_mfma_drain_all();
@@ -986,7 +987,7 @@ __global__ __launch_bounds__(256, 1) void bilinear_flash_kernel(FlashArgs args) 
       const float up = __uint_as_float((unsigned)(127 + k) << 23), down = __uint_as_float((unsigned)(127 - k) << 23);
       f16_t* slab16 = reinterpret_cast<f16_t*>(P.slab);
       float* unscale = reinterpret_cast<float*>(slab16 + (int64_t)P.n_split * P.n_rb * 4 * (32 * D));
-      if (lane == 0) unscale[wv] = down;
+      if (lane == 0) seam_store<kSeam_FLASH>(&unscale[wv], down);
       f16_t* dst = slab16 + wv * (32 * D) + lane * 8;
 #pragma unroll
       for (int c = 0; c < C::NT; ++c)
@@ -995,7 +996,7 @@ __global__ __launch_bounds__(256, 1) void bilinear_flash_kernel(FlashArgs args) 
           f16x8 h;
 #pragma unroll
           for (int e = 0; e < 8; ++e) h[e] = (f16_t)(o[c][8 * gp + e] * up);
-          *reinterpret_cast<f16x8*>(dst + c * 1024 + gp * 512) = h;
+          seam_store<kSeam_FLASH>(reinterpret_cast<f16x8*>(dst + c * 1024 + gp * 512), h);
         }
     } else if (wave_active) {
       float* dst = P.slab + wv * (32 * D) + lane * 4;
@@ -1004,7 +1005,7 @@ __global__ __launch_bounds__(256, 1) void bilinear_flash_kernel(FlashArgs args) 
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const f32x4 v = {o[c][4 * g], o[c][4 * g + 1], o[c][4 * g + 2], o[c][4 * g + 3]};
-          *reinterpret_cast<f32x4*>(dst + c * 1024 + g * 256) = v;
+          seam_store<kSeam_FLASH>(reinterpret_cast<f32x4*>(dst + c * 1024 + g * 256), v);
         }
     }
   }

@@ -48,6 +48,9 @@ struct FlashTailArgs {
   bf16_t* dtt_frag1;
 };
 
+#ifndef MI_TAIL_REC_FIRST
+#define MI_TAIL_REC_FIRST 1
+#endif
 constexpr int kTailPad = 4;  // floats of padding per LDS row: 16-byte row reads conflict-free, column reads too
 constexpr int kTailThreads = 512;  // eight waves: the grid is one workgroup per CU, so the loads a CU keeps in flight are
                                    // this workgroup's; every slab load of the block is issued before the first use
@@ -57,6 +60,7 @@ constexpr int kTailThreads = 512;  // eight waves: the grid is one workgroup per
 template <int D, bool F16, bool MERGE, bool GBF = false>
 __global__ __launch_bounds__(kTailThreads, 2) void flash_tail_kernel(FlashTailArgs args) {
   kernarg_prefetch<(int)sizeof(FlashTailArgs)>();
+  MI_WALL_SCOPE(kWallTail);
   extern __shared__ __attribute__((aligned(16))) char smem_tail[];
   float(*tile)[D + kTailPad] = reinterpret_cast<float(*)[D + kTailPad]>(smem_tail);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (scalar: see bilinear_dw_kernel)
@@ -71,11 +75,39 @@ __global__ __launch_bounds__(kTailThreads, 2) void flash_tail_kernel(FlashTailAr
   const float* unscale = reinterpret_cast<const float*>(slab16 + (int64_t)J.n_split * J.n_rb * 4 * (32 * D));
   constexpr int NC = D / 128;  // 128-column chunks: 4096 elements of a wave's slab each
 
-  // ---- every slab load of the first four splits goes out before anything else (the record merge below runs under
-  // their latency).  Element index inside a chunk: thread t holds 8 (fp16) / 2 x 4 (fp32) consecutive elements.
   int64_t wvs[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) wvs[q] = ((int64_t)(q < J.n_split ? q : J.n_split - 1) * J.n_rb + rb) * 4 + w;
+
+  // ---- MERGE: the first two records of each merging thread (all of them up to n_merge = 512: the headline has 512) and
+  // the splits' reference points and scales go out FIRST.  Vector loads return in issue order, so behind the 128 KB of
+  // slab loads the merge's first record would wait for every slab byte; in front of them the merge chain (records ->
+  // wave reductions -> barrier -> thread 0 -> barrier) runs under the slabs' latency.
+  // (build-time A/B switch -DMI_TAIL_REC_FIRST=0: the same loads behind the slab loads)
+  Partial pre[2];
+  float m_rec[4], u_rec[4], go_pre;
+  auto load_heads = [&]() __attribute__((always_inline)) {
+    if constexpr (MERGE) {
+      // (unconditional loads of a clamped index, in all eight waves: a load under a condition makes hipcc wait for it --
+      // and for every load issued before it -- at the end of the conditional block; n_merge >= 1)
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int64_t k = tid + 256 * u;
+        pre[u] = args.merge_rec[k < args.n_merge ? k : args.n_merge - 1];
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      m_rec[q] = J.rec[wvs[q]].m;
+      u_rec[q] = F16 ? unscale[wvs[q]] : 1.0f;
+    }
+    // dL/dloss too (behind the merge it was one more dependent round trip); null: any valid word, replaced by 1 below
+    go_pre = *(args.grad_out ? args.grad_out : &J.rec[wvs[0]].m);
+  };
+  if constexpr (MI_TAIL_REC_FIRST) load_heads();
+
+  // ---- every slab load of the first four splits goes out before anything is used.  Element index inside a chunk:
+  // thread t holds 8 (fp16) / 2 x 4 (fp32) consecutive elements.
   f16x8 vh[NC][4];
   f32x4 vf[NC][4][2];
 #pragma unroll
@@ -91,24 +123,19 @@ __global__ __launch_bounds__(kTailThreads, 2) void flash_tail_kernel(FlashTailAr
       }
     }
 
-  // ... and so does everything else this workgroup reads that does not depend on the statistics: the splits' reference
-  // points and scales, and the rows subtracted on the diagonal.  (A block moves ~200 KB; what it costs is the chain of
-  // DEPENDENT round trips to memory, each 1 - 2 us under load.)
-  float m_rec[4], u_rec[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    m_rec[q] = J.rec[wvs[q]].m;
-    u_rec[q] = F16 ? unscale[wvs[q]] : 1.0f;
-  }
+  if constexpr (!MI_TAIL_REC_FIRST) load_heads();
+
+  // ... and so do the rows subtracted on the diagonal: nothing this workgroup reads depends on the statistics.  (A block
+  // moves ~200 KB; what it costs is the chain of DEPENDENT round trips to memory, each 1 - 2 us under load.)
   const int orow = tid >> 4;  // row-major pass below: 16 threads per row, each D / 128 groups of 8 columns
   const int64_t ojo = i0 + orow + J.diag;
   const bool has_other = ojo >= 0 && ojo < J.n_other;
+  // (loaded unconditionally from a clamped row and used under has_other only: as a conditional load it made every wave
+  // wait for ALL its slab loads right here, in front of the record merge; n_other >= 1)
+  const int64_t ojc = has_other ? ojo : 0;
   bf16x8 oth[D / 128];
 #pragma unroll
-  for (int g = 0; g < D / 128; ++g) {
-    oth[g] = bf16x8{};
-    if (has_other) oth[g] = *reinterpret_cast<const bf16x8*>(J.other + ojo * D + ((tid & 15) + 16 * g) * 8);
-  }
+  for (int g = 0; g < D / 128; ++g) oth[g] = *reinterpret_cast<const bf16x8*>(J.other + ojc * D + ((tid & 15) + 16 * g) * 8);
 
   // ---- statistics
   float lse, n_pos_f;
@@ -124,7 +151,14 @@ __global__ __launch_bounds__(kTailThreads, 2) void flash_tail_kernel(FlashTailAr
     if (wave < 4) {
       Partial p{MI_NEG_INF, 0.0f, 0.0f, 0u};
       unsigned long long cnt = 0;
-      for (int64_t k = tid; k < args.n_merge; k += 256) {
+#pragma unroll
+      for (int u = 0; u < 2; ++u)  // (loaded above; same order as the loop below continues)
+        if (tid + 256 * u < args.n_merge) {
+          lse_merge(p.m, p.s, pre[u].m, pre[u].s);
+          p.pos += pre[u].pos;
+          cnt += pre[u].cnt;
+        }
+      for (int64_t k = tid + 512; k < args.n_merge; k += 256) {
         const Partial q = args.merge_rec[k];
         lse_merge(p.m, p.s, q.m, q.s);
         p.pos += q.pos;
@@ -174,7 +208,7 @@ __global__ __launch_bounds__(kTailThreads, 2) void flash_tail_kernel(FlashTailAr
     lse = args.stats->lse;
     n_pos_f = (float)args.stats->n_pos;
   }
-  const float go = args.grad_out ? args.grad_out[0] : 1.0f;
+  const float go = args.grad_out ? go_pre : 1.0f;
   const float gpos = go / n_pos_f;
 
   // ---- add the splits (split order) into the LDS tile [32][D]
@@ -281,11 +315,11 @@ __global__ __launch_bounds__(kTailThreads, 2) void flash_tail_kernel(FlashTailAr
         if (J.out_bf) {
           const bf16x8 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3],
                             (bf16_t)v[4], (bf16_t)v[5], (bf16_t)v[6], (bf16_t)v[7]};
-          *reinterpret_cast<bf16x8*>(J.out_bf + i * D + c) = o;
+          seam_store<kSeam_TAIL_GRAD>(reinterpret_cast<bf16x8*>(J.out_bf + i * D + c), o);
         }
       } else if (J.out_f32) {
-        *reinterpret_cast<f32x4*>(J.out_f32 + i * D + c) = f32x4{v[0], v[1], v[2], v[3]};
-        *reinterpret_cast<f32x4*>(J.out_f32 + i * D + c + 4) = f32x4{v[4], v[5], v[6], v[7]};
+        seam_store<kSeam_TAIL_GRAD>(reinterpret_cast<f32x4*>(J.out_f32 + i * D + c), f32x4{v[0], v[1], v[2], v[3]});
+        seam_store<kSeam_TAIL_GRAD>(reinterpret_cast<f32x4*>(J.out_f32 + i * D + c + 4), f32x4{v[4], v[5], v[6], v[7]});
       }
     }
   }
@@ -334,7 +368,7 @@ __global__ __launch_bounds__(kTailThreads, 2) void flash_tail_kernel(FlashTailAr
       bf16x8 o;
 #pragma unroll
       for (int jj = 0; jj < 8; ++jj) o[jj] = (bf16_t)tile[16 * kl + 8 * h + jj][32 * cb + r];
-      *reinterpret_cast<bf16x8*>(dtt_out + (((int64_t)cb * nkb + (i0 / 16 + kl)) * 64 + lane) * 8) = o;
+      seam_store<kSeam_TAIL_DTT>(reinterpret_cast<bf16x8*>(dtt_out + (((int64_t)cb * nkb + (i0 / 16 + kl)) * 64 + lane) * 8), o);
     }
   }
 
@@ -377,8 +411,8 @@ __global__ __launch_bounds__(kTailThreads, 2) void flash_tail_kernel(FlashTailAr
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int64_t o = (i0 + 8 * g + 4 * h + e) * dx_out + (at0 + t) * 32 + r;
-          if constexpr (GBF) args.grad_x_bf[o] = (bf16_t)acc[t][4 * g + e];
-          else gx_out[o] = acc[t][4 * g + e];
+          if constexpr (GBF) seam_store<kSeam_TAIL_GRAD>(&args.grad_x_bf[o], (bf16_t)acc[t][4 * g + e]);
+          else seam_store<kSeam_TAIL_GRAD>(&gx_out[o], acc[t][4 * g + e]);
         }
     }
   }
@@ -399,6 +433,16 @@ static inline int launch_flash_tail_t(const FlashTailArgs& a, unsigned grid, hip
 // job 0 blocks first; a.n_blocks0 is set here
 static inline int launch_flash_tail(FlashTailArgs a, int64_t d, bool slab_f16, bool merge, hipStream_t st, const char* what) {
   a.n_blocks0 = (int)(a.j[0].m / 32);
+  // the kernel loads its diagonal rows and its first records from clamped indices without a test
+  for (int k = 0; k < 2; ++k)
+    if (a.j[k].m > 0 && (a.j[k].n_other < 1 || a.j[k].other == nullptr)) {
+      set_error("launch_flash_tail: job %d has no rows to subtract on the diagonal", k);
+      return MI_EINVAL;
+    }
+  if (merge && (a.n_merge < 1 || a.merge_rec == nullptr)) {
+    set_error("launch_flash_tail: the merged form needs at least one record");
+    return MI_EINVAL;
+  }
   const unsigned grid = (unsigned)(a.n_blocks0 + a.j[1].m / 32);
 #define MI_TAIL_CASE(DD)                                                                          \
   if (d == DD) {                                                                                  \
@@ -439,17 +483,28 @@ constexpr int kDwWaves = 8;  // the batch dimension is split over the waves of a
 struct DwArgs2 {
   DwArgs p[2];
   int n_tiles0;  // workgroups of problem 0 (they come first)
+  int natural;   // A/B switch (MI_DW_XCD_NATURAL=1): tiles in row-major order over the grid, as before the XCD blocks
 };
 static __global__ __launch_bounds__(64 * kDwWaves, 1) void bilinear_dw_kernel(DwArgs2 a2) {
   __shared__ float part[kDwWaves - 1][32][33];
+  MI_WALL_SCOPE(kWallDw);
   const int prob = (int)blockIdx.x >= a2.n_tiles0 ? 1 : 0;
   const DwArgs& a = a2.p[prob];
   const int64_t tile_id = prob ? (int64_t)blockIdx.x - a2.n_tiles0 : (int64_t)blockIdx.x;
   // (readfirstlane: the wave index must be a SCALAR for hipcc -- an MFMA ignores EXEC, so a matrix instruction under a
   // condition hipcc takes for divergent, and lowers to an EXEC mask without a skip branch, would still execute)
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int64_t nct = a.dy / 32;
-  const int64_t at = tile_id / nct, ct = tile_id % nct;
+  const int64_t nct = a.dy / 32, nat = a.dx / 32;
+  int64_t at = tile_id / nct, ct = tile_id % nct;
+  // Workgroups go to the 8 XCDs round-robin (mi_common.h, xcd_decode): in row-major order XCD x gets tile columns
+  // {x, x + 8, ...} of EVERY row, so each private L2 pulls all of X^T.  Give XCD x one (nat / 4) x (nct / 2) block of
+  // tiles instead -- 4 x 8 at d = 512: a quarter of X^T and half of dT^T per XCD.  Which workgroup computes which tile
+  // changes, the tile's arithmetic does not.  (A problem must start at a multiple of 8 for b % 8 to be its XCD.)
+  if (!a2.natural && nat % 4 == 0 && nct % 2 == 0 && (prob == 0 || a2.n_tiles0 % 8 == 0)) {
+    const int64_t xcd = tile_id & 7, i = tile_id >> 3, br = nat / 4, bc = nct / 2;
+    at = br * (xcd >> 1) + i / bc;
+    ct = bc * (xcd & 1) + i % bc;
+  }
   const int64_t nkb = a.k / 16;                 // 16-deep blocks over the batch
   const int64_t kb0 = nkb * wave / kDwWaves, kb1 = nkb * (wave + 1) / kDwWaves;
   const bf16_t* ap = a.xt_frag + ((at * nkb + kb0) * 64 + lane) * 8;
@@ -495,7 +550,7 @@ static __global__ __launch_bounds__(64 * kDwWaves, 1) void bilinear_dw_kernel(Dw
         float v = acc[4 * g + e];
 #pragma unroll
         for (int k = 0; k < kDwWaves - 1; ++k) v += part[k][row][r];  // wave order: bit-reproducible
-        a.out[(at * 32 + row) * a.dy + ct * 32 + r] = v;
+        seam_store<kSeam_DW>(&a.out[(at * 32 + row) * a.dy + ct * 32 + r], v);
       }
   }
 }
@@ -506,6 +561,8 @@ static inline int launch_bilinear_dw(const DwArgs& a, hipStream_t st, const char
   a2.p[0] = a;
   a2.p[1] = b ? *b : a;
   a2.n_tiles0 = (int)((a.dx / 32) * (a.dy / 32));
+  static const int natural = getenv("MI_DW_XCD_NATURAL") ? 1 : 0;  // A/B switch
+  a2.natural = natural;
   const unsigned grid = (unsigned)(a2.n_tiles0 + (b ? (b->dx / 32) * (b->dy / 32) : 0));
   {
     ProfScope prof_(what, st);

@@ -106,7 +106,100 @@ typedef short s16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// ------------------------------------------------------------------------------------------------ seam stores
+// Cache policy of the stores that cross a kernel boundary of the fused bilinear step (prep -> fused kernel -> tail -> dW).
+// A plain store leaves its line dirty in the XCD's L2; the write-back happens when the kernel ends and the next launch
+// waits for it.  kSeamNT (`global_store_* ... nt`) marks the line as streaming; kSeamWT (`... sc0 sc1`) writes it through
+// while the kernel still runs.  The policy is a compile-time argument: no branch in any kernel.
+//
+// The write-through form is inline asm (no builtin emits a 16-byte sc0 sc1 store).  hipcc does not count it in vmcnt:
+// use it only for data that the storing kernel never reads back (s_endpgm waits for every outstanding store).  And its
+// hazard recognizer does not see the store either: a VALU write to the data registers of a store wider than 8 bytes needs
+// a wait state behind it, which hipcc inserts for its own stores only -- without the s_nop in the statement the compiler
+// reused the registers at once and the slabs, dT^T and the gradients came out wrong (the first A/B run: bits differed
+// from the plain build).  tests/test_seam_store_isa.py checks that every such store keeps its s_nop.
+enum SeamPolicy { kSeamPlain = 0, kSeamNT = 1, kSeamWT = 2 };
+
+template <int POLICY, typename V>
+__device__ __forceinline__ void seam_store(V* p, const V& v) {
+  static_assert(sizeof(V) == 2 || sizeof(V) == 4 || sizeof(V) == 8 || sizeof(V) == 16, "seam_store: 2 to 16 bytes");
+  if constexpr (POLICY == kSeamPlain) {
+    *p = v;
+  } else if constexpr (sizeof(V) == 16) {
+    const u32x4 b = __builtin_bit_cast(u32x4, v);
+    if constexpr (POLICY == kSeamNT) __builtin_nontemporal_store(b, reinterpret_cast<u32x4*>(p));
+    else asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(b) : "memory");
+  } else if constexpr (sizeof(V) == 8) {
+    const u32x2 b = __builtin_bit_cast(u32x2, v);
+    if constexpr (POLICY == kSeamNT) __builtin_nontemporal_store(b, reinterpret_cast<u32x2*>(p));
+    else asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(b) : "memory");
+  } else if constexpr (sizeof(V) == 4) {
+    const unsigned b = __builtin_bit_cast(unsigned, v);
+    if constexpr (POLICY == kSeamNT) __builtin_nontemporal_store(b, reinterpret_cast<unsigned*>(p));
+    else asm volatile("global_store_dword %0, %1, off sc0 sc1" ::"v"(p), "v"(b) : "memory");
+  } else {
+    const unsigned b = __builtin_bit_cast(unsigned short, v);
+    if constexpr (POLICY == kSeamNT) __builtin_nontemporal_store((unsigned short)b, reinterpret_cast<unsigned short*>(p));
+    else asm volatile("global_store_short %0, %1, off sc0 sc1" ::"v"(p), "v"(b) : "memory");
+  }
+}
+
+// THE table: which policy the stores of each site group carry (tests/test_seam_store_isa.py reads these rows and checks
+// the compiled kernels against them).  X(bit, group, kernel, policy).  Build-time A/B switches (csrc/Makefile):
+// MI_SEAM_OFF = mask of groups compiled with plain stores (make SEAM=plain: all of them), MI_SEAM_ALT = mask of groups
+// compiled with the other non-plain policy (NT <-> WT).
+#define MI_SEAM_TABLE(X)                          \
+  X(0, PREP_TILE, bilinear_prep_t_kernel, WT)     \
+  X(1, PREP_CVT, bilinear_prep_t_kernel, WT)      \
+  X(2, FLASH, bilinear_flash_kernel, WT)          \
+  X(3, TAIL_GRAD, flash_tail_kernel, NT)          \
+  X(4, TAIL_DTT, flash_tail_kernel, WT)           \
+  X(5, DW, bilinear_dw_kernel, NT)
+#ifndef MI_SEAM_OFF
+#define MI_SEAM_OFF 0
+#endif
+#ifndef MI_SEAM_ALT
+#define MI_SEAM_ALT 0
+#endif
+constexpr int seam_pick(int bit, int policy) {
+  return ((MI_SEAM_OFF) >> bit) & 1 ? (int)kSeamPlain
+         : ((MI_SEAM_ALT) >> bit) & 1 ? (policy == kSeamNT ? (int)kSeamWT : (int)kSeamNT)
+                                      : policy;
+}
+#define MI_SEAM_ROW(bit, group, kernel, policy) constexpr int kSeam_##group = seam_pick(bit, kSeam##policy);
+MI_SEAM_TABLE(MI_SEAM_ROW)
+#undef MI_SEAM_ROW
+
+// Diagnostic build only (make STAMPS=1): wall-clock stamps of the four launches of the fused bilinear step, for
+// tools/diag/seam_time.py.  Slot k of workgroup g: (s_memrealtime, s_memtime) when thread 0 enters the kernel and when it
+// leaves it with all its stores acknowledged -- s_memrealtime is the 100 MHz constant clock, s_memtime the shader clock,
+// so the pair also gives the clock a kernel really ran at.  The stamps go to a side buffer only, never into an output.
+#ifdef MI_STAMPS
+constexpr int kWallMaxWg = 8192;  // workgroups stamped per launch
+enum WallKernel { kWallPrep = 0, kWallFlash = 1, kWallTail = 2, kWallDw = 3 };
+static __device__ unsigned long long* g_wall;
+struct WallScope {
+  int k;
+  __device__ __forceinline__ void stamp(int end) const {
+    if (threadIdx.x == 0 && g_wall && blockIdx.x < (unsigned)kWallMaxWg) {
+      unsigned long long* p = g_wall + (((size_t)k * kWallMaxWg + blockIdx.x) * 2 + end) * 2;
+      p[0] = __builtin_amdgcn_s_memrealtime();
+      p[1] = __builtin_amdgcn_s_memtime();
+    }
+  }
+  __device__ __forceinline__ explicit WallScope(int kernel) : k(kernel) { stamp(0); }
+  __device__ __forceinline__ ~WallScope() {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    stamp(1);
+  }
+};
+#define MI_WALL_SCOPE(kernel) ::mi::WallScope mi_wall_scope_(kernel)
+#else
+#define MI_WALL_SCOPE(kernel) do {} while (0)
+#endif
 
 // Partial record of the bound reduction: merged in a fixed order, so results are bit-reproducible.
 struct Partial {

@@ -26,6 +26,9 @@ static unsigned long long* g_stamp_buf = nullptr;
 static inline void stamp_select(const char* what, hipStream_t st) {
   const char* f = getenv("MI_STAMP_KERNEL");
   unsigned long long* p = (g_stamp_buf && f && strstr(what, f)) ? g_stamp_buf : nullptr;
+  static bool dev_set = false;  // no copy between the launches while no stamp buffer was ever selected (seam_time.py)
+  if (!p && !dev_set) return;
+  dev_set = true;
   (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_stamps), &p, sizeof(p), 0, hipMemcpyHostToDevice, st);
 }
 #define MI_STAMP(slot)                                                                                           \
@@ -203,7 +206,8 @@ __device__ __forceinline__ void wave_lds_fence() {
 // and / or transposed into tr[(nb + c) * ld_tr + mb + r] -- through the wave's LDS staging area, so that every global
 // store is a 16-byte chunk of a 128-byte row segment (the direct accumulator-layout stores are 2-byte / strided 8-byte
 // writes).  Needs ld_rm % 8 == 0 (ld_tr % 8 == 0) and 16-byte aligned bases; elements beyond M x N are dropped, which
-// with N % 8 == 0 (M % 8 == 0) happens in whole chunks.
+// with N % 8 == 0 (M % 8 == 0) happens in whole chunks.  SEAM: cache policy of the global stores (seam_store, mi_common.h).
+template <int SEAM = kSeamPlain>
 __device__ __forceinline__ void wave_tile_store_bf16(f32x16 (&acc)[2][2], char* lds, bf16_t* rm, int64_t ld_rm,
                                                      bf16_t* tr, int64_t ld_tr, int64_t mb, int64_t nb, int64_t M,
                                                      int64_t N, bf16_t* frag = nullptr) {
@@ -228,8 +232,8 @@ __device__ __forceinline__ void wave_tile_store_bf16(f32x16 (&acc)[2][2], char* 
       const bf16x8 v = *reinterpret_cast<const bf16x8*>(lds + row_l * kEpiPitch + chunk * 16);
       const int64_t grow = mb + row_l, gcol = nb + chunk * 8;
       if (grow < M && gcol < N) {
-        if (rm) *reinterpret_cast<bf16x8*>(rm + grow * ld_rm + gcol) = v;
-        if (frag) *reinterpret_cast<bf16x8*>(frag + frag_major_offset(grow, gcol, N)) = v;
+        if (rm) seam_store<SEAM>(reinterpret_cast<bf16x8*>(rm + grow * ld_rm + gcol), v);
+        if (frag) seam_store<SEAM>(reinterpret_cast<bf16x8*>(frag + frag_major_offset(grow, gcol, N)), v);
       }
     }
   }
@@ -252,7 +256,7 @@ __device__ __forceinline__ void wave_tile_store_bf16(f32x16 (&acc)[2][2], char* 
       const int c_l = it * 8 + srow;
       const bf16x8 v = *reinterpret_cast<const bf16x8*>(lds + c_l * kEpiPitch + chunk * 16);
       const int64_t gcol = nb + c_l, grow = mb + chunk * 8;
-      if (gcol < N && grow < M) *reinterpret_cast<bf16x8*>(tr + gcol * ld_tr + grow) = v;
+      if (gcol < N && grow < M) seam_store<SEAM>(reinterpret_cast<bf16x8*>(tr + gcol * ld_tr + grow), v);
     }
   }
 }
@@ -1534,7 +1538,9 @@ __device__ __forceinline__ void dup_flags_block(const DupFlagJob& J, int a, int 
   }
 }
 // 64 x 64 tiles, 16-byte loads and 8-byte stores in both orientations (R % 4 == 0 and C % 4 == 0; 16-byte aligned
-// bases): 34 MB move per bilinear forward, ~10 us with 4-byte accesses on 32 x 32 tiles.
+// bases): 34 MB move per bilinear forward, ~10 us with 4-byte accesses on 32 x 32 tiles.  SEAM: cache policy of the
+// stores (seam_store, mi_common.h).
+template <int SEAM = kSeamPlain>
 __device__ __forceinline__ void cvt_tile_block(const CvtJob& J, int bx, int by, float (*tile)[65]) {
   const int64_t r0 = (int64_t)by * 64, c0 = (int64_t)bx * 64;
   if (r0 >= J.R || c0 >= J.C) return;
@@ -1564,18 +1570,18 @@ __device__ __forceinline__ void cvt_tile_block(const CvtJob& J, int bx, int by, 
     for (int e = 0; e < 4; ++e) tile[rl][4 * tx + e] = v[e];
     if ((J.out_rm || J.out_frag) && r < J.R && c < J.C) {
       const bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-      if (J.out_rm && !J.split_rm) *reinterpret_cast<bf16x4*>(J.out_rm + r * J.C + c) = o;
+      if (J.out_rm && !J.split_rm) seam_store<SEAM>(reinterpret_cast<bf16x4*>(J.out_rm + r * J.C + c), o);
       if (J.out_rm && J.split_rm) {
         int64_t h0, h1, lo;
         split3_offsets(J.split_rm, J.C, h0, h1, lo);
         const bf16x4 l = {(bf16_t)bf16_residual(v[0]), (bf16_t)bf16_residual(v[1]), (bf16_t)bf16_residual(v[2]),
                           (bf16_t)bf16_residual(v[3])};
         bf16_t* row = J.out_rm + r * 3 * J.C + c;
-        *reinterpret_cast<bf16x4*>(row + h0) = o;
-        *reinterpret_cast<bf16x4*>(row + h1) = o;
-        *reinterpret_cast<bf16x4*>(row + lo) = l;
+        seam_store<SEAM>(reinterpret_cast<bf16x4*>(row + h0), o);
+        seam_store<SEAM>(reinterpret_cast<bf16x4*>(row + h1), o);
+        seam_store<SEAM>(reinterpret_cast<bf16x4*>(row + lo), l);
       }
-      if (J.out_frag) *reinterpret_cast<bf16x4*>(J.out_frag + frag_major_offset(r, c & ~(int64_t)7, J.C) + (c & 4)) = o;
+      if (J.out_frag) seam_store<SEAM>(reinterpret_cast<bf16x4*>(J.out_frag + frag_major_offset(r, c & ~(int64_t)7, J.C) + (c & 4)), o);
     }
   }
   if (!J.out_t && !J.out_t_frag) return;
@@ -1587,19 +1593,19 @@ __device__ __forceinline__ void cvt_tile_block(const CvtJob& J, int bx, int by, 
     if (c < J.C && r < J.R) {
       const bf16x4 o = {(bf16_t)tile[4 * tx][cl], (bf16_t)tile[4 * tx + 1][cl], (bf16_t)tile[4 * tx + 2][cl],
                         (bf16_t)tile[4 * tx + 3][cl]};
-      if (J.out_t_frag) *reinterpret_cast<bf16x4*>(J.out_t_frag + frag_major_offset(c, r & ~(int64_t)7, J.R) + (r & 4)) = o;
+      if (J.out_t_frag) seam_store<SEAM>(reinterpret_cast<bf16x4*>(J.out_t_frag + frag_major_offset(c, r & ~(int64_t)7, J.R) + (r & 4)), o);
       if (!J.out_t) {
       } else if (!J.split_t) {
-        *reinterpret_cast<bf16x4*>(J.out_t + c * J.R + r) = o;
+        seam_store<SEAM>(reinterpret_cast<bf16x4*>(J.out_t + c * J.R + r), o);
       } else {
         int64_t h0, h1, lo;
         split3_offsets(J.split_t, J.R, h0, h1, lo);
         const bf16x4 l = {(bf16_t)bf16_residual(tile[4 * tx][cl]), (bf16_t)bf16_residual(tile[4 * tx + 1][cl]),
                           (bf16_t)bf16_residual(tile[4 * tx + 2][cl]), (bf16_t)bf16_residual(tile[4 * tx + 3][cl])};
         bf16_t* row = J.out_t + c * 3 * J.R + r;
-        *reinterpret_cast<bf16x4*>(row + h0) = o;
-        *reinterpret_cast<bf16x4*>(row + h1) = o;
-        *reinterpret_cast<bf16x4*>(row + lo) = l;
+        seam_store<SEAM>(reinterpret_cast<bf16x4*>(row + h0), o);
+        seam_store<SEAM>(reinterpret_cast<bf16x4*>(row + h1), o);
+        seam_store<SEAM>(reinterpret_cast<bf16x4*>(row + lo), l);
       }
     }
   }
@@ -1720,6 +1726,7 @@ constexpr size_t kPrepTSmem = (2 * kTile * kG2LD + 2 * kG2KT * kPrepTLdB) * size
 template <bool XB16>
 static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArgs a) {
   kernarg_prefetch<(int)sizeof(PrepTArgs)>();
+  MI_WALL_SCOPE(kWallPrep);
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const int blk = (int)blockIdx.x;
   MI_STAMP(0);
@@ -1735,7 +1742,7 @@ static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArg
     int q = 0;
     while (q < 3 && c >= a.job_begin[q + 1]) ++q;
     const int t = c - a.job_begin[q];
-    cvt_tile_block(a.jobs.j[q], t % a.job_nx[q], t / a.job_nx[q], tile);
+    cvt_tile_block<kSeam_PREP_CVT>(a.jobs.j[q], t % a.job_nx[q], t / a.job_nx[q], tile);
     MI_STAMP(5);
     return;
   }
@@ -1864,7 +1871,7 @@ static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArg
     if (t == 0) MI_STAMP(3);
   }
   MI_STAMP(4);
-  wave_tile_store_bf16(acc, smem_raw + wave * kEpiLdsPerWave, ptb, pn, second ? nullptr : a.ttb, pm, m0 + wm * 64,
+  wave_tile_store_bf16<kSeam_PREP_TILE>(acc, smem_raw + wave * kEpiLdsPerWave, ptb, pn, second ? nullptr : a.ttb, pm, m0 + wm * 64,
                        n0 + wn * 64, pm, pn, ptfb);
   MI_STAMP(5);
 }
