@@ -23,6 +23,58 @@
 
 namespace mi {
 
+// The fused B x B stage (mi_bilinear_flash.h) of a critic with scores S = Q K^T -- T Y^T for the bilinear critic, A C^T
+// for the separable one: scores, masked log-sum-exp records and (grad) the unnormalised sums of both gradient
+// contractions.  Problem 0 sweeps the b rows of K for every local row of Q; problem 1 is problem 0 with operands, ids and
+// the sign of row_offset swapped.  That convention is written here and nowhere else.
+struct ReduceOut {
+  float* f32;      // [m][d] or null
+  bf16_t* bf;      // [m][d] or null
+  bf16_t* bf_t;    // [d][m] or null
+};
+struct FusedStage {
+  FlashPlan fl;
+  int64_t br, b, d;                  // local rows of Q, rows of K, score width
+  const bf16_t* frag[2];             // stationary operand per problem, fragment-major: Q [br][d], K [b][d]
+  const bf16_t* rows[2];             // streamed operand per problem, row-major: K [b][d], Q [br][d]
+  Partial* rec[2];                   // per-wave records
+  float* slab[2];                    // partial sums
+  unsigned char* dup[2];             // equal-id flags per 32 x 32 block: [br / 32][b / 32] and its transpose
+  const char *what_grad, *what_fwd;  // launch labels with and without the gradient sums
+
+  int64_t m(int q) const { return q ? b : br; }
+  // records, slabs and flags of both problems (nothing where the shape does not take the fused kernel)
+  void take(Workspace& ws) {
+    for (int q = 0; q < 2 && fl.ok; ++q) {
+      rec[q] = ws.take<Partial>(fl.n_rec[q]);
+      slab[q] = ws.take<float>((fl.slab_bytes[q] + 3) / 4);
+      dup[q] = ws.take<unsigned char>((br / 32) * (b / 32));
+    }
+  }
+  // the flags ride along with a conversion launch
+  DupFlagJob dup_job(const int64_t* sid_rows, const int64_t* sid_cols, int64_t row_offset) const {
+    return DupFlagJob{sid_rows, sid_cols, (int)(br / 32), (int)(b / 32), dup[0], dup[1], row_offset};
+  }
+  int launch(const int64_t* sid_rows, const int64_t* sid_cols, int64_t row_offset, bool grad, hipStream_t st) const {
+    const int64_t* sid[2] = {sid_rows, sid_cols};
+    FlashArgs a{};
+    for (int q = 0; q < 2; ++q)
+      a.p[q] = FlashProblem{frag[q], rows[q], sid[q], sid[1 - q], m(q), m(1 - q), q ? -row_offset : row_offset, fl.n_rb[q],
+                            fl.n_split[q], fl.tiles_per_split[q], dup[q], slab[q], rec[q]};
+    a.n_problems = grad ? 2 : 1;
+    a.slab_f16 = fl.slab_f16 ? 1 : 0;
+    return launch_flash(a, d, grad, st, grad ? what_grad : what_fwd);
+  }
+  // the two jobs that turn the launch's sums into gradient rows: job q scales the slabs of problem q, subtracts the
+  // diagonal term (a row of the problem's streamed operand) and writes to out[q]
+  void reduce_jobs(FlashReduceJob* j, int64_t row_offset, const ReduceOut& out0, const ReduceOut& out1) const {
+    const ReduceOut* out[2] = {&out0, &out1};
+    for (int q = 0; q < 2; ++q)
+      j[q] = FlashReduceJob{slab[q], rec[q], fl.n_split[q], fl.n_rb[q], m(q), rows[q], m(1 - q),
+                            q ? -row_offset : row_offset, out[q]->f32, out[q]->bf, out[q]->bf_t};
+  }
+};
+
 struct BilinearPlan {
   // generic path
   float* t;
@@ -39,11 +91,8 @@ struct BilinearPlan {
   float* dt_slab;
   int dt_splits;
   int64_t dt_kchunk;
-  // fused B x B stage (mi_bilinear_flash.h): partial sums and per-wave records of the two problems
-  FlashPlan fl;
-  float* fl_slab[2];
-  Partial* fl_rec[2];
-  unsigned char* fl_dup[2];  // equal-id flags per 32 x 32 block: [br / 32][b / 32] and its transpose
+  // fused B x B stage on S = T Y^T
+  FusedStage stage;
   bf16_t *tfb, *yfb;         // fragment-major copies of T and Y: the stationary operands of the fused kernel
   // the backward's tail (mi_bilinear_tail.h): fragment-major W (B operand of dX = dT W^T), X^T and dT^T (operands of dW)
   bool tail;
@@ -58,6 +107,8 @@ struct BilinearPlan {
   // exact-fp32 path (MI_PREC_F32): split-K slabs of the products whose output has too few 128 x 128 tiles to fill the chip
   float* gen_slab;
   int64_t gen_slab_floats;
+  // which kernels the shape takes (MI_PATH_*), or MI_ESHAPE for an fp8 call outside the fp8 kernels' shapes
+  int path;
   size_t bytes;
 };
 
@@ -87,8 +138,9 @@ static bool fast_ok(int64_t br, int64_t b, int64_t dx, int64_t dy, int precision
          dx % 8 == 0 && dy % 8 == 0;
 }
 
-// gemms_only: no fused B x B stage (the per-sample InfoNCE runs the G-materialising chain, mi_nce.h)
-static BilinearPlan plan_bilinear(Workspace& ws, int64_t br, int64_t b, int64_t dx, int64_t dy, int precision,
+// has_w: the call has a weight matrix (w == NULL, S = X Y^T, runs the generic kernels); it decides the path only, never
+// the layout.  gemms_only: no fused B x B stage (the per-sample InfoNCE runs the G-materialising chain, mi_nce.h)
+static BilinearPlan plan_bilinear(Workspace& ws, int64_t br, int64_t b, int64_t dx, int64_t dy, int precision, bool has_w,
                                   bool gemms_only = false) {
   BilinearPlan p{};
   p.n_partials = ((b + kTile - 1) / kTile) * ((br + kTile - 1) / kTile);
@@ -112,17 +164,21 @@ static BilinearPlan plan_bilinear(Workspace& ws, int64_t br, int64_t b, int64_t 
     p.qt8 = ws.take<fp8_t>(br * dy);
     p.f8sc = ws.take<Fp8Scales>(1);
   }
-  p.fl = FlashPlan{};
-  if (precision == MI_PREC_BF16 && br % 8 == 0 && b % 8 == 0 && dx % 8 == 0 && !gemms_only) p.fl = flash_plan(br, b, dy);
-  for (int q = 0; q < 2; ++q) {
-    p.fl_rec[q] = p.fl.ok ? ws.take<Partial>(p.fl.n_rec[q]) : nullptr;
-    p.fl_slab[q] = p.fl.ok ? ws.take<float>((p.fl.slab_bytes[q] + 3) / 4) : nullptr;
-    p.fl_dup[q] = p.fl.ok ? ws.take<unsigned char>((br / 32) * (b / 32)) : nullptr;
-  }
-  p.tfb = p.fl.ok ? ws.take<bf16_t>(br * dy) : nullptr;
-  p.yfb = p.fl.ok ? ws.take<bf16_t>(b * dy) : nullptr;
+  FusedStage& s = p.stage;
+  if (precision == MI_PREC_BF16 && br % 8 == 0 && b % 8 == 0 && dx % 8 == 0 && !gemms_only) s.fl = flash_plan(br, b, dy);
+  s.br = br, s.b = b, s.d = dy;
+  s.what_grad = "bilinear fused S | P Y | P^T T", s.what_fwd = "bilinear fused S + LSE";
+  s.take(ws);
+  p.tfb = s.fl.ok ? ws.take<bf16_t>(br * dy) : nullptr;
+  p.yfb = s.fl.ok ? ws.take<bf16_t>(b * dy) : nullptr;
+  s.frag[0] = p.tfb, s.rows[0] = p.yb;  // problem 0: the rows of Y for every row of T
+  s.frag[1] = p.yfb, s.rows[1] = p.tb;
   static const bool no_tail = getenv("MI_NO_TAIL") != nullptr;  // A/B switch: the round-2 backward tail (three launches)
-  p.tail = p.fl.ok && !no_tail && flash_tail_ok(br, dx, dy);
+  p.tail = s.fl.ok && !no_tail && flash_tail_ok(br, dx, dy);
+  if (precision == MI_PREC_FP8) p.path = fp8_ok(br, b, dx, dy, precision, has_w) ? MI_PATH_FP8_GEMMS : MI_ESHAPE;
+  else if (!fast_ok(br, b, dx, dy, precision, has_w)) p.path = MI_PATH_GENERIC;
+  else if (!s.fl.ok) p.path = MI_PATH_GEMMS;
+  else p.path = p.tail ? MI_PATH_FUSED_TAIL : MI_PATH_FUSED;
   p.wfb = p.tail ? ws.take<bf16_t>(dx * dy) : nullptr;
   p.xtfb = p.tail ? ws.take<bf16_t>(br * dx) : nullptr;
   p.dttfb = p.tail ? ws.take<bf16_t>(br * dy) : nullptr;
@@ -189,30 +245,31 @@ static int fast_prep_and_t(const float* x, const float* y, const float* w, const
                            const BilinearPlan& p, hipStream_t st, int part = 0) {
   // part 1 / part 2: a sharded run prepares what depends on its OWN rows only (the conversions of X and W, T = X W)
   // while the all-gather of the text embeddings is in flight (mi_bilinear_prep_local), and the rest -- the conversions of
-  // the gathered Y, the equal-id flags -- behind it.  Fused-kernel shapes only (the callers check p.fl.ok).
+  // the gathered Y, the equal-id flags -- behind it.  Fused-kernel shapes only (the callers check the plan's path).
+  const bool fused = p.stage.fl.ok;
   if (part == 2) {
     CvtJobs rest{};
     rest.j[1] = CvtJob{y, b, dy, p.yb, nullptr, 0, 0, p.yfb};
-    rest.dup = DupFlagJob{sid_rows, sid_cols, (int)(br / 32), (int)(b / 32), p.fl_dup[0], p.fl_dup[1], row_offset};
+    rest.dup = p.stage.dup_job(sid_rows, sid_cols, row_offset);
     return launch_cvt_transpose3(rest, st, "bilinear prep Y, id flags");
   }
   // With the fused B x B kernel nobody reads Y^T or T^T any more; instead T and Y get a fragment-major copy (the
   // kernel's stationary operand, loaded straight into MFMA B fragments) and the equal-id tile flags ride along.
-  if (p.fl.ok) {
+  if (fused) {
     // one launch: T tiles straight from the fp32 operands, the other conversions on the CUs the tiles leave free
     CvtJobs side{};
     // (with the two-launch tail nobody reads X^T row-major any more: only its fragment-major form)
     side.j[0] = CvtJob{x, br, dx, nullptr, p.tail ? nullptr : p.xtb, 0, 0, nullptr, 0, 0, p.xtfb};
     if (part == 0) side.j[1] = CvtJob{y, b, dy, p.yb, nullptr, 0, 0, p.yfb};
     side.j[2] = CvtJob{w, dx, dy, p.wb, nullptr, 0, 0, p.wfb};
-    if (part == 0) side.dup = DupFlagJob{sid_rows, sid_cols, (int)(br / 32), (int)(b / 32), p.fl_dup[0], p.fl_dup[1], row_offset};
+    if (part == 0) side.dup = p.stage.dup_job(sid_rows, sid_cols, row_offset);
     const int rc1 = launch_prep_t(x, w, br, dy, dx, p.tb, p.tfb, side, st, "bilinear prep + T = X W");
     if (rc1 != MI_EINVAL) return rc1;
   }
   const int x3 = p.x3;
   // G-materialising path in plain bf16 (widths outside the fused kernel, e.g. the reference's 768): the same single
   // launch -- T tiles (row-major and transposed) beside the conversions.  MI_NO_PREP_T=1: the two launches below.
-  if (!p.fl.ok && x3 == 1 && part == 0) {
+  if (!fused && x3 == 1 && part == 0) {
     CvtJobs side{};
     side.j[0] = CvtJob{x, br, dx, nullptr, p.xtb, 0, 0, nullptr, 0, 0, p.xtfb};
     side.j[1] = CvtJob{y, b, dy, p.yb, p.ytb};
@@ -223,14 +280,14 @@ static int fast_prep_and_t(const float* x, const float* y, const float* w, const
   const int ra = x3 == 3 ? 1 : 0, rb = x3 == 3 ? 2 : 0;  // bf16x3 roles of A-side and B-side operands
   CvtJobs jobs{};
   jobs.j[0] = CvtJob{x, br, dx, p.xb, p.xtb, 0, 0, nullptr, ra, ra, p.xtfb};
-  if (part == 0) jobs.j[1] = CvtJob{y, b, dy, p.yb, p.fl.ok ? nullptr : p.ytb, 0, 0, p.fl.ok ? p.yfb : nullptr, rb, rb};
+  if (part == 0) jobs.j[1] = CvtJob{y, b, dy, p.yb, fused ? nullptr : p.ytb, 0, 0, fused ? p.yfb : nullptr, rb, rb};
   jobs.j[2] = CvtJob{w, dx, dy, p.wb, p.wtb, 0, 0, p.wfb, rb, rb};
-  if (p.fl.ok && part == 0) jobs.dup = DupFlagJob{sid_rows, sid_cols, (int)(br / 32), (int)(b / 32), p.fl_dup[0], p.fl_dup[1], row_offset};
+  if (fused && part == 0) jobs.dup = p.stage.dup_job(sid_rows, sid_cols, row_offset);
   int rc = launch_cvt_transpose3(jobs, st, "bilinear prep X Y W");
   if (rc) return rc;
   // T[i, c] = sum_a X[i, a] W[a, c]: A = Xb [br][dx], B = W^T [dy][dx]
   EpiStoreMulti e{};
-  e.out[0] = EpiOut{nullptr, 0, 0, p.tb, dy, p.fl.ok ? nullptr : p.ttb, br, p.fl.ok ? p.tfb : nullptr, ra, rb};
+  e.out[0] = EpiOut{nullptr, 0, 0, p.tb, dy, fused ? nullptr : p.ttb, br, fused ? p.tfb : nullptr, ra, rb};
   return launch_gemm_bf16(one_problem(p.xb, x3 * dx, p.wtb, x3 * dx, br, dy, x3 * dx), 1, e, st, "bilinear T = X W");
 }
 
@@ -244,7 +301,7 @@ static int fast_prep_and_t_bf16(const bf16_t* x, const bf16_t* y, const float* w
   side.j[0] = CvtJob{reinterpret_cast<const float*>(x), br, dx, nullptr, nullptr, 0, 0, nullptr, 0, 0, p.xtfb, 1};
   side.j[1] = CvtJob{reinterpret_cast<const float*>(y), b, dy, nullptr, nullptr, 0, 0, p.yfb, 0, 0, nullptr, 1};
   side.j[2] = CvtJob{w, dx, dy, p.wb, nullptr, 0, 0, p.wfb};
-  side.dup = DupFlagJob{sid_rows, sid_cols, (int)(br / 32), (int)(b / 32), p.fl_dup[0], p.fl_dup[1], row_offset};
+  side.dup = p.stage.dup_job(sid_rows, sid_cols, row_offset);
   return launch_prep_t(reinterpret_cast<const float*>(x), w, br, dy, dx, p.tb, p.tfb, side, st,
                        "bilinear prep + T = X W (bf16 in)", true);
 }
@@ -253,21 +310,6 @@ static int bilinear_bwd_small(int64_t br, int64_t dx, int64_t dy, float* grad_x,
                               hipStream_t st);
 static int bilinear_bwd_from_g(int64_t br, int64_t b, int64_t dx, int64_t dy, float* grad_x, float* grad_y, float* grad_w,
                                bool has_w, const BilinearPlan& p, hipStream_t st);
-
-// the fused B x B launch: scores, masked log-sum-exp partials and (grad) the unnormalised sums U, V of both gradient
-// contractions.  Problem 0 sweeps the text rows for every local image row, problem 1 the local image rows for every
-// text row.
-static int flash_stage(const int64_t* sid_rows, const int64_t* sid_cols, int64_t br, int64_t b, int64_t row_offset,
-                       int64_t dy, bool grad, const BilinearPlan& p, hipStream_t st) {
-  FlashArgs a{};
-  a.p[0] = FlashProblem{p.tfb, p.yb, sid_rows, sid_cols, br, b, row_offset, p.fl.n_rb[0], p.fl.n_split[0],
-                        p.fl.tiles_per_split[0], p.fl_dup[0], p.fl_slab[0], p.fl_rec[0]};
-  a.p[1] = FlashProblem{p.yfb, p.tb, sid_cols, sid_rows, b, br, -row_offset, p.fl.n_rb[1], p.fl.n_split[1],
-                        p.fl.tiles_per_split[1], p.fl_dup[1], p.fl_slab[1], p.fl_rec[1]};
-  a.n_problems = grad ? 2 : 1;
-  a.slab_f16 = p.fl.slab_f16 ? 1 : 0;
-  return launch_flash(a, dy, grad, st, grad ? "bilinear fused S | P Y | P^T T" : "bilinear fused S + LSE");
-}
 
 // The backward's tail in two launches (mi_bilinear_tail.h): [partial sums -> dT rows, grad_y; dX = dT W^T; dT^T
 // fragment-major] and [dW = X^T dT].  `merge` != null: the first launch also merges the fused kernel's records into the
@@ -281,44 +323,59 @@ struct TailMerge {
   int64_t n_records = 0, n_pos = 0;
   int grads_bf16 = 0;              // grad_x / grad_y point to bf16 buffers (the bf16 boundary)
 };
-static int bilinear_tail(int64_t br, int64_t b, int64_t row_offset, int64_t dx, int64_t dy, const mi_stats* stats,
-                         const float* grad_out, float* grad_x, float* grad_y, float* grad_w, const BilinearPlan& p,
-                         const TailMerge* merge, hipStream_t st) {
+// One weight matrix behind the rows the tail reduces: its product dX = dT W^T in the first launch, dW = X^T dT in the second
+struct TailSide {
+  const bf16_t* w_frag;    // W [dx][d] fragment-major
+  int64_t dx;
+  float* grad;             // [rows][dx]
+  bf16_t* dtt_frag;        // dT^T fragment-major: the first launch writes it, the second reads it
+  const bf16_t* xt_frag;   // X^T fragment-major
+  float* grad_w;           // [dx][d]
+};
+// The bilinear critic has one side (job 0: dT -> grad_x, dW; job 1 writes grad_y rows directly), the separable critic two
+// (s1: dC -> grad_y, dWh; grad_y here is null).
+static int bilinear_tail(const FusedStage& s, int64_t row_offset, const mi_stats* stats, const float* grad_out,
+                         const TailSide& s0, const TailSide* s1, float* grad_y, const TailMerge* merge, hipStream_t st) {
   FlashTailArgs ta{};
-  ta.j[0] = FlashReduceJob{p.fl_slab[0], p.fl_rec[0], p.fl.n_split[0], p.fl.n_rb[0], br, p.yb, b, row_offset,
-                           nullptr, nullptr, nullptr};
   const bool gbf = merge && merge->grads_bf16;
-  ta.j[1] = FlashReduceJob{p.fl_slab[1], p.fl_rec[1], p.fl.n_split[1], p.fl.n_rb[1], b, p.tb, br, -row_offset,
-                           gbf ? nullptr : grad_y, gbf ? reinterpret_cast<bf16_t*>(grad_y) : nullptr, nullptr};
+  s.reduce_jobs(ta.j, row_offset, ReduceOut{},
+                ReduceOut{gbf ? nullptr : grad_y, gbf ? reinterpret_cast<bf16_t*>(grad_y) : nullptr, nullptr});
   ta.stats = stats;
   ta.grad_out = grad_out;
   if (merge) {
-    ta.merge_rec = merge->records ? (const Partial*)merge->records : p.fl_rec[0];
-    ta.n_merge = merge->records ? merge->n_records : p.fl.n_rec[0];
-    ta.n_pos = merge->records ? merge->n_pos : b;
+    ta.merge_rec = merge->records ? (const Partial*)merge->records : s.rec[0];
+    ta.n_merge = merge->records ? merge->n_records : s.fl.n_rec[0];
+    ta.n_pos = merge->records ? merge->n_pos : s.b;
     ta.estimator = merge->estimator;
     ta.loss_out = merge->loss_out;
     ta.stats_out = merge->stats_out;
     ta.partials_out = merge->partials_out;
   }
-  ta.w_frag = p.wfb;
-  ta.dx = dx;
+  ta.w_frag = s0.w_frag, ta.dx = s0.dx, ta.dtt_frag = s0.dtt_frag;
 #ifdef MI_STAMPS  // diagnostic library only (make STAMPS=1): a timing experiment that leaves grad_x / grad_w wrong
   static const bool diag_no_dx = getenv("MI_TAIL_DIAG_NO_DX") != nullptr;
-  ta.grad_x = diag_no_dx ? nullptr : grad_x;
+  ta.grad_x = diag_no_dx ? nullptr : s0.grad;
 #else
-  ta.grad_x = grad_x;
+  ta.grad_x = s0.grad;
 #endif
   if (gbf) {
-    ta.grad_x_bf = reinterpret_cast<bf16_t*>(grad_x);
+    ta.grad_x_bf = reinterpret_cast<bf16_t*>(s0.grad);
     ta.grad_x = nullptr;
   }
-  ta.dtt_frag = p.dttfb;
-  int rc = launch_flash_tail(ta, dy, p.fl.slab_f16, merge != nullptr, st,
-                             merge ? "bilinear sums -> loss, dT, dY | dX = dT W^T" : "bilinear sums -> dT, dY | dX = dT W^T");
+  if (s1) ta.w_frag1 = s1->w_frag, ta.dx1 = s1->dx, ta.grad_x1 = s1->grad, ta.dtt_frag1 = s1->dtt_frag;
+  const char* what = s1      ? "separable sums -> loss, dA, dC | dX = dA Wg^T | dY = dC Wh^T"
+                     : merge ? "bilinear sums -> loss, dT, dY | dX = dT W^T"
+                             : "bilinear sums -> dT, dY | dX = dT W^T";
+  int rc = launch_flash_tail(ta, s.d, s.fl.slab_f16, merge != nullptr, st, what);
   if (rc) return rc;
-  if (!grad_w) return MI_OK;  // the caller launches dW itself (mi_bilinear_bwd_dw), e.g. behind the start of a reduce-scatter
-  return launch_bilinear_dw(DwArgs{p.xtfb, p.dttfb, dx, dy, br, grad_w}, st, "bilinear dW = X^T dT");
+  if (!s0.grad_w) return MI_OK;  // the caller launches dW itself (mi_bilinear_bwd_dw), e.g. behind a reduce-scatter's start
+  const DwArgs g{s0.xt_frag, s0.dtt_frag, s0.dx, s.d, s.br, s0.grad_w};
+  if (!s1) return launch_bilinear_dw(g, st, "bilinear dW = X^T dT");
+  const DwArgs h{s1->xt_frag, s1->dtt_frag, s1->dx, s.d, s.b, s1->grad_w};
+  return launch_bilinear_dw(g, st, "separable dWg = X^T dA | dWh = Y^T dC", &h);
+}
+static TailSide bilinear_side(const BilinearPlan& p, int64_t dx, float* grad_x, float* grad_w) {
+  return TailSide{p.wfb, dx, grad_x, p.dttfb, p.xtfb, grad_w};
 }
 
 static int bilinear_fwd_fast(const float* x, const float* y, const float* w, const int64_t* sid_rows,
@@ -326,12 +383,13 @@ static int bilinear_fwd_fast(const float* x, const float* y, const float* w, con
                              int estimator, int need_grad, float* loss_out, mi_stats* stats, float* partials_out,
                              float* scores_out, const BilinearPlan& p, hipStream_t st) {
   // need_grad bit 2: mi_bilinear_prep_local already made the part of the preparation that needs neither Y nor the column ids
-  int rc = fast_prep_and_t(x, y, w, sid_rows, sid_cols, br, b, row_offset, dx, dy, p, st, (need_grad & 4) && p.fl.ok ? 2 : 0);
+  const bool fused = p.path != MI_PATH_GEMMS;
+  int rc = fast_prep_and_t(x, y, w, sid_rows, sid_cols, br, b, row_offset, dx, dy, p, st, (need_grad & 4) && fused ? 2 : 0);
   if (rc) return rc;
-  if (p.fl.ok) {
+  if (fused) {
     // bit 0: gradients wanted (the fused launch then accumulates both contractions); bits 1-3 are flags (fp8 staged,
     // local part prepared, raw records)
-    rc = flash_stage(sid_rows, sid_cols, br, b, row_offset, dy, (need_grad & 1) != 0, p, st);
+    rc = p.stage.launch(sid_rows, sid_cols, row_offset, (need_grad & 1) != 0, st);
     if (rc) return rc;
     if (scores_out) {  // per-pair scores are a diagnostic output: the stand-alone score GEMM writes them
       rc = launch_gemm_bf16(one_problem(p.tb, dy, p.yb, dy, br, b, dy), 1,
@@ -341,8 +399,8 @@ static int bilinear_fwd_fast(const float* x, const float* y, const float* w, con
     }
     // need_grad bit 3: the caller gathers the RAW per-wave records (mi_bilinear_raw_records) from every rank and hands
     // them to mi_bilinear_bwd_records, whose first launch merges them: no finalize launch, nothing written to loss / stats
-    if ((need_grad & 8) && p.tail) return MI_OK;
-    return launch_finalize(p.fl_rec[0], p.fl.n_rec[0], b, estimator, loss_out, stats, partials_out, st);
+    if ((need_grad & 8) && p.path == MI_PATH_FUSED_TAIL) return MI_OK;
+    return launch_finalize(p.stage.rec[0], p.stage.fl.n_rec[0], b, estimator, loss_out, stats, partials_out, st);
   }
   const int x3 = p.x3;
   rc = launch_gemm_bf16(one_problem(p.tb, x3 * dy, p.yb, x3 * dy, br, b, x3 * dy), 1,
@@ -355,20 +413,19 @@ static int bilinear_fwd_fast(const float* x, const float* y, const float* w, con
 
 static int bilinear_bwd_fast(const int64_t* sid_rows, const int64_t* sid_cols, int64_t br, int64_t b, int64_t row_offset,
                              int64_t dx, int64_t dy, const mi_stats* stats, const float* grad_out, float* grad_x,
-                             float* grad_y, float* grad_w, const BilinearPlan& p, bool flash_sums, hipStream_t st) {
+                             float* grad_y, float* grad_w, const BilinearPlan& p, hipStream_t st) {
   int rc = MI_OK;
-  if (flash_sums && p.tail) return bilinear_tail(br, b, row_offset, dx, dy, stats, grad_out, grad_x, grad_y, grad_w, p, nullptr, st);
-  if (flash_sums) {
+  if (p.path == MI_PATH_FUSED_TAIL)
+    return bilinear_tail(p.stage, row_offset, stats, grad_out, bilinear_side(p, dx, grad_x, grad_w), nullptr, grad_y, nullptr,
+                         st);
+  if (p.path == MI_PATH_FUSED) {
     // the forward's fused launch left U, V as slabs: scale by exp(m_ref - lse), subtract the diagonal term, add the
     // slabs in a fixed order -> dT (bf16, both orientations, operands of dW | dX) and grad_y
     FlashReduceArgs ra{};
-    ra.j[0] = FlashReduceJob{p.fl_slab[0], p.fl_rec[0], p.fl.n_split[0], p.fl.n_rb[0], br, p.yb, b, row_offset,
-                             nullptr, p.dtb, p.dttb};
-    ra.j[1] = FlashReduceJob{p.fl_slab[1], p.fl_rec[1], p.fl.n_split[1], p.fl.n_rb[1], b, p.tb, br, -row_offset,
-                             grad_y, nullptr, nullptr};
+    p.stage.reduce_jobs(ra.j, row_offset, ReduceOut{nullptr, p.dtb, p.dttb}, ReduceOut{grad_y, nullptr, nullptr});
     ra.stats = stats;
     ra.grad_out = grad_out;
-    rc = launch_flash_reduce(ra, 2, dy, p.fl.slab_f16, st, "bilinear dT, dY from the fused sums");
+    rc = launch_flash_reduce(ra, 2, dy, p.stage.fl.slab_f16, st, "bilinear dT, dY from the fused sums");
     if (rc) return rc;
     return bilinear_bwd_small(br, dx, dy, grad_x, grad_w, p, st);
   }
@@ -426,35 +483,46 @@ static int bilinear_bwd_from_g(int64_t br, int64_t b, int64_t dx, int64_t dy, fl
   return bilinear_bwd_small(br, dx, dy, grad_x, grad_w, p, st);
 }
 
-// dW[a, c] = sum_i X[i, a] dT[i, c]: A = X^T [dx][br], B = dT^T [dy][br], split over i into slabs
-// dX[i, a] = sum_c dT[i, c] W[a, c]: A = dT [br][dy], B = W [dx][dy]
-// Both only wait for dT: one launch (few tiles each; on their own they leave most CUs idle).
-static int bilinear_bwd_small(int64_t br, int64_t dx, int64_t dy, float* grad_x, float* grad_w, const BilinearPlan& p,
-                              hipStream_t st) {
-  int rc = MI_OK;
+// dW[a, c] = sum_i X[i, a] dT[i, c]: A = X^T [dx][rows], B = dT^T [dy][rows], split over i into slabs
+// dX[i, a] = sum_c dT[i, c] W[a, c]: A = dT [rows][dy], B = W [dx][dy]
+// Both only wait for dT: one launch (few tiles each; on their own they leave most CUs idle).  The separable critic runs it
+// once per modality.  what[3]: the labels of the pair and, for shapes the LDS-DMA kernel does not take, of dW and dX alone.
+struct DwDxPair {
+  const bf16_t *xt, *dtt, *dt, *w;
+  int64_t rows, dx, dy;
+  int x3;
+  float* slab;
+  int splits;
+  int64_t kchunk;
+};
+static int launch_dw_dx(const DwDxPair& q, float* grad_x, float* grad_w, hipStream_t st, const char* const (&what)[3]) {
+  const int64_t x3 = q.x3, rows = q.rows, dx = q.dx, dy = q.dy;
   GemmBf16Args dwx{};
-  const int x3 = p.x3;
-  dwx.p[0] = GemmBf16Problem{p.xtb, x3 * br, p.dttb, x3 * br, dx, dy, x3 * br};
-  dwx.p[1] = GemmBf16Problem{p.dtb, x3 * dy, p.wb, x3 * dy, br, dx, x3 * dy};
+  dwx.p[0] = GemmBf16Problem{q.xt, x3 * rows, q.dtt, x3 * rows, dx, dy, x3 * rows};
+  dwx.p[1] = GemmBf16Problem{q.dt, x3 * dy, q.w, x3 * dy, rows, dx, x3 * dy};
   dwx.n_problems = 2;
   EpiStoreMulti e3{};
-  e3.out[0] = EpiOut{p.dw_slab, dy, dx * dy, nullptr, 0, nullptr, 0};
+  e3.out[0] = EpiOut{q.slab, dy, dx * dy, nullptr, 0, nullptr, 0};
   e3.out[1] = EpiOut{grad_x, dx, 0, nullptr, 0, nullptr, 0};
-  const int splits[2] = {p.dw_splits, 1};
-  const int64_t chunks[2] = {x3 * p.dw_kchunk, x3 * dy};
-  rc = launch_gemm_bf16_flat(dwx, splits, chunks, e3, st, "bilinear dW = X^T dT | dX = dT W^T");
-  if (rc == MI_EINVAL) {  // shapes the LDS-DMA kernel does not take: one launch each
+  const int splits[2] = {q.splits, 1};
+  const int64_t chunks[2] = {x3 * q.kchunk, x3 * dy};
+  int rc = launch_gemm_bf16_flat(dwx, splits, chunks, e3, st, what[0]);
+  if (rc == MI_EINVAL) {  // one launch each
     EpiStoreMulti e4{};
     e4.out[0] = e3.out[0];
-    rc = launch_gemm_bf16(one_problem(p.xtb, x3 * br, p.dttb, x3 * br, dx, dy, x3 * br, x3 * p.dw_kchunk), p.dw_splits,
-                          e4, st, "bilinear dW = X^T dT");
+    rc = launch_gemm_bf16(one_problem(q.xt, x3 * rows, q.dtt, x3 * rows, dx, dy, x3 * rows, x3 * q.kchunk), q.splits, e4, st,
+                          what[1]);
     if (rc) return rc;
     e4.out[0] = e3.out[1];
-    rc = launch_gemm_bf16(one_problem(p.dtb, x3 * dy, p.wb, x3 * dy, br, dx, x3 * dy), 1, e4, st,
-                          "bilinear dX = dT W^T");
+    rc = launch_gemm_bf16(one_problem(q.dt, x3 * dy, q.w, x3 * dy, rows, dx, x3 * dy), 1, e4, st, what[2]);
   }
   if (rc) return rc;
-  return launch_slab_reduce_ld(p.dw_slab, p.dw_splits, dx, dy, grad_w, dy, st, "slab_reduce_ld_kernel");
+  return launch_slab_reduce_ld(q.slab, q.splits, dx, dy, grad_w, dy, st, "slab_reduce_ld_kernel");
+}
+static int bilinear_bwd_small(int64_t br, int64_t dx, int64_t dy, float* grad_x, float* grad_w, const BilinearPlan& p,
+                              hipStream_t st) {
+  return launch_dw_dx(DwDxPair{p.xtb, p.dttb, p.dtb, p.wb, br, dx, dy, p.x3, p.dw_slab, p.dw_splits, p.dw_kchunk}, grad_x,
+                      grad_w, st, {"bilinear dW = X^T dT | dX = dT W^T", "bilinear dW = X^T dT", "bilinear dX = dT W^T"});
 }
 
 // ------------------------------------------------------------------------------------------------ fp8 path (mi_fp8.h)
@@ -567,6 +635,16 @@ static int bilinear_bwd_fp8(const int64_t* sid_rows, const int64_t* sid_cols, in
 }
 
 // ------------------------------------------------------------------------------------------------ generic path
+// The operand type of the strided-operand kernels (mi_gemm.h): bf16, or float for exact fp32 products.  `f` is a generic
+// lambda called with a null pointer of that type (OperandOf names it).  The bilinear critic and the chains run bf16
+// operands in the bf16 mode only (bf16x3 falls back to exact products), the separable critic in every mode but f32.
+template <typename F>
+static int with_operand_type(bool bf16, F&& f) {
+  return bf16 ? f((bf16_t*)nullptr) : f((float*)nullptr);
+}
+template <typename P>
+using OperandOf = std::remove_pointer_t<P>;
+
 // out [M][N] (ld) = A B^T with K split into slabs when the output has too few tiles (exact-fp32 mode only: the plan holds
 // the slab buffer); the slabs are added in split order (fixed order: reproducible)
 template <typename OpT, typename TA, typename TB>
@@ -663,6 +741,13 @@ static int check_common(const char* fn, int64_t br, int64_t b, int64_t row_offse
   return MI_OK;
 }
 
+// the plan's path of an fp8 call outside the fp8 kernels' shapes
+static int fp8_shape_error(const char* fn) {
+  set_error("%s: the fp8 mode needs a weight matrix, batch sizes that are multiples of 8 and widths that are multiples of 16",
+            fn);
+  return MI_ESHAPE;
+}
+
 }  // namespace mi
 
 using namespace mi;
@@ -672,7 +757,7 @@ extern "C" {
 size_t mi_bilinear_workspace_bytes(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, int precision) {
   if (b_rows <= 0 || b <= 0 || d_img <= 0 || d_txt <= 0) return 0;  // (the planner divides by tile counts)
   Workspace ws(nullptr, 0);
-  return plan_bilinear(ws, b_rows, b, d_img, d_txt, precision).bytes + 256;
+  return plan_bilinear(ws, b_rows, b, d_img, d_txt, precision, true).bytes + 256;
 }
 
 int mi_bilinear_fwd(const float* x, const float* y, const float* w, const int64_t* sid_rows, const int64_t* sid_cols,
@@ -685,27 +770,25 @@ int mi_bilinear_fwd(const float* x, const float* y, const float* w, const int64_
   if (rc) return rc;
   MI_CHECK_ARG(estimator == MI_DV || estimator == MI_INFONCE, "mi_bilinear_fwd: unknown estimator %d", estimator);
   Workspace ws(workspace, workspace_bytes);
-  BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, precision);
+  const BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, precision, w != nullptr);
   rc = ws_fits(ws, "mi_bilinear_fwd");
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (precision == MI_PREC_FP8) {
-    if (!fp8_ok(b_rows, b, d_img, d_txt, precision, w != nullptr)) {
-      set_error("mi_bilinear_fwd: the fp8 mode needs a weight matrix, batch sizes that are multiples of 8 and widths that "
-                "are multiples of 16");
-      return MI_ESHAPE;
-    }
-    return bilinear_fwd_fp8(x, y, w, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, estimator, loss_out, stats,
-                            partials_out, scores_out, p, (need_grad & 2) != 0, st);
+  switch (p.path) {
+    case MI_ESHAPE:
+      return fp8_shape_error("mi_bilinear_fwd");
+    case MI_PATH_FP8_GEMMS:
+      return bilinear_fwd_fp8(x, y, w, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, estimator, loss_out, stats,
+                              partials_out, scores_out, p, (need_grad & 2) != 0, st);
+    case MI_PATH_GENERIC:
+      return with_operand_type(precision == MI_PREC_BF16, [&](auto* op) {
+        return bilinear_fwd_impl<OperandOf<decltype(op)>>(x, y, w, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt,
+                                                          estimator, loss_out, stats, partials_out, scores_out, p, st);
+      });
+    default:  // MI_PATH_GEMMS, MI_PATH_FUSED, MI_PATH_FUSED_TAIL
+      return bilinear_fwd_fast(x, y, w, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, estimator, need_grad,
+                               loss_out, stats, partials_out, scores_out, p, st);
   }
-  if (fast_ok(b_rows, b, d_img, d_txt, precision, w != nullptr))
-    return bilinear_fwd_fast(x, y, w, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, estimator, need_grad,
-                             loss_out, stats, partials_out, scores_out, p, st);
-  if (precision == MI_PREC_BF16)
-    return bilinear_fwd_impl<bf16_t>(x, y, w, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, estimator,
-                                     loss_out, stats, partials_out, scores_out, p, st);
-  return bilinear_fwd_impl<float>(x, y, w, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, estimator, loss_out,
-                                  stats, partials_out, scores_out, p, st);
 }
 
 int mi_bilinear_bwd(const float* x, const float* y, const float* w, const int64_t* sid_rows, const int64_t* sid_cols,
@@ -719,40 +802,38 @@ int mi_bilinear_bwd(const float* x, const float* y, const float* w, const int64_
   int rc = check_common("mi_bilinear_bwd", b_rows, b, row_offset, d_img, d_txt, precision);
   if (rc) return rc;
   Workspace ws(workspace, workspace_bytes);
-  BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, precision);
+  const BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, precision, w != nullptr);
   rc = ws_fits(ws, "mi_bilinear_bwd");
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (precision == MI_PREC_FP8) {
-    if (!fp8_ok(b_rows, b, d_img, d_txt, precision, w != nullptr)) {
-      set_error("mi_bilinear_bwd: the fp8 mode needs a weight matrix, batch sizes that are multiples of 8 and widths that "
-                "are multiples of 16");
-      return MI_ESHAPE;
-    }
-    if (!workspace_from_forward) {
-      rc = fp8_prep_and_t(x, y, w, b_rows, b, d_img, d_txt, p, st);
-      if (rc) return rc;
-    }
-    return bilinear_bwd_fp8(sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, stats, grad_out, grad_x, grad_y, grad_w,
-                            p, st);
-  }
-  if (fast_ok(b_rows, b, d_img, d_txt, precision, w != nullptr)) {
-    if (!workspace_from_forward) {  // rebuild the bf16 operand copies, T and the fused sums
-      rc = fast_prep_and_t(x, y, w, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, p, st);
-      if (rc) return rc;
-      if (p.fl.ok) {
-        rc = flash_stage(sid_rows, sid_cols, b_rows, b, row_offset, d_txt, true, p, st);
+  switch (p.path) {
+    case MI_ESHAPE:
+      return fp8_shape_error("mi_bilinear_bwd");
+    case MI_PATH_FP8_GEMMS:
+      if (!workspace_from_forward) {
+        rc = fp8_prep_and_t(x, y, w, b_rows, b, d_img, d_txt, p, st);
         if (rc) return rc;
       }
-    }
-    return bilinear_bwd_fast(sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, stats, grad_out, grad_x, grad_y,
-                             grad_w, p, p.fl.ok, st);
+      return bilinear_bwd_fp8(sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, stats, grad_out, grad_x, grad_y,
+                              grad_w, p, st);
+    case MI_PATH_GENERIC:
+      return with_operand_type(precision == MI_PREC_BF16, [&](auto* op) {
+        using OpT = OperandOf<decltype(op)>;  // G is stored in the operand type
+        return bilinear_bwd_impl<OpT, OpT>(x, y, w, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, stats, grad_out,
+                                           grad_x, grad_y, grad_w, p, st);
+      });
+    default:  // MI_PATH_GEMMS, MI_PATH_FUSED, MI_PATH_FUSED_TAIL
+      if (!workspace_from_forward) {  // rebuild the bf16 operand copies, T and the fused sums
+        rc = fast_prep_and_t(x, y, w, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, p, st);
+        if (rc) return rc;
+        if (p.path != MI_PATH_GEMMS) {
+          rc = p.stage.launch(sid_rows, sid_cols, row_offset, true, st);
+          if (rc) return rc;
+        }
+      }
+      return bilinear_bwd_fast(sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, stats, grad_out, grad_x, grad_y,
+                               grad_w, p, st);
   }
-  if (precision == MI_PREC_BF16)
-    return bilinear_bwd_impl<bf16_t, bf16_t>(x, y, w, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, stats,
-                                             grad_out, grad_x, grad_y, grad_w, p, st);
-  return bilinear_bwd_impl<float, float>(x, y, w, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, stats,
-                                         grad_out, grad_x, grad_y, grad_w, p, st);
 }
 
 /* Sharded batches without the finalize and merge launches.  The fused kernel leaves one 16-byte record per wave in the
@@ -766,10 +847,10 @@ size_t mi_bilinear_raw_records(int64_t b_rows, int64_t b, int64_t d_img, int64_t
   if (b_rows <= 0 || b <= 0 || d_img <= 0 || d_txt <= 0) return 0;
   char* fake = reinterpret_cast<char*>(uintptr_t(1) << 20);  // only pointer differences are used
   Workspace ws(fake, ~size_t(0) >> 1);
-  BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, precision);
-  if (!(fast_ok(b_rows, b, d_img, d_txt, precision, true) && p.fl.ok && p.tail)) return 0;
-  if (offset_bytes) *offset_bytes = (size_t)(reinterpret_cast<char*>(p.fl_rec[0]) - fake);
-  return (size_t)p.fl.n_rec[0];
+  const BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, precision, true);
+  if (p.path != MI_PATH_FUSED_TAIL) return 0;
+  if (offset_bytes) *offset_bytes = (size_t)(reinterpret_cast<char*>(p.stage.rec[0]) - fake);
+  return (size_t)p.stage.fl.n_rec[0];
 }
 
 int mi_bilinear_bwd_records(const float* x, const float* y, const float* w, const int64_t* sid_rows,
@@ -784,16 +865,16 @@ int mi_bilinear_bwd_records(const float* x, const float* y, const float* w, cons
   int rc = check_common("mi_bilinear_bwd_records", b_rows, b, row_offset, d_img, d_txt, precision);
   if (rc) return rc;
   Workspace ws(workspace, workspace_bytes);
-  BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, precision);
+  const BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, precision, true);
   rc = ws_fits(ws, "mi_bilinear_bwd_records");
   if (rc) return rc;
-  if (!(fast_ok(b_rows, b, d_img, d_txt, precision, true) && p.fl.ok && p.tail)) {
+  if (p.path != MI_PATH_FUSED_TAIL) {
     set_error("mi_bilinear_bwd_records: shape / precision outside the fused kernels (mi_bilinear_raw_records returns 0)");
     return MI_ESHAPE;
   }
-  TailMerge tm{estimator, loss_out, stats_out, nullptr, records, n_records, n_pos};
-  return bilinear_tail(b_rows, b, row_offset, d_img, d_txt, nullptr, grad_out, grad_x, grad_y, grad_w, p, &tm,
-                       (hipStream_t)stream);
+  const TailMerge tm{estimator, loss_out, stats_out, nullptr, records, n_records, n_pos};
+  const TailSide side = bilinear_side(p, d_img, grad_x, grad_w);
+  return bilinear_tail(p.stage, row_offset, nullptr, grad_out, side, nullptr, grad_y, &tm, (hipStream_t)stream);
 }
 
 /* The second launch of the backward's tail on its own (dW = X^T dT from the fragment-major operands the first launch and
@@ -806,10 +887,10 @@ int mi_bilinear_bwd_dw(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, 
   int rc = check_common("mi_bilinear_bwd_dw", b_rows, b, 0, d_img, d_txt, precision);
   if (rc) return rc;
   Workspace ws(workspace, workspace_bytes);
-  BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, precision);
+  const BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, precision, true);
   rc = ws_fits(ws, "mi_bilinear_bwd_dw");
   if (rc) return rc;
-  if (!(fast_ok(b_rows, b, d_img, d_txt, precision, true) && p.fl.ok && p.tail)) {
+  if (p.path != MI_PATH_FUSED_TAIL) {
     set_error("mi_bilinear_bwd_dw: shape / precision outside the fused kernels");
     return MI_ESHAPE;
   }
@@ -826,10 +907,10 @@ int mi_bilinear_prep_local(const float* x, const float* w, int64_t b_rows, int64
   int rc = check_common("mi_bilinear_prep_local", b_rows, b, 0, d_img, d_txt, precision);
   if (rc) return rc;
   Workspace ws(workspace, workspace_bytes);
-  BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, precision);
+  const BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, precision, true);
   rc = ws_fits(ws, "mi_bilinear_prep_local");
   if (rc) return rc;
-  if (!(fast_ok(b_rows, b, d_img, d_txt, precision, true) && p.fl.ok)) {
+  if (p.path != MI_PATH_FUSED && p.path != MI_PATH_FUSED_TAIL) {
     set_error("mi_bilinear_prep_local: shape / precision outside the fused kernels (call mi_bilinear_fwd alone)");
     return MI_ESHAPE;
   }
@@ -853,7 +934,7 @@ int mi_bilinear_fp8_stage(const float* x, const float* y, const float* w, int64_
     return MI_ESHAPE;
   }
   Workspace ws(workspace, workspace_bytes);
-  BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, MI_PREC_FP8);
+  const BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, MI_PREC_FP8, true);
   rc = ws_fits(ws, "mi_bilinear_fp8_stage");
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
@@ -894,17 +975,17 @@ int mi_bilinear_step(const float* x, const float* y, const float* w, const int64
   if (rc) return rc;
   MI_CHECK_ARG(estimator == MI_DV || estimator == MI_INFONCE, "mi_bilinear_step: unknown estimator %d", estimator);
   Workspace ws(workspace, workspace_bytes);
-  BilinearPlan p = plan_bilinear(ws, b, b, d_img, d_txt, precision);
+  const BilinearPlan p = plan_bilinear(ws, b, b, d_img, d_txt, precision, w != nullptr);
   rc = ws_fits(ws, "mi_bilinear_step");
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (fast_ok(b, b, d_img, d_txt, precision, w != nullptr) && p.fl.ok && p.tail) {
+  if (p.path == MI_PATH_FUSED_TAIL) {
     rc = fast_prep_and_t(x, y, w, sid, sid, b, b, 0, d_img, d_txt, p, st);
     if (rc) return rc;
-    rc = flash_stage(sid, sid, b, b, 0, d_txt, true, p, st);
+    rc = p.stage.launch(sid, sid, 0, true, st);
     if (rc) return rc;
     const TailMerge m{estimator, loss_out, stats, partials_out};
-    return bilinear_tail(b, b, 0, d_img, d_txt, stats, grad_out, grad_x, grad_y, grad_w, p, &m, st);
+    return bilinear_tail(p.stage, 0, stats, grad_out, bilinear_side(p, d_img, grad_x, grad_w), nullptr, grad_y, &m, st);
   }
   rc = mi_bilinear_fwd(x, y, w, sid, sid, b, b, 0, d_img, d_txt, estimator, precision, 1, loss_out, stats, partials_out,
                        nullptr, workspace, workspace_bytes, stream);
@@ -929,10 +1010,10 @@ int mi_bilinear_step_bf16(const void* x_bf16, const void* y_bf16, const float* w
   if (rc) return rc;
   MI_CHECK_ARG(estimator == MI_DV || estimator == MI_INFONCE, "mi_bilinear_step_bf16: unknown estimator %d", estimator);
   Workspace ws(workspace, workspace_bytes);
-  BilinearPlan p = plan_bilinear(ws, b, b, d_img, d_txt, MI_PREC_BF16);
+  BilinearPlan p = plan_bilinear(ws, b, b, d_img, d_txt, MI_PREC_BF16, true);
   rc = ws_fits(ws, "mi_bilinear_step_bf16");
   if (rc) return rc;
-  if (!(fast_ok(b, b, d_img, d_txt, MI_PREC_BF16, true) && p.fl.ok && p.tail) || (uintptr_t)x_bf16 % 16 != 0 ||
+  if (p.path != MI_PATH_FUSED_TAIL || (uintptr_t)x_bf16 % 16 != 0 ||
       (uintptr_t)y_bf16 % 16 != 0) {
     set_error("mi_bilinear_step_bf16: shape outside the fused kernels (mi_bilinear_path != MI_PATH_FUSED_TAIL) or "
               "embeddings not 16-byte aligned: convert to fp32 and call mi_bilinear_step");
@@ -940,28 +1021,24 @@ int mi_bilinear_step_bf16(const void* x_bf16, const void* y_bf16, const float* w
   }
   hipStream_t st = (hipStream_t)stream;
   const bf16_t* xb = reinterpret_cast<const bf16_t*>(x_bf16);
-  p.yb = const_cast<bf16_t*>(reinterpret_cast<const bf16_t*>(y_bf16));  // the streamed operand of problem 0: the input itself
-  rc = fast_prep_and_t_bf16(xb, p.yb, w, sid, sid, b, b, 0, d_img, d_txt, p, st);
+  const bf16_t* yb = reinterpret_cast<const bf16_t*>(y_bf16);
+  p.stage.rows[0] = yb;  // the streamed operand of problem 0: the input itself
+  rc = fast_prep_and_t_bf16(xb, yb, w, sid, sid, b, b, 0, d_img, d_txt, p, st);
   if (rc) return rc == MI_EINVAL ? MI_ESHAPE : rc;
-  rc = flash_stage(sid, sid, b, b, 0, d_txt, true, p, st);
+  rc = p.stage.launch(sid, sid, 0, true, st);
   if (rc) return rc;
   TailMerge m{estimator, loss_out, stats, partials_out};
   m.grads_bf16 = grads_bf16 ? 1 : 0;
-  return bilinear_tail(b, b, 0, d_img, d_txt, stats, grad_out, reinterpret_cast<float*>(grad_x),
-                       reinterpret_cast<float*>(grad_y), grad_w, p, &m, st);
+  const TailSide side = bilinear_side(p, d_img, reinterpret_cast<float*>(grad_x), grad_w);
+  return bilinear_tail(p.stage, 0, stats, grad_out, side, nullptr, reinterpret_cast<float*>(grad_y), &m, st);
 }
 
 /* Which kernels a bilinear-critic shape takes (host-side arithmetic only, nothing is launched): MI_PATH_*.  The Python
  * binding warns once per shape when a 16-bit call leaves the fused kernels. */
 int mi_bilinear_path(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, int precision) {
   if (b_rows <= 0 || b <= 0 || d_img <= 0 || d_txt <= 0) return MI_EINVAL;
-  if (precision == MI_PREC_FP8) return fp8_ok(b_rows, b, d_img, d_txt, precision, true) ? MI_PATH_FP8_GEMMS : MI_ESHAPE;
-  if (!fast_ok(b_rows, b, d_img, d_txt, precision, true)) return MI_PATH_GENERIC;
-  char* fake = reinterpret_cast<char*>(uintptr_t(1) << 20);
-  Workspace ws(fake, ~size_t(0) >> 1);
-  BilinearPlan p = plan_bilinear(ws, b_rows, b, d_img, d_txt, precision);
-  if (!p.fl.ok) return MI_PATH_GEMMS;
-  return p.tail ? MI_PATH_FUSED_TAIL : MI_PATH_FUSED;
+  Workspace ws(nullptr, 0);
+  return plan_bilinear(ws, b_rows, b, d_img, d_txt, precision, true).path;
 }
 
 }  // extern "C"
@@ -976,14 +1053,11 @@ int mi_bilinear_path(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, in
 namespace mi {
 
 struct SeparablePlan {
-  bool fast;
-  FlashPlan fl;
+  int path;            // MI_PATH_GENERIC, MI_PATH_FUSED or MI_PATH_FUSED_TAIL
+  FusedStage stage;    // the fused B x B stage on S = A C^T
   bf16_t *xb, *xtb, *yb, *ytb, *gb, *gtb, *hb, *htb;   // X, Y, Wg, Wh as bf16, row-major and transposed
   bf16_t *ab, *afb, *cb, *cfb;                          // projections, row-major and fragment-major
   bf16_t *dab, *datb, *dcb, *dctb;                      // their gradients, both orientations
-  float *slab[2];
-  Partial* rec[2];
-  unsigned char* dup[2];
   float *wg_slab, *wh_slab;
   int wg_splits, wh_splits;
   int64_t wg_kchunk, wh_kchunk;
@@ -1010,10 +1084,11 @@ static void split_plan(int64_t rows, int64_t m, int64_t n, int& splits, int64_t&
 static SeparablePlan plan_separable(Workspace& ws, int64_t br, int64_t b, int64_t dx, int64_t dy, int64_t k,
                                     int precision) {
   SeparablePlan p{};
-  p.fl = FlashPlan{};
-  if (precision == MI_PREC_BF16 && dx % 8 == 0 && dy % 8 == 0 && k % 64 == 0) p.fl = flash_plan(br, b, k);
-  p.fast = p.fl.ok;
-  if (p.fast) {
+  FusedStage& s = p.stage;
+  if (precision == MI_PREC_BF16 && dx % 8 == 0 && dy % 8 == 0 && k % 64 == 0) s.fl = flash_plan(br, b, k);
+  s.br = br, s.b = b, s.d = k;
+  s.what_grad = "separable fused S | P C | P^T A", s.what_fwd = "separable fused S + LSE";
+  if (s.fl.ok) {
     p.xb = ws.take<bf16_t>(br * dx);
     p.xtb = ws.take<bf16_t>(br * dx);
     p.yb = ws.take<bf16_t>(b * dy);
@@ -1030,17 +1105,15 @@ static SeparablePlan plan_separable(Workspace& ws, int64_t br, int64_t b, int64_
     p.datb = ws.take<bf16_t>(br * k);
     p.dcb = ws.take<bf16_t>(b * k);
     p.dctb = ws.take<bf16_t>(b * k);
-    for (int q = 0; q < 2; ++q) {
-      p.rec[q] = ws.take<Partial>(p.fl.n_rec[q]);
-      p.slab[q] = ws.take<float>((p.fl.slab_bytes[q] + 3) / 4);
-      p.dup[q] = ws.take<unsigned char>((br / 32) * (b / 32));
-    }
+    s.frag[0] = p.afb, s.rows[0] = p.cb;  // problem 0: the rows of C for every row of A
+    s.frag[1] = p.cfb, s.rows[1] = p.ab;
+    s.take(ws);
     split_plan(br, dx, k, p.wg_splits, p.wg_kchunk);
     split_plan(b, dy, k, p.wh_splits, p.wh_kchunk);
     p.wg_slab = ws.take<float>((int64_t)p.wg_splits * dx * k);
     p.wh_slab = ws.take<float>((int64_t)p.wh_splits * dy * k);
     static const bool no_tail = getenv("MI_NO_TAIL") != nullptr;  // A/B switch, as for the bilinear critic
-    p.tail = !no_tail && flash_tail_ok(br, dx, k) && flash_tail_ok(b, dy, k) && p.fl.slab_f16;
+    p.tail = !no_tail && flash_tail_ok(br, dx, k) && flash_tail_ok(b, dy, k) && s.fl.slab_f16;
     if (p.tail) {
       p.gfb = ws.take<bf16_t>(dx * k);
       p.hfb = ws.take<bf16_t>(dy * k);
@@ -1059,6 +1132,7 @@ static SeparablePlan plan_separable(Workspace& ws, int64_t br, int64_t b, int64_
     if (precision == MI_PREC_BF16) p.g = ws.take<bf16_t>(br * b);
     else p.g = ws.take<float>(br * b);
   }
+  p.path = !s.fl.ok ? MI_PATH_GENERIC : p.tail ? MI_PATH_FUSED_TAIL : MI_PATH_FUSED;
   p.bytes = ws.off;
   return p;
 }
@@ -1072,7 +1146,7 @@ static int separable_prep_project(const float* x, const float* y, const float* w
   jobs.j[1] = CvtJob{y, b, dy, p.yb, p.ytb, 0, 0, nullptr, 0, 0, p.tail ? p.ytfb : nullptr};
   jobs.j[2] = CvtJob{wg, dx, k, p.gb, p.gtb, 0, 0, p.tail ? p.gfb : nullptr};
   jobs.j[3] = CvtJob{wh, dy, k, p.hb, p.htb, 0, 0, p.tail ? p.hfb : nullptr};
-  jobs.dup = DupFlagJob{sid_rows, sid_cols, (int)(br / 32), (int)(b / 32), p.dup[0], p.dup[1], row_offset};
+  jobs.dup = p.stage.dup_job(sid_rows, sid_cols, row_offset);
   int rc = launch_cvt_transpose3(jobs, st, "separable prep X Y Wg Wh");
   if (rc) return rc;
   // A[i, c] = sum_a X[i, a] Wg[a, c] (A operand Xb [br][dx], B operand Wg^T [k][dx]);  C likewise from Y, Wh
@@ -1101,21 +1175,54 @@ static int separable_prep_project_fused(const float* x, const float* y, const fl
   side.j[1] = CvtJob{y, b, dy, nullptr, nullptr, 0, 0, nullptr, 0, 0, p.ytfb};
   side.j[2] = CvtJob{wg, dx, k, nullptr, nullptr, 0, 0, p.gfb};
   side.j[3] = CvtJob{wh, dy, k, nullptr, nullptr, 0, 0, p.hfb};
-  side.dup = DupFlagJob{sid_rows, sid_cols, (int)(br / 32), (int)(b / 32), p.dup[0], p.dup[1], row_offset};
+  side.dup = p.stage.dup_job(sid_rows, sid_cols, row_offset);
   const PrepTSecond c{y, wh, b, k, dy, p.cb, p.cfb};
   return launch_prep_t(x, wg, br, k, dx, p.ab, p.afb, side, st, "separable prep + A = X Wg | C = Y Wh", false, &c);
 }
 
-static int separable_flash(const int64_t* sid_rows, const int64_t* sid_cols, int64_t br, int64_t b, int64_t row_offset,
-                           int64_t k, bool grad, const SeparablePlan& p, hipStream_t st) {
-  FlashArgs a{};
-  a.p[0] = FlashProblem{p.afb, p.cb, sid_rows, sid_cols, br, b, row_offset, p.fl.n_rb[0], p.fl.n_split[0],
-                        p.fl.tiles_per_split[0], p.dup[0], p.slab[0], p.rec[0]};
-  a.p[1] = FlashProblem{p.cfb, p.ab, sid_cols, sid_rows, b, br, -row_offset, p.fl.n_rb[1], p.fl.n_split[1],
-                        p.fl.tiles_per_split[1], p.dup[1], p.slab[1], p.rec[1]};
-  a.n_problems = grad ? 2 : 1;
-  a.slab_f16 = p.fl.slab_f16 ? 1 : 0;
-  return launch_flash(a, k, grad, st, grad ? "separable fused S | P C | P^T A" : "separable fused S + LSE");
+// The separable critic's projections on the strided-operand kernels (its generic path, and every shape of the InfoNCE /
+// f-divergence chains): A = X Wg [br][k], C = Y Wh [b][k] (a row block projects all b text rows) and their gradients,
+// bf16 operands in the bf16 mode, exact fp32 products otherwise.  The launch labels are the caller's.
+struct SepLabels {
+  const char *a, *c, *dx, *dwg, *dy, *dwh;
+};
+static constexpr SepLabels kSepFwd = {"separable A = X Wg (generic)", "separable C = Y Wh (generic)"};
+static constexpr SepLabels kSepBwd = {"separable A = X Wg (generic, bwd)", "separable C = Y Wh (generic, bwd)",
+                                      "separable dX = dA Wg^T (generic)", "separable dWg = X^T dA (generic)",
+                                      "separable dY = dC Wh^T (generic)", "separable dWh = Y^T dC (generic)"};
+
+static int separable_project(const SepLabels& l, bool bf, const float* x, const float* y, const float* wg,
+                             const float* wh, int64_t br, int64_t b, int64_t dx, int64_t dy, int64_t k, float* a, float* c,
+                             hipStream_t st) {
+  return with_operand_type(bf, [&](auto* op) {
+    using OpT = OperandOf<decltype(op)>;
+    const int rc = launch_gemm<OpT>(make_operand(x, dx, 1), make_operand(wg, 1, k), br, k, dx,
+                                    EpiStore{a, k, nullptr, 1.0f, 0}, st, l.a);
+    if (rc) return rc;
+    return launch_gemm<OpT>(make_operand(y, dy, 1), make_operand(wh, 1, k), b, k, dy, EpiStore{c, k, nullptr, 1.0f, 0},
+                            st, l.c);
+  });
+}
+
+// dA [br][k] -> dX = dA Wg^T and (the row block's part of) dWg = X^T dA; dC [b][k] -> (parts of) dY = dC Wh^T, dWh = Y^T dC
+static int separable_project_back(const SepLabels& l, bool bf, const float* x, const float* y, const float* wg,
+                                  const float* wh, int64_t br, int64_t b, int64_t dx, int64_t dy, int64_t k,
+                                  const float* da, const float* dc, float* grad_x, float* grad_y, float* grad_wg,
+                                  float* grad_wh, hipStream_t st) {
+  return with_operand_type(bf, [&](auto* op) {
+    using OpT = OperandOf<decltype(op)>;
+    int rc = launch_gemm<OpT>(make_operand(da, k, 1), make_operand(wg, k, 1), br, dx, k,
+                              EpiStore{grad_x, dx, nullptr, 1.0f, 0}, st, l.dx);
+    if (rc) return rc;
+    rc = launch_gemm<OpT>(make_operand(x, 1, dx), make_operand(da, 1, k), dx, k, br, EpiStore{grad_wg, k, nullptr, 1.0f, 0},
+                          st, l.dwg);
+    if (rc) return rc;
+    rc = launch_gemm<OpT>(make_operand(dc, k, 1), make_operand(wh, k, 1), b, dy, k, EpiStore{grad_y, dy, nullptr, 1.0f, 0},
+                          st, l.dy);
+    if (rc) return rc;
+    return launch_gemm<OpT>(make_operand(y, 1, dy), make_operand(dc, 1, k), dy, k, b,
+                            EpiStore{grad_wh, k, nullptr, 1.0f, 0}, st, l.dwh);
+  });
 }
 
 static int check_separable(const char* fn, int64_t br, int64_t b, int64_t row_offset, int64_t dx, int64_t dy, int64_t k,
@@ -1146,35 +1253,27 @@ int mi_separable_fwd(const float* x, const float* y, const float* wg, const floa
   if (rc) return rc;
   MI_CHECK_ARG(estimator == MI_DV || estimator == MI_INFONCE, "mi_separable_fwd: unknown estimator %d", estimator);
   Workspace ws(workspace, workspace_bytes);
-  SeparablePlan p = plan_separable(ws, b_rows, b, d_img, d_txt, d_proj, precision);
+  const SeparablePlan p = plan_separable(ws, b_rows, b, d_img, d_txt, d_proj, precision);
   rc = ws_fits(ws, "mi_separable_fwd");
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (p.fast) {
+  if (p.path != MI_PATH_GENERIC) {
     rc = separable_prep_project(x, y, wg, wh, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt, d_proj, p, st);
     if (rc) return rc;
-    rc = separable_flash(sid_rows, sid_cols, b_rows, b, row_offset, d_proj, need_grad != 0, p, st);
+    rc = p.stage.launch(sid_rows, sid_cols, row_offset, need_grad != 0, st);
     if (rc) return rc;
-    return launch_finalize(p.rec[0], p.fl.n_rec[0], b, estimator, loss_out, stats, partials_out, st);
+    return launch_finalize(p.stage.rec[0], p.stage.fl.n_rec[0], b, estimator, loss_out, stats, partials_out, st);
   }
   // generic: projections on the strided-operand kernels (exact fp32 products in the parity mode), then the S = A C^T
   // score + LSE kernel of the bilinear path's generic form
-  const bool f32 = precision == MI_PREC_F32;
-  auto project = [&](const float* in, const float* w, int64_t rows, int64_t d, float* out, const char* what) {
-    return f32 ? launch_gemm<float>(make_operand(in, d, 1), make_operand(w, 1, d_proj), rows, d_proj, d,
-                                    EpiStore{out, d_proj, nullptr, 1.0f, 0}, st, what)
-               : launch_gemm<bf16_t>(make_operand(in, d, 1), make_operand(w, 1, d_proj), rows, d_proj, d,
-                                     EpiStore{out, d_proj, nullptr, 1.0f, 0}, st, what);
-  };
-  rc = project(x, wg, b_rows, d_img, p.a32, "separable A = X Wg (generic)");
+  const bool bf = precision != MI_PREC_F32;
+  rc = separable_project(kSepFwd, bf, x, y, wg, wh, b_rows, b, d_img, d_txt, d_proj, p.a32, p.c32, st);
   if (rc) return rc;
-  rc = project(y, wh, b, d_txt, p.c32, "separable C = Y Wh (generic)");
-  if (rc) return rc;
-  EpiScoreLse epi{sid_rows, sid_cols, row_offset, nullptr, p.partials};
-  rc = f32 ? launch_gemm<float>(make_operand((const float*)p.a32, d_proj, 1), make_operand((const float*)p.c32, d_proj, 1),
-                                b_rows, b, d_proj, epi, st, "separable score+LSE (generic)")
-           : launch_gemm<bf16_t>(make_operand((const float*)p.a32, d_proj, 1), make_operand((const float*)p.c32, d_proj, 1),
-                                 b_rows, b, d_proj, epi, st, "separable score+LSE (generic)");
+  rc = with_operand_type(bf, [&](auto* op) {
+    return launch_gemm<OperandOf<decltype(op)>>(
+        make_operand((const float*)p.a32, d_proj, 1), make_operand((const float*)p.c32, d_proj, 1), b_rows, b, d_proj,
+        EpiScoreLse{sid_rows, sid_cols, row_offset, nullptr, p.partials}, st, "separable score+LSE (generic)");
+  });
   if (rc) return rc;
   return launch_finalize(p.partials, p.n_partials, b, estimator, loss_out, stats, partials_out, st);
 }
@@ -1189,92 +1288,53 @@ int mi_separable_bwd(const float* x, const float* y, const float* wg, const floa
   int rc = check_separable("mi_separable_bwd", b_rows, b, row_offset, d_img, d_txt, d_proj, precision);
   if (rc) return rc;
   Workspace ws(workspace, workspace_bytes);
-  SeparablePlan p = plan_separable(ws, b_rows, b, d_img, d_txt, d_proj, precision);
+  const SeparablePlan p = plan_separable(ws, b_rows, b, d_img, d_txt, d_proj, precision);
   rc = ws_fits(ws, "mi_separable_bwd");
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int64_t br = b_rows, k = d_proj;
-  if (p.fast) {
+  if (p.path != MI_PATH_GENERIC) {
     if (!workspace_from_forward) {
       rc = separable_prep_project(x, y, wg, wh, sid_rows, sid_cols, br, b, row_offset, d_img, d_txt, k, p, st);
       if (rc) return rc;
-      rc = separable_flash(sid_rows, sid_cols, br, b, row_offset, k, true, p, st);
+      rc = p.stage.launch(sid_rows, sid_cols, row_offset, true, st);
       if (rc) return rc;
     }
     FlashReduceArgs ra{};
-    ra.j[0] = FlashReduceJob{p.slab[0], p.rec[0], p.fl.n_split[0], p.fl.n_rb[0], br, p.cb, b, row_offset, nullptr, p.dab,
-                             p.datb};
-    ra.j[1] = FlashReduceJob{p.slab[1], p.rec[1], p.fl.n_split[1], p.fl.n_rb[1], b, p.ab, br, -row_offset, nullptr, p.dcb,
-                             p.dctb};
+    p.stage.reduce_jobs(ra.j, row_offset, ReduceOut{nullptr, p.dab, p.datb}, ReduceOut{nullptr, p.dcb, p.dctb});
     ra.stats = stats;
     ra.grad_out = grad_out;
-    rc = launch_flash_reduce(ra, 2, k, p.fl.slab_f16, st, "separable dA, dC from the fused sums");
+    rc = launch_flash_reduce(ra, 2, k, p.stage.fl.slab_f16, st, "separable dA, dC from the fused sums");
     if (rc) return rc;
     // per modality: dW[a, c] = sum_i X[i, a] dA[i, c] (split over i into slabs) | dX[i, a] = sum_c dA[i, c] W[a, c]
-    auto pair = [&](const bf16_t* xt, const bf16_t* dat, const bf16_t* da, const bf16_t* wb, int64_t rows, int64_t d,
-                    float* slab, int splits, int64_t kchunk, float* gx, float* gw, const char* what) {
-      GemmBf16Args g{};
-      g.p[0] = GemmBf16Problem{xt, rows, dat, rows, d, k, rows};
-      g.p[1] = GemmBf16Problem{da, k, wb, k, rows, d, k};
-      g.n_problems = 2;
-      EpiStoreMulti e{};
-      e.out[0] = EpiOut{slab, k, d * k, nullptr, 0, nullptr, 0};
-      e.out[1] = EpiOut{gx, d, 0, nullptr, 0, nullptr, 0};
-      const int sp[2] = {splits, 1};
-      const int64_t ch[2] = {kchunk, k};
-      int r = launch_gemm_bf16_flat(g, sp, ch, e, st, what);
-      if (r == MI_EINVAL) {
-        EpiStoreMulti e1{};
-        e1.out[0] = e.out[0];
-        r = launch_gemm_bf16(one_problem(xt, rows, dat, rows, d, k, rows, kchunk), splits, e1, st, what);
-        if (r) return r;
-        e1.out[0] = e.out[1];
-        r = launch_gemm_bf16(one_problem(da, k, wb, k, rows, d, k), 1, e1, st, what);
-      }
-      if (r) return r;
-      return launch_slab_reduce_ld(slab, splits, d, k, gw, k, st, "slab_reduce_ld_kernel");
-    };
-    rc = pair(p.xtb, p.datb, p.dab, p.gb, br, d_img, p.wg_slab, p.wg_splits, p.wg_kchunk, grad_x, grad_wg,
-              "separable dWg = X^T dA | dX = dA Wg^T");
+    const char* const wg_what = "separable dWg = X^T dA | dX = dA Wg^T";
+    const char* const wh_what = "separable dWh = Y^T dC | dY = dC Wh^T";
+    rc = launch_dw_dx(DwDxPair{p.xtb, p.datb, p.dab, p.gb, br, d_img, k, 1, p.wg_slab, p.wg_splits, p.wg_kchunk}, grad_x,
+                      grad_wg, st, {wg_what, wg_what, wg_what});
     if (rc) return rc;
-    return pair(p.ytb, p.dctb, p.dcb, p.hb, b, d_txt, p.wh_slab, p.wh_splits, p.wh_kchunk, grad_y, grad_wh,
-                "separable dWh = Y^T dC | dY = dC Wh^T");
+    return launch_dw_dx(DwDxPair{p.ytb, p.dctb, p.dcb, p.hb, b, d_txt, k, 1, p.wh_slab, p.wh_splits, p.wh_kchunk}, grad_y,
+                        grad_wh, st, {wh_what, wh_what, wh_what});
   }
-  // generic path: recompute the projections (cheap), G from recomputed scores, then six strided-operand products
-  const bool f32 = precision == MI_PREC_F32;
-#define MI_SEP_GEMM(A, B, M, N, K, OUT, LD, WHAT)                                                                    \
-  do {                                                                                                               \
-    rc = f32 ? launch_gemm<float>(A, B, M, N, K, EpiStore{OUT, LD, nullptr, 1.0f, 0}, st, WHAT)                       \
-             : launch_gemm<bf16_t>(A, B, M, N, K, EpiStore{OUT, LD, nullptr, 1.0f, 0}, st, WHAT);                     \
-    if (rc) return rc;                                                                                               \
-  } while (0)
-  MI_SEP_GEMM(make_operand(x, d_img, 1), make_operand(wg, 1, k), br, k, d_img, p.a32, k, "separable A = X Wg (generic, bwd)");
-  MI_SEP_GEMM(make_operand(y, d_txt, 1), make_operand(wh, 1, k), b, k, d_txt, p.c32, k, "separable C = Y Wh (generic, bwd)");
-  const float* a = p.a32;
-  const float* c = p.c32;
-  if (f32) {
-    float* g = (float*)p.g;
-    rc = launch_gemm<float>(make_operand(a, k, 1), make_operand(c, k, 1), br, b, k,
-                            EpiGradScore<float>{sid_rows, sid_cols, row_offset, stats, grad_out, g}, st, "separable G (generic)");
-    if (rc) return rc;
-    MI_SEP_GEMM(make_operand((const float*)g, b, 1), make_operand(c, 1, k), br, k, b, p.da32, k, "separable dA = G C (generic)");
-    MI_SEP_GEMM(make_operand((const float*)g, 1, b), make_operand(a, 1, k), b, k, br, p.dc32, k, "separable dC = G^T A (generic)");
-  } else {
-    bf16_t* g = (bf16_t*)p.g;
-    rc = launch_gemm<bf16_t>(make_operand(a, k, 1), make_operand(c, k, 1), br, b, k,
-                             EpiGradScore<bf16_t>{sid_rows, sid_cols, row_offset, stats, grad_out, g}, st, "separable G (generic)");
-    if (rc) return rc;
-    MI_SEP_GEMM(make_operand((const bf16_t*)g, b, 1), make_operand(c, 1, k), br, k, b, p.da32, k, "separable dA = G C (generic)");
-    MI_SEP_GEMM(make_operand((const bf16_t*)g, 1, b), make_operand(a, 1, k), b, k, br, p.dc32, k, "separable dC = G^T A (generic)");
-  }
-  const float* da = p.da32;
-  const float* dc = p.dc32;
-  MI_SEP_GEMM(make_operand(da, k, 1), make_operand(wg, k, 1), br, d_img, k, grad_x, d_img, "separable dX = dA Wg^T (generic)");
-  MI_SEP_GEMM(make_operand(x, 1, d_img), make_operand(da, 1, k), d_img, k, br, grad_wg, k, "separable dWg = X^T dA (generic)");
-  MI_SEP_GEMM(make_operand(dc, k, 1), make_operand(wh, k, 1), b, d_txt, k, grad_y, d_txt, "separable dY = dC Wh^T (generic)");
-  MI_SEP_GEMM(make_operand(y, 1, d_txt), make_operand(dc, 1, k), d_txt, k, b, grad_wh, k, "separable dWh = Y^T dC (generic)");
-#undef MI_SEP_GEMM
-  return MI_OK;
+  // generic path: recompute the projections (cheap), G from recomputed scores, dA = G C and dC = G^T A, back-projections
+  const bool bf = precision != MI_PREC_F32;
+  rc = separable_project(kSepBwd, bf, x, y, wg, wh, br, b, d_img, d_txt, k, p.a32, p.c32, st);
+  if (rc) return rc;
+  rc = with_operand_type(bf, [&](auto* op) {
+    using OpT = OperandOf<decltype(op)>;  // G is stored in the operand type
+    const float *a = p.a32, *c = p.c32;
+    OpT* g = (OpT*)p.g;
+    const EpiGradScore<OpT> eg{sid_rows, sid_cols, row_offset, stats, grad_out, g};
+    int r = launch_gemm<OpT>(make_operand(a, k, 1), make_operand(c, k, 1), br, b, k, eg, st, "separable G (generic)");
+    if (r) return r;
+    r = launch_gemm<OpT>(make_operand((const OpT*)g, b, 1), make_operand(c, 1, k), br, k, b,
+                         EpiStore{p.da32, k, nullptr, 1.0f, 0}, st, "separable dA = G C (generic)");
+    if (r) return r;
+    return launch_gemm<OpT>(make_operand((const OpT*)g, 1, b), make_operand(a, 1, k), b, k, br,
+                            EpiStore{p.dc32, k, nullptr, 1.0f, 0}, st, "separable dC = G^T A (generic)");
+  });
+  if (rc) return rc;
+  return separable_project_back(kSepBwd, bf, x, y, wg, wh, br, b, d_img, d_txt, k, p.da32, p.dc32, grad_x, grad_y,
+                                grad_wg, grad_wh, st);
 }
 
 }  // extern "C"
@@ -1296,34 +1356,19 @@ extern "C" int mi_separable_step(const float* x, const float* y, const float* wg
   if (rc) return rc;
   MI_CHECK_ARG(estimator == MI_DV || estimator == MI_INFONCE, "mi_separable_step: unknown estimator %d", estimator);
   Workspace ws(workspace, workspace_bytes);
-  SeparablePlan p = plan_separable(ws, b, b, d_img, d_txt, d_proj, precision);
+  const SeparablePlan p = plan_separable(ws, b, b, d_img, d_txt, d_proj, precision);
   rc = ws_fits(ws, "mi_separable_step");
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (p.fast && p.tail) {
+  if (p.path == MI_PATH_FUSED_TAIL) {
     rc = separable_prep_project_fused(x, y, wg, wh, sid, sid, b, b, 0, d_img, d_txt, d_proj, p, st);
     if (rc == MI_EINVAL) rc = separable_prep_project(x, y, wg, wh, sid, sid, b, b, 0, d_img, d_txt, d_proj, p, st);
     if (rc) return rc;
-    rc = separable_flash(sid, sid, b, b, 0, d_proj, true, p, st);
+    rc = p.stage.launch(sid, sid, 0, true, st);
     if (rc) return rc;
-    FlashTailArgs ta{};
-    ta.j[0] = FlashReduceJob{p.slab[0], p.rec[0], p.fl.n_split[0], p.fl.n_rb[0], b, p.cb, b, 0, nullptr, nullptr, nullptr};
-    ta.j[1] = FlashReduceJob{p.slab[1], p.rec[1], p.fl.n_split[1], p.fl.n_rb[1], b, p.ab, b, 0, nullptr, nullptr, nullptr};
-    ta.stats = stats;
-    ta.grad_out = grad_out;
-    ta.merge_rec = p.rec[0];
-    ta.n_merge = p.fl.n_rec[0];
-    ta.n_pos = b;
-    ta.estimator = estimator;
-    ta.loss_out = loss_out;
-    ta.stats_out = stats;
-    ta.partials_out = partials_out;
-    ta.w_frag = p.gfb;  ta.dx = d_img;  ta.grad_x = grad_x;  ta.dtt_frag = p.datfb;
-    ta.w_frag1 = p.hfb; ta.dx1 = d_txt; ta.grad_x1 = grad_y; ta.dtt_frag1 = p.dctfb;
-    rc = launch_flash_tail(ta, d_proj, p.fl.slab_f16, true, st, "separable sums -> loss, dA, dC | dX = dA Wg^T | dY = dC Wh^T");
-    if (rc) return rc;
-    const DwArgs g{p.xtfb, p.datfb, d_img, d_proj, b, grad_wg}, h{p.ytfb, p.dctfb, d_txt, d_proj, b, grad_wh};
-    return launch_bilinear_dw(g, st, "separable dWg = X^T dA | dWh = Y^T dC", &h);
+    const TailMerge m{estimator, loss_out, stats, partials_out};
+    const TailSide g{p.gfb, d_img, grad_x, p.datfb, p.xtfb, grad_wg}, h{p.hfb, d_txt, grad_y, p.dctfb, p.ytfb, grad_wh};
+    return bilinear_tail(p.stage, 0, stats, grad_out, g, &h, nullptr, &m, st);
   }
   rc = mi_separable_fwd(x, y, wg, wh, sid, sid, b, b, 0, d_img, d_txt, d_proj, estimator, precision, 1, loss_out, stats,
                         partials_out, workspace, workspace_bytes, stream);
@@ -1334,10 +1379,8 @@ extern "C" int mi_separable_step(const float* x, const float* y, const float* wg
 
 extern "C" int mi_separable_path(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int precision) {
   if (b_rows <= 0 || b <= 0 || d_img <= 0 || d_txt <= 0 || d_proj <= 0) return MI_EINVAL;
-  char* fake = reinterpret_cast<char*>(uintptr_t(1) << 20);
-  mi::Workspace ws(fake, ~size_t(0) >> 1);
-  const mi::SeparablePlan p = mi::plan_separable(ws, b_rows, b, d_img, d_txt, d_proj, precision);
-  return p.fast ? (p.tail ? MI_PATH_FUSED_TAIL : MI_PATH_FUSED) : MI_PATH_GENERIC;
+  mi::Workspace ws(nullptr, 0);
+  return mi::plan_separable(ws, b_rows, b, d_img, d_txt, d_proj, precision).path;
 }
 
 #ifdef MI_STAMPS
@@ -1386,12 +1429,9 @@ struct NceEst {
   static constexpr const char* kScores16 = "nce score + row / column records";
   static constexpr const char* kG = "nce G (generic)";
   static constexpr const char* kG16 = "nce G";
-  static constexpr const char* kA = "nce separable A = X Wg";
-  static constexpr const char* kC = "nce separable C = Y Wh";
-  static constexpr const char* kDX = "nce separable dX = dA Wg^T";
-  static constexpr const char* kDWg = "nce separable dWg = X^T dA";
-  static constexpr const char* kDY = "nce separable dY = dC Wh^T";
-  static constexpr const char* kDWh = "nce separable dWh = Y^T dC";
+  static constexpr SepLabels kSep = {"nce separable A = X Wg",      "nce separable C = Y Wh",
+                                     "nce separable dX = dA Wg^T",  "nce separable dWg = X^T dA",
+                                     "nce separable dY = dC Wh^T",  "nce separable dWh = Y^T dC"};
 };
 
 struct FdivEst {
@@ -1409,12 +1449,9 @@ struct FdivEst {
   static constexpr const char* kScores16 = "fdiv score + records";
   static constexpr const char* kG = "fdiv G (generic)";
   static constexpr const char* kG16 = "fdiv G";
-  static constexpr const char* kA = "fdiv separable A = X Wg";
-  static constexpr const char* kC = "fdiv separable C = Y Wh";
-  static constexpr const char* kDX = "fdiv separable dX = dA Wg^T";
-  static constexpr const char* kDWg = "fdiv separable dWg = X^T dA";
-  static constexpr const char* kDY = "fdiv separable dY = dC Wh^T";
-  static constexpr const char* kDWh = "fdiv separable dWh = Y^T dC";
+  static constexpr SepLabels kSep = {"fdiv separable A = X Wg",     "fdiv separable C = Y Wh",
+                                     "fdiv separable dX = dA Wg^T", "fdiv separable dWg = X^T dA",
+                                     "fdiv separable dY = dC Wh^T", "fdiv separable dWh = Y^T dC"};
 };
 
 static bool chain_16bit_ok(int64_t br, int64_t b, int64_t dx, int64_t dy, int precision) {
@@ -1448,7 +1485,7 @@ static int chain_scores(const float* x, const float* y, const float* w, const in
     const int x3 = p.x3;
     int rc;
     if (w) {
-      rc = fast_prep_and_t(x, y, w, sid_rows, sid_cols, br, b, row_offset, dx, dy, p, st);  // p.fl.ok is false
+      rc = fast_prep_and_t(x, y, w, sid_rows, sid_cols, br, b, row_offset, dx, dy, p, st);  // (no fused stage in this plan)
     } else {
       // X takes the place of T (A operand of the scores, B operand of dY = G^T T)
       const int ra = x3 == 3 ? 1 : 0, rb = x3 == 3 ? 2 : 0;
@@ -1461,8 +1498,8 @@ static int chain_scores(const float* x, const float* y, const float* w, const in
     return launch_gemm_bf16(one_problem(p.tb, x3 * dy, p.yb, x3 * dy, br, b, x3 * dy), 1, typename Est::Stats16{so}, st,
                             Est::kScores16);
   }
-  auto generic = [&](auto* op) {
-    using OpT = std::remove_pointer_t<decltype(op)>;
+  return with_operand_type(precision == MI_PREC_BF16, [&](auto* op) {
+    using OpT = OperandOf<decltype(op)>;
     const float* t = x;
     if (w) {
       const int rc =
@@ -1472,8 +1509,7 @@ static int chain_scores(const float* x, const float* y, const float* w, const in
     }
     return launch_gemm<OpT>(make_operand(t, dy, 1), make_operand(y, dy, 1), br, b, dy, typename Est::Stats{so}, st,
                             Est::kScores);
-  };
-  return precision == MI_PREC_BF16 ? generic((bf16_t*)nullptr) : generic((float*)nullptr);
+  });
 }
 
 // The gradient half: the G GEMM of the row block with Est's gradient epilogue (recomputed scores; T is chain_scores' in
@@ -1489,54 +1525,15 @@ static int chain_grads(const float* x, const float* y, const float* w, int64_t b
     if (rc) return rc;
     return bilinear_bwd_from_g(br, b, dx, dy, grad_x, grad_y, grad_w, w != nullptr, p, st);
   }
-  auto generic = [&](auto* op) {
-    using OpT = std::remove_pointer_t<decltype(op)>;  // G is stored in the operand type
+  return with_operand_type(precision == MI_PREC_BF16, [&](auto* op) {
+    using OpT = OperandOf<decltype(op)>;  // G is stored in the operand type
     const float* t = w ? p.t : x;
     OpT* g = (OpT*)p.g;
     const int rc = launch_gemm<OpT>(make_operand(t, dy, 1), make_operand(y, dy, 1), br, b, dy,
                                     typename Est::template Grad<OpT>{gi, g}, st, Est::kG);
     if (rc) return rc;
     return generic_bwd_from_g<OpT, OpT>(x, y, w, t, g, br, b, dx, dy, grad_x, grad_y, grad_w, p, st);
-  };
-  return precision == MI_PREC_BF16 ? generic((bf16_t*)nullptr) : generic((float*)nullptr);
-}
-
-// The separable critic on the chain: A = X Wg [br][k], C = Y Wh [b][k] (a row block projects all b text rows) and
-// their gradients on the strided-operand kernels, bf16 operands in the bf16 mode (bf), exact fp32 products otherwise
-template <typename Est>
-static int separable_project(bool bf, const float* x, const float* y, const float* wg, const float* wh, int64_t br,
-                             int64_t b, int64_t dx, int64_t dy, int64_t k, float* a, float* c, hipStream_t st) {
-  auto run = [&](auto* op) {
-    using OpT = std::remove_pointer_t<decltype(op)>;
-    const int rc = launch_gemm<OpT>(make_operand(x, dx, 1), make_operand(wg, 1, k), br, k, dx,
-                                    EpiStore{a, k, nullptr, 1.0f, 0}, st, Est::kA);
-    if (rc) return rc;
-    return launch_gemm<OpT>(make_operand(y, dy, 1), make_operand(wh, 1, k), b, k, dy, EpiStore{c, k, nullptr, 1.0f, 0},
-                            st, Est::kC);
-  };
-  return bf ? run((bf16_t*)nullptr) : run((float*)nullptr);
-}
-
-// dA [br][k] -> dX = dA Wg^T and (the row block's part of) dWg = X^T dA; dC [b][k] -> (parts of) dY = dC Wh^T, dWh = Y^T dC
-template <typename Est>
-static int separable_project_back(bool bf, const float* x, const float* y, const float* wg, const float* wh, int64_t br,
-                                  int64_t b, int64_t dx, int64_t dy, int64_t k, const float* da, const float* dc,
-                                  float* grad_x, float* grad_y, float* grad_wg, float* grad_wh, hipStream_t st) {
-  auto run = [&](auto* op) {
-    using OpT = std::remove_pointer_t<decltype(op)>;
-    int rc = launch_gemm<OpT>(make_operand(da, k, 1), make_operand(wg, k, 1), br, dx, k,
-                              EpiStore{grad_x, dx, nullptr, 1.0f, 0}, st, Est::kDX);
-    if (rc) return rc;
-    rc = launch_gemm<OpT>(make_operand(x, 1, dx), make_operand(da, 1, k), dx, k, br, EpiStore{grad_wg, k, nullptr, 1.0f, 0},
-                          st, Est::kDWg);
-    if (rc) return rc;
-    rc = launch_gemm<OpT>(make_operand(dc, k, 1), make_operand(wh, k, 1), b, dy, k, EpiStore{grad_y, dy, nullptr, 1.0f, 0},
-                          st, Est::kDY);
-    if (rc) return rc;
-    return launch_gemm<OpT>(make_operand(y, 1, dy), make_operand(dc, 1, k), dy, k, b,
-                            EpiStore{grad_wh, k, nullptr, 1.0f, 0}, st, Est::kDWh);
-  };
-  return bf ? run((bf16_t*)nullptr) : run((float*)nullptr);
+  });
 }
 
 // The separable entry points' workspace: A, C, dA, dC, then the plan of the chain on (A, C)
@@ -1565,7 +1562,7 @@ struct NceBilinearPlan {
 };
 static NceBilinearPlan plan_nce_bilinear(Workspace& ws, int64_t b, int64_t dx, int64_t dy, int precision) {
   NceBilinearPlan n{};
-  n.p = plan_bilinear(ws, b, b, dx, dy, precision, true);
+  n.p = plan_bilinear(ws, b, b, dx, dy, precision, true, true);
   n.q = plan_nce(ws, b);
   n.bytes = ws.off;
   return n;
@@ -1586,7 +1583,7 @@ struct NceShardBilinearPlan {
 static NceShardBilinearPlan plan_nce_shard_bilinear(Workspace& ws, int64_t br, int64_t b, int64_t dx, int64_t dy,
                                                     int precision) {
   NceShardBilinearPlan n{};
-  n.p = plan_bilinear(ws, br, b, dx, dy, precision, true);
+  n.p = plan_bilinear(ws, br, b, dx, dy, precision, true, true);
   n.q = plan_nce_shard(ws, br, b);
   n.bytes = ws.off;
   return n;
@@ -1605,7 +1602,7 @@ struct FdivBilinearPlan {
 };
 static FdivBilinearPlan plan_fdiv_bilinear(Workspace& ws, int64_t b, int64_t dx, int64_t dy, int precision) {
   FdivBilinearPlan n{};
-  n.p = plan_bilinear(ws, b, b, dx, dy, precision, true);
+  n.p = plan_bilinear(ws, b, b, dx, dy, precision, true, true);
   n.n_t = (b + 63) / 64;
   n.rec = ws.take<FdivRec>(n.n_t * n.n_t);
   n.stats = ws.take<mi_stats>(1);
@@ -1676,7 +1673,7 @@ int mi_nce_separable_step(const float* x, const float* y, const float* wg, const
   const int64_t k = d_proj;
   const NceBilinearPlan& n = sp.n;
   const bool bf = precision == MI_PREC_BF16;
-  rc = separable_project<NceEst>(bf, x, y, wg, wh, b, b, d_img, d_txt, k, sp.a, sp.c, st);
+  rc = separable_project(NceEst::kSep, bf, x, y, wg, wh, b, b, d_img, d_txt, k, sp.a, sp.c, st);
   if (rc) return rc;
   rc = chain_scores<NceEst>(sp.a, sp.c, nullptr, sid, sid, b, b, 0, k, k, precision, nce_stats_out(n.q, sid), n.p, st);
   if (rc) return rc;
@@ -1685,8 +1682,8 @@ int mi_nce_separable_step(const float* x, const float* y, const float* wg, const
   rc = chain_grads<NceEst>(sp.a, sp.c, nullptr, b, b, k, k, precision, nce_grad_in(sid, n.q.r, n.q.c, grad_out, b, mode),
                            sp.da, sp.dc, nullptr, n.p, st);
   if (rc) return rc;
-  return separable_project_back<NceEst>(bf, x, y, wg, wh, b, b, d_img, d_txt, k, sp.da, sp.dc, grad_x, grad_y, grad_wg,
-                                        grad_wh, st);
+  return separable_project_back(NceEst::kSep, bf, x, y, wg, wh, b, b, d_img, d_txt, k, sp.da, sp.dc, grad_x, grad_y, grad_wg,
+                                grad_wh, st);
 }
 
 /* Row blocks of a sharded batch (include/mi_critic.h): forward -> part, merge of the gathered parts -> loss and c,
@@ -1782,7 +1779,8 @@ int mi_nce_separable_shard_fwd(const float* x, const float* y, const float* wg, 
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int64_t k = d_proj;
-  rc = separable_project<NceEst>(precision == MI_PREC_BF16, x, y, wg, wh, b_rows, b, d_img, d_txt, k, sp.a, sp.c, st);
+  rc = separable_project(NceEst::kSep, precision == MI_PREC_BF16, x, y, wg, wh, b_rows, b, d_img, d_txt, k, sp.a, sp.c,
+                         st);
   if (rc) return rc;
   rc = chain_scores<NceEst>(sp.a, sp.c, nullptr, sid_rows, sid_cols, b_rows, b, row_offset, k, k, precision,
                             nce_stats_out(sp.n.q, sid_rows, sid_cols, row_offset), sp.n.p, st);
@@ -1812,7 +1810,7 @@ int mi_nce_separable_shard_bwd(const float* x, const float* y, const float* wg, 
                            sp.dc, nullptr, sp.n.p, st);
   if (rc) return rc;
   // dA -> the rank's dX and its partial dWg; the rank's partial dC (all b text rows) -> partial dY and dWh
-  return separable_project_back<NceEst>(precision == MI_PREC_BF16, x, y, wg, wh, b_rows, b, d_img, d_txt, k, sp.da, sp.dc,
+  return separable_project_back(NceEst::kSep, precision == MI_PREC_BF16, x, y, wg, wh, b_rows, b, d_img, d_txt, k, sp.da, sp.dc,
                                         grad_x, grad_y, grad_wg, grad_wh, st);
 }
 
@@ -1919,7 +1917,7 @@ int mi_fdiv_separable_step(const float* x, const float* y, const float* wg, cons
   const FdivBilinearPlan& n = sp.n;
   const bool bf = precision == MI_PREC_BF16;
   if (!stats) stats = n.stats;
-  rc = separable_project<FdivEst>(bf, x, y, wg, wh, b, b, d_img, d_txt, k, sp.a, sp.c, st);
+  rc = separable_project(FdivEst::kSep, bf, x, y, wg, wh, b, b, d_img, d_txt, k, sp.a, sp.c, st);
   if (rc) return rc;
   rc = chain_scores<FdivEst>(sp.a, sp.c, nullptr, sid, sid, b, b, 0, k, k, precision,
                              FdivStatsOut{sid, sid, 0, mode, n.rec, n.n_t}, n.p, st);
@@ -1929,8 +1927,8 @@ int mi_fdiv_separable_step(const float* x, const float* y, const float* wg, cons
   rc = chain_grads<FdivEst>(sp.a, sp.c, nullptr, b, b, k, k, precision, FdivGradIn{sid, sid, 0, mode, stats, grad_out},
                             sp.da, sp.dc, nullptr, n.p, st);
   if (rc) return rc;
-  return separable_project_back<FdivEst>(bf, x, y, wg, wh, b, b, d_img, d_txt, k, sp.da, sp.dc, grad_x, grad_y, grad_wg,
-                                         grad_wh, st);
+  return separable_project_back(FdivEst::kSep, bf, x, y, wg, wh, b, b, d_img, d_txt, k, sp.da, sp.dc, grad_x, grad_y, grad_wg,
+                                grad_wh, st);
 }
 
 }  // extern "C"
