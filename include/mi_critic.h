@@ -20,6 +20,8 @@
  *                            (main_utils.py:105); the reference has no such loss
  *   mi_fdiv_*             <- an extension: the Jensen-Shannon (Deep InfoMax) and NWJ bounds on the reference's pairs
  *                            (main_utils.py:88-110), for every critic; the reference has "dv" and "infonce" only
+ *   mi_rank_*             <- an extension: image-report retrieval ranks (for recall@K, median rank, MRR) of every
+ *                            critic under the same masking rule; an evaluation, not an estimator
  *
  * Conventions
  *   - every pointer is a DEVICE pointer unless the name ends in _host; all tensors are dense row-major
@@ -420,6 +422,32 @@ int mi_fdiv_concat_mlp_bwd(const float* x, const float* y, const float* w1, cons
                            const float* grad_out, const float* scores, float* grad_x, float* grad_y, float* grad_w1,
                            float* grad_b1, float* grad_w2, float* grad_b2, float* grad_w3, float* grad_b3,
                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- image-report retrieval ranks -------------------------------------------------------- */
+/* S[i, j] = critic(img_i, txt_j) over b pairs, positives (i, i); a pair i != j with sid_i == sid_j is dropped (neither a
+ * hit nor a miss), as everywhere above:
+ *   rank_i2t[i] = #{ j : sid_j != sid_i and S[i, j] > S[i, i] }      image -> report
+ *   rank_t2i[j] = #{ i : sid_i != sid_j and S[i, j] > S[j, j] }      report -> image
+ * 0-based int32 [b]; strictly greater, so a tie counts for the true pair; every id equal: all zeros.  recall@K is the
+ * mean of rank < K.  Integer counts: exact and identical from call to call.  rank_i2t and rank_t2i may each be NULL (one
+ * direction alone); both NULL is MI_EINVAL.  Not an estimator: no mode, no loss, no gradients. */
+/* a caller's fp32 [b, b] score matrix (any critic); no workspace */
+int mi_rank_matrix(const float* scores, const int64_t* sid, int64_t b, int32_t* rank_i2t, int32_t* rank_t2i, void* stream);
+/* Bilinear S = (X W) Y^T (w == NULL: X Y^T, d_img == d_txt) and separable S = (X Wg)(Y Wh)^T critics on the forward half
+ * of the GEMM chain of mi_nce_*_step: prep and T = X W, the diagonal S[i, i] from the score GEMM's own operands (bf16:
+ * bf16 T and Y, fp32 accumulation; bf16x3: the split parts), then the score sweep, whose epilogue counts per 64 x 64 tile
+ * and adds the counts to the ranks.  No score matrix, G or per-tile buffer: the workspace grows linearly in b.
+ * diag_out (optional, [b]) receives S[i, i].  precision: MI_PREC_F32 (exact fp32 products), MI_PREC_BF16 /
+ * MI_PREC_BF16X3 (16-bit chain where b and the widths are multiples of 8, generic kernels otherwise); MI_PREC_FP8 / F16
+ * / F16X3 are rejected (MI_EINVAL). */
+size_t mi_rank_bilinear_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int precision);
+int mi_rank_bilinear(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t d_img,
+                     int64_t d_txt, int precision, int32_t* rank_i2t, int32_t* rank_t2i, float* diag_out, void* workspace,
+                     size_t workspace_bytes, void* stream);
+size_t mi_rank_separable_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int precision);
+int mi_rank_separable(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid, int64_t b,
+                      int64_t d_img, int64_t d_txt, int64_t d_proj, int precision, int32_t* rank_i2t, int32_t* rank_t2i,
+                      float* diag_out, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

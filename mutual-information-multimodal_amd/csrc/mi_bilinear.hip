@@ -20,6 +20,7 @@
 #include "mi_fp8.h"
 #include "mi_nce.h"
 #include "mi_fdiv.h"
+#include "mi_rank.h"
 
 namespace mi {
 
@@ -1407,6 +1408,8 @@ extern "C" int mi_debug_set_wall(void* buf) {
 // nce_rank_part (a row block's part for the cross-rank merge) or launch_fdiv_finalize.  The fused B x B kernel is not
 // used: per-row normalisation needs r_i before any row's P tile can be weighted, and the fdiv bounds keep one record per
 // 64 x 64 score tile.  The separable critic runs the chain on its projections A = X Wg, C = Y Wh with W = I.
+// The retrieval ranks (mi_rank.h) run the forward half alone, with the diagonal S[i, i] computed
+// between prep / T and the score GEMM, whose epilogue counts the scores above it.
 namespace mi {
 
 // Est: what an estimator puts into the chain -- the statistics epilogue of the score GEMM and the gradient epilogue of
@@ -1454,6 +1457,20 @@ struct FdivEst {
                                      "fdiv separable dY = dC Wh^T", "fdiv separable dWh = Y^T dC"};
 };
 
+// Retrieval ranks (mi_rank.h) are not an estimator, but they run the forward half of the chain:
+// the score GEMM's epilogue counts instead of reducing.  No mode, no gradient half.
+struct RankEst {
+  using StatsOut = RankOut;
+  using Stats = EpiRankCounts;
+  using Stats16 = EpiRankCounts;
+  static int check_mode(const char*, int) { return MI_OK; }
+  static constexpr const char* kName = "the retrieval ranks";
+  static constexpr const char* kT = "rank T = X W (generic)";
+  static constexpr const char* kScores = "rank score + counts (generic)";
+  static constexpr const char* kScores16 = "rank score + counts";
+  static constexpr SepLabels kSep = {"rank separable A = X Wg", "rank separable C = Y Wh"};
+};
+
 static bool chain_16bit_ok(int64_t br, int64_t b, int64_t dx, int64_t dy, int precision) {
   return (precision == MI_PREC_BF16 || precision == MI_PREC_BF16X3) && br % 8 == 0 && b % 8 == 0 && dx % 8 == 0 &&
          dy % 8 == 0;
@@ -1475,41 +1492,51 @@ static int chain_check(const char* fn, int64_t br, int64_t b, int64_t row_offset
   return MI_OK;
 }
 
-// The forward half: prep / T = X W (w == nullptr: S = X Y^T), then the score GEMM of the row block with Est's
-// statistics epilogue writing to `so`
+// The forward half, first part: prep / T = X W (w == nullptr: S = X Y^T), which leaves the score GEMM's operands in the
+// workspace (16-bit chain: p.tb, p.yb) or in p.t (generic kernels with a weight)
 template <typename Est>
-static int chain_scores(const float* x, const float* y, const float* w, const int64_t* sid_rows, const int64_t* sid_cols,
-                        int64_t br, int64_t b, int64_t row_offset, int64_t dx, int64_t dy, int precision,
-                        const typename Est::StatsOut& so, const BilinearPlan& p, hipStream_t st) {
+static int chain_operands(const float* x, const float* y, const float* w, const int64_t* sid_rows, const int64_t* sid_cols,
+                          int64_t br, int64_t b, int64_t row_offset, int64_t dx, int64_t dy, int precision,
+                          const BilinearPlan& p, hipStream_t st) {
+  if (chain_16bit_ok(br, b, dx, dy, precision)) {
+    if (w) return fast_prep_and_t(x, y, w, sid_rows, sid_cols, br, b, row_offset, dx, dy, p, st);  // (no fused stage in this plan)
+    // X takes the place of T (A operand of the scores, B operand of dY = G^T T)
+    const int ra = p.x3 == 3 ? 1 : 0, rb = p.x3 == 3 ? 2 : 0;
+    CvtJobs jobs{};
+    jobs.j[0] = CvtJob{x, br, dx, p.tb, p.ttb, 0, 0, nullptr, ra, rb};
+    jobs.j[1] = CvtJob{y, b, dy, p.yb, p.ytb, 0, 0, nullptr, rb, rb};
+    return launch_cvt_transpose3(jobs, st, "nce prep X Y");
+  }
+  if (!w) return MI_OK;
+  return with_operand_type(precision == MI_PREC_BF16, [&](auto* op) {
+    using OpT = OperandOf<decltype(op)>;
+    return generic_gemm_store<OpT>(make_operand(x, dx, 1), make_operand(w, 1, dy), br, dy, dx, p.t, dy, p, st, Est::kT);
+  });
+}
+
+// ... second part: the score GEMM of the row block on those operands with Est's statistics epilogue writing to `so`
+template <typename Est>
+static int chain_sweep(const float* x, const float* y, const float* w, int64_t br, int64_t b, int64_t dx, int64_t dy,
+                       int precision, const typename Est::StatsOut& so, const BilinearPlan& p, hipStream_t st) {
   if (chain_16bit_ok(br, b, dx, dy, precision)) {
     const int x3 = p.x3;
-    int rc;
-    if (w) {
-      rc = fast_prep_and_t(x, y, w, sid_rows, sid_cols, br, b, row_offset, dx, dy, p, st);  // (no fused stage in this plan)
-    } else {
-      // X takes the place of T (A operand of the scores, B operand of dY = G^T T)
-      const int ra = x3 == 3 ? 1 : 0, rb = x3 == 3 ? 2 : 0;
-      CvtJobs jobs{};
-      jobs.j[0] = CvtJob{x, br, dx, p.tb, p.ttb, 0, 0, nullptr, ra, rb};
-      jobs.j[1] = CvtJob{y, b, dy, p.yb, p.ytb, 0, 0, nullptr, rb, rb};
-      rc = launch_cvt_transpose3(jobs, st, "nce prep X Y");
-    }
-    if (rc) return rc;
     return launch_gemm_bf16(one_problem(p.tb, x3 * dy, p.yb, x3 * dy, br, b, x3 * dy), 1, typename Est::Stats16{so}, st,
                             Est::kScores16);
   }
   return with_operand_type(precision == MI_PREC_BF16, [&](auto* op) {
     using OpT = OperandOf<decltype(op)>;
-    const float* t = x;
-    if (w) {
-      const int rc =
-          generic_gemm_store<OpT>(make_operand(x, dx, 1), make_operand(w, 1, dy), br, dy, dx, p.t, dy, p, st, Est::kT);
-      if (rc) return rc;
-      t = p.t;
-    }
-    return launch_gemm<OpT>(make_operand(t, dy, 1), make_operand(y, dy, 1), br, b, dy, typename Est::Stats{so}, st,
-                            Est::kScores);
+    return launch_gemm<OpT>(make_operand(w ? p.t : x, dy, 1), make_operand(y, dy, 1), br, b, dy, typename Est::Stats{so},
+                            st, Est::kScores);
   });
+}
+
+template <typename Est>
+static int chain_scores(const float* x, const float* y, const float* w, const int64_t* sid_rows, const int64_t* sid_cols,
+                        int64_t br, int64_t b, int64_t row_offset, int64_t dx, int64_t dy, int precision,
+                        const typename Est::StatsOut& so, const BilinearPlan& p, hipStream_t st) {
+  const int rc = chain_operands<Est>(x, y, w, sid_rows, sid_cols, br, b, row_offset, dx, dy, precision, p, st);
+  if (rc) return rc;
+  return chain_sweep<Est>(x, y, w, br, b, dx, dy, precision, so, p, st);
 }
 
 // The gradient half: the G GEMM of the row block with Est's gradient epilogue (recomputed scores; T is chain_scores' in
@@ -1611,6 +1638,72 @@ static FdivBilinearPlan plan_fdiv_bilinear(Workspace& ws, int64_t b, int64_t dx,
 }
 static SeparableChainPlan<FdivBilinearPlan> plan_fdiv_separable(Workspace& ws, int64_t b, int64_t k, int precision) {
   return plan_separable_chain(ws, b, b, k, [&] { return plan_fdiv_bilinear(ws, b, k, k, precision); });
+}
+
+// Retrieval ranks: the forward half's buffers only -- the operand copies and T of the 16-bit chain, or T and the split-K
+// slabs of the generic kernels -- and the diagonal.  No G, no G^T, no tile records: linear in b.
+struct RankBilinearPlan {
+  BilinearPlan p;
+  float* diag;  // [b]
+  size_t bytes;
+};
+static RankBilinearPlan plan_rank_bilinear(Workspace& ws, int64_t b, int64_t dx, int64_t dy, int precision) {
+  RankBilinearPlan n{};
+  BilinearPlan& p = n.p;
+  const int64_t x3 = precision == MI_PREC_BF16X3 ? 3 : 1;
+  p.x3 = (int)x3;
+  if (chain_16bit_ok(b, b, dx, dy, precision)) {
+    p.xb = ws.take<bf16_t>(x3 * b * dx);
+    p.xtb = ws.take<bf16_t>(x3 * b * dx);
+    p.yb = ws.take<bf16_t>(x3 * b * dy);
+    p.ytb = ws.take<bf16_t>(x3 * b * dy);
+    p.wb = ws.take<bf16_t>(x3 * dx * dy);
+    p.wtb = ws.take<bf16_t>(x3 * dx * dy);
+    p.tb = ws.take<bf16_t>(x3 * b * dy);
+    p.ttb = ws.take<bf16_t>(x3 * b * dy);
+    p.path = MI_PATH_GEMMS;
+  } else {
+    p.t = ws.take<float>(b * dy);
+    p.gen_slab_floats = precision == MI_PREC_F32 ? generic_slab_floats(b, dy, dx) : 0;  // T = X W
+    p.gen_slab = p.gen_slab_floats > 0 ? ws.take<float>(p.gen_slab_floats) : nullptr;
+    p.path = MI_PATH_GENERIC;
+  }
+  n.diag = ws.take<float>(b);
+  p.bytes = n.bytes = ws.off;
+  return n;
+}
+
+struct RankSeparablePlan {
+  float *a, *c;  // the projections A = X Wg, C = Y Wh [b][k]
+  RankBilinearPlan n;
+  size_t bytes;
+};
+static RankSeparablePlan plan_rank_separable(Workspace& ws, int64_t b, int64_t k, int precision) {
+  RankSeparablePlan s{};
+  s.a = ws.take<float>(b * k);
+  s.c = ws.take<float>(b * k);
+  s.n = plan_rank_bilinear(ws, b, k, k, precision);
+  s.bytes = ws.off;
+  return s;
+}
+
+// prep / T, the diagonal from the sweep's operands (which zeroes the ranks), the sweep with the counting epilogue
+static int rank_chain(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t dx,
+                      int64_t dy, int precision, int* rank_i2t, int* rank_t2i, float* diag_out, const RankBilinearPlan& n,
+                      hipStream_t st) {
+  const BilinearPlan& p = n.p;
+  const RankOut o = rank_out(sid, n.diag, rank_i2t, rank_t2i);
+  int rc = chain_operands<RankEst>(x, y, w, sid, sid, b, b, 0, dx, dy, precision, p, st);
+  if (rc) return rc;
+  if (chain_16bit_ok(b, b, dx, dy, precision)) {
+    rc = rank_diag_bf16(p.tb, p.yb, b, p.x3 * dy, o, diag_out, st);
+  } else {
+    rc = with_operand_type(precision == MI_PREC_BF16, [&](auto* op) {
+      return rank_diag<OperandOf<decltype(op)>>(w ? p.t : x, y, b, dy, o, diag_out, st);
+    });
+  }
+  if (rc) return rc;
+  return chain_sweep<RankEst>(x, y, w, b, b, dx, dy, precision, o, p, st);
 }
 
 }  // namespace mi
@@ -1929,6 +2022,53 @@ int mi_fdiv_separable_step(const float* x, const float* y, const float* wg, cons
   if (rc) return rc;
   return separable_project_back(FdivEst::kSep, bf, x, y, wg, wh, b, b, d_img, d_txt, k, sp.da, sp.dc, grad_x, grad_y, grad_wg,
                                 grad_wh, st);
+}
+
+// ------------------------------------------------------------------------------------------------ retrieval ranks
+size_t mi_rank_bilinear_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int precision) {
+  if (b <= 0 || d_img <= 0 || d_txt <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_rank_bilinear(ws, b, d_img, d_txt, precision).bytes + 256;
+}
+
+int mi_rank_bilinear(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t d_img,
+                     int64_t d_txt, int precision, int32_t* rank_i2t, int32_t* rank_t2i, float* diag_out, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && sid && workspace, "mi_rank_bilinear: null pointer");
+  int rc = chain_check<RankEst>("mi_rank_bilinear", b, b, 0, d_img, d_txt, 0, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(rank_i2t || rank_t2i, "mi_rank_bilinear: pass rank_i2t, rank_t2i or both");
+  MI_CHECK_ARG(w || d_img == d_txt, "mi_rank_bilinear: w == NULL (S = X Y^T) needs d_img == d_txt");
+  Workspace ws(workspace, workspace_bytes);
+  const RankBilinearPlan n = plan_rank_bilinear(ws, b, d_img, d_txt, precision);
+  rc = ws_fits(ws, "mi_rank_bilinear");
+  if (rc) return rc;
+  return rank_chain(x, y, w, sid, b, d_img, d_txt, precision, rank_i2t, rank_t2i, diag_out, n, (hipStream_t)stream);
+}
+
+size_t mi_rank_separable_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int precision) {
+  if (b <= 0 || d_img <= 0 || d_txt <= 0 || d_proj <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_rank_separable(ws, b, d_proj, precision).bytes + 256;
+}
+
+int mi_rank_separable(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid, int64_t b,
+                      int64_t d_img, int64_t d_txt, int64_t d_proj, int precision, int32_t* rank_i2t, int32_t* rank_t2i,
+                      float* diag_out, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && wg && wh && sid && workspace, "mi_rank_separable: null pointer");
+  int rc = chain_check<RankEst>("mi_rank_separable", b, b, 0, d_img, d_txt, 0, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(d_proj >= 1, "mi_rank_separable: projection width must be >= 1");
+  MI_CHECK_ARG(rank_i2t || rank_t2i, "mi_rank_separable: pass rank_i2t, rank_t2i or both");
+  Workspace ws(workspace, workspace_bytes);
+  const RankSeparablePlan sp = plan_rank_separable(ws, b, d_proj, precision);
+  rc = ws_fits(ws, "mi_rank_separable");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t k = d_proj;
+  rc = separable_project(RankEst::kSep, precision == MI_PREC_BF16, x, y, wg, wh, b, b, d_img, d_txt, k, sp.a, sp.c, st);
+  if (rc) return rc;
+  return rank_chain(sp.a, sp.c, nullptr, sid, b, k, k, precision, rank_i2t, rank_t2i, diag_out, sp.n, st);
 }
 
 }  // extern "C"

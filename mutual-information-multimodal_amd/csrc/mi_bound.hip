@@ -10,6 +10,7 @@
 
 #include "mi_common.h"
 #include "mi_fdiv.h"
+#include "mi_rank.h"
 
 namespace mi {
 
@@ -500,6 +501,14 @@ int mi_fdiv_matrix_bwd(const float* scores, const int64_t* sid, int64_t b, int m
   }
   MI_LAUNCH_CHECK("fdiv_matrix_bwd_kernel");
   return MI_OK;
+}
+
+// ---- retrieval ranks (mi_rank.h) of a [b, b] matrix: no workspace ---------------------------------------------------------
+int mi_rank_matrix(const float* scores, const int64_t* sid, int64_t b, int32_t* rank_i2t, int32_t* rank_t2i, void* stream) {
+  MI_CHECK_ARG(scores && sid, "mi_rank_matrix: null pointer");
+  MI_CHECK_ARG(b >= 1, "mi_rank_matrix: b must be >= 1");
+  MI_CHECK_ARG(rank_i2t || rank_t2i, "mi_rank_matrix: pass rank_i2t, rank_t2i or both");
+  return rank_matrix(scores, sid, b, rank_i2t, rank_t2i, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -180,6 +180,11 @@ SIGNATURES = {
     "mi_fdiv_separable_step": (c_int, [_P] * 5 + [_I64] * 4 + [_I, _I] + [_P] * 9 + [_SZ, _P]),
     "mi_fdiv_concat_mlp_fwd": (c_int, [_P] * 10 + [_I64] * 7 + [_I, _I, _I] + [_P] * 5 + [_SZ, _P]),
     "mi_fdiv_concat_mlp_bwd": (c_int, [_P] * 10 + [_I64] * 7 + [_I, _I] + [_P] * 12 + [_SZ, _P]),
+    "mi_rank_matrix": (c_int, [_P, _P, _I64, _P, _P, _P]),
+    "mi_rank_bilinear_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I]),
+    "mi_rank_bilinear": (c_int, [_P] * 4 + [_I64] * 3 + [_I] + [_P] * 4 + [_SZ, _P]),
+    "mi_rank_separable_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I]),
+    "mi_rank_separable": (c_int, [_P] * 5 + [_I64] * 4 + [_I] + [_P] * 4 + [_SZ, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

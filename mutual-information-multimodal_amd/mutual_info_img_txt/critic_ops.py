@@ -1,5 +1,5 @@
 """The one binding of the critic entry points of the C ABI (mi_bilinear_*, mi_separable_*, mi_concat_mlp_*, mi_nce_*,
-mi_fdiv_*), shared by ``mi_critics`` (eager autograd), ``graphed`` (hipGraph step) and ``distributed`` (sharded step).
+mi_fdiv_*, mi_rank_*), shared by ``mi_critics`` (eager autograd), ``graphed`` (hipGraph step) and ``distributed`` (sharded step).
 
 An ops object scores the row block ``x`` [b_rows, d_img] (starting at ``row_offset``) against all of ``y_all``
 [b, d_txt]; a whole batch is ``b_rows == b``, ``row_offset == 0``.  Each ``*_call`` method writes one entry point's
@@ -74,6 +74,16 @@ def _call(name, device, *args):
     return partial(_hip.call, name, device, *args)
 
 
+def rank_matrix(scores, sid, i2t=True, t2i=True):
+    """Retrieval ranks of a float32 [B, B] score matrix (mi_rank_matrix): (rank_i2t, rank_t2i) int32 [B]; a direction
+    not asked for is None."""
+    b, dev = scores.shape[0], scores.device
+    ri = torch.empty(b, dtype=torch.int32, device=dev) if i2t else None
+    rt = torch.empty(b, dtype=torch.int32, device=dev) if t2i else None
+    _hip.call("mi_rank_matrix", dev, scores.data_ptr(), sid.data_ptr(), b, _p(ri), _p(rt))
+    return ri, rt
+
+
 class _HipOps:
     """The ops protocol of ``distributed.GlobalBatchCriticFn`` (forward / merge / backward) on the C ABI.  ``saved`` is
     (x, y_all, params, sid_rows, sid_all, row_offset, precision, scores, ws) for every critic."""
@@ -132,6 +142,16 @@ class _HipOps:
     def nce_step(self, x, y, params, sid, mode, precision, need_grad):
         """``chain_step("mi_nce", ...)``: the one-call reference the row-block protocol below is checked against."""
         return self.chain_step("mi_nce", x, y, params, sid, mode, precision, need_grad)
+
+    def rank_step(self, x, y, params, sid, precision, want_diag=False):
+        """Retrieval ranks of the whole batch in one call of ``mi_rank_<critic>`` (bilinear and separable critics):
+        (rank_i2t, rank_t2i) int32 [B], and the diagonal scores S[i, i] when ``want_diag``."""
+        b, dev = x.shape[0], x.device
+        ws = _hip.workspace(self.rank_workspace_bytes(b, x.shape[1], y.shape[1], params, precision), dev)
+        ri, rt = (torch.empty(b, dtype=torch.int32, device=dev) for _ in range(2))
+        diag = torch.empty(b, dtype=torch.float32, device=dev) if want_diag else None
+        self.rank_call(x, y, params, sid, precision, ri, rt, diag, ws)()
+        return (ri, rt, diag) if want_diag else (ri, rt)
 
     # ---------------------------------------------- per-sample InfoNCE on a row block (distributed.GlobalBatchNceFn)
     def nce_forward(self, x, y_all, params, sid_rows, sid_all, row_offset, mode, precision, need_grad=True):
@@ -216,6 +236,17 @@ class HipBilinearOps(_HipOps):
         return _call(f"{entry}_bilinear_step", x.device, x.data_ptr(), y.data_ptr(), _p(w), sid.data_ptr(), x.shape[0],
                      x.shape[1], y.shape[1], mode, precision, None, loss.data_ptr(), r.data_ptr(), _p(c), _p(gx),
                      _p(gy), _p(gw), ws.data_ptr(), ws.numel())
+
+    @staticmethod
+    def rank_workspace_bytes(b, dx, dy, params, precision):
+        return _hip.load().mi_rank_bilinear_workspace_bytes(b, dx, dy, precision)
+
+    def rank_call(self, x, y, params, sid, precision, rank_i2t, rank_t2i, diag, ws):
+        """Retrieval ranks of the whole batch (mi_rank_bilinear); ``rank_i2t`` / ``rank_t2i`` int32 [B] (either may be
+        None), ``diag`` float32 [B] or None."""
+        return _call("mi_rank_bilinear", x.device, x.data_ptr(), y.data_ptr(), _p(params[0] if params else None),
+                     sid.data_ptr(), x.shape[0], x.shape[1], y.shape[1], precision, _p(rank_i2t), _p(rank_t2i), _p(diag),
+                     ws.data_ptr(), ws.numel())
 
     @staticmethod
     def nce_shard_workspace_bytes(br, b, dx, dy, params, precision):
@@ -372,6 +403,17 @@ class HipSeparableOps(_HipOps):
                      sid.data_ptr(), x.shape[0], x.shape[1], y.shape[1], wg.shape[1], mode, precision, None,
                      loss.data_ptr(), r.data_ptr(), _p(c), *[_p(g) for g in grads or [None] * 4], ws.data_ptr(),
                      ws.numel())
+
+    @staticmethod
+    def rank_workspace_bytes(b, dx, dy, params, precision):
+        return _hip.load().mi_rank_separable_workspace_bytes(b, dx, dy, params[0].shape[1], precision)
+
+    def rank_call(self, x, y, params, sid, precision, rank_i2t, rank_t2i, diag, ws):
+        """Retrieval ranks of the whole batch (mi_rank_separable), as ``HipBilinearOps.rank_call``."""
+        wg, wh = params
+        return _call("mi_rank_separable", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
+                     sid.data_ptr(), x.shape[0], x.shape[1], y.shape[1], wg.shape[1], precision, _p(rank_i2t),
+                     _p(rank_t2i), _p(diag), ws.data_ptr(), ws.numel())
 
     @staticmethod
     def nce_shard_workspace_bytes(br, b, dx, dy, params, precision):

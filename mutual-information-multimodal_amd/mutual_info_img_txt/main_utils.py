@@ -179,6 +179,14 @@ class MultiModalManager:
         mi_output = self.mi_discriminator(mi_input)
         return getattr(mi_critics, est.logits)(mi_output, len(study_id), embedding_img.device)
 
+    def retrieval_eval(self, embedding_img, embedding_txt, study_id, ks=(1, 5, 10), precision: str = "f32"):
+        """Cross-modal retrieval of the batch under the manager's critic (``retrieval.retrieval_ranks``):
+        ``{"i2t": metrics, "t2i": metrics}`` with ``retrieval.retrieval_metrics`` of the image -> report and the
+        report -> image ranks (recall@K for each K of ``ks``, 1-based median rank, MRR).  Evaluation only: no gradients."""
+        from . import retrieval
+        ri, rt = retrieval.retrieval_ranks(embedding_img, embedding_txt, study_id, self.mi_discriminator, precision)
+        return {"i2t": retrieval.retrieval_metrics(ri, ks), "t2i": retrieval.retrieval_metrics(rt, ks)}
+
     # ------------------------------------------------------------------------------------------ batches
     def _build_loader(self, text_token_features, args):
         """Dataset + shuffling ``drop_last`` DataLoader of the reference (main_utils.py:123-129), built once per manager:
