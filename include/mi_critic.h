@@ -22,6 +22,8 @@
  *                            (main_utils.py:88-110), for every critic; the reference has "dv" and "infonce" only
  *   mi_rank_*             <- an extension: image-report retrieval ranks (for recall@K, median rank, MRR) of every
  *                            critic under the same masking rule; an evaluation, not an estimator
+ *   mi_topk_*             <- an extension: the k best reports of an image and the k best images of a report over a
+ *                            gallery (n_img != n_txt allowed), optionally without equal-id candidates; an evaluation too
  *
  * Conventions
  *   - every pointer is a DEVICE pointer unless the name ends in _host; all tensors are dense row-major
@@ -448,6 +450,41 @@ size_t mi_rank_separable_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt
 int mi_rank_separable(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid, int64_t b,
                       int64_t d_img, int64_t d_txt, int64_t d_proj, int precision, int32_t* rank_i2t, int32_t* rank_t2i,
                       float* diag_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- top-k retrieval over a gallery ------------------------------------------------------ */
+/* Queries q and candidates g with scores S[q, g]; with ids, a candidate whose id equals the query's is excluded.  The
+ * result of a query is its first k candidates in the total order "score descending, then candidate index ascending"
+ * (-0.0 counts as +0.0): idx int32 [n_q, k] and val float32 [n_q, k], val = the kernel's own fp32 score of idx.  Where
+ * fewer than k candidates remain the tail is idx = -1, val = -inf.  The order is total, so the result is unique and
+ * identical from call to call; NaN scores carry no ordering promise (indices stay in range).  The two id pointers are
+ * both NULL (nothing excluded) or both given.  k in [1, MI_TOPK_MAX_K], every size below 2^31, else MI_EINVAL.  Not an
+ * estimator: no mode, no loss, no gradients. */
+#define MI_TOPK_MAX_K 32
+/* a caller's fp32 [n_rows, n_cols] score matrix.  axis 0: each row's top-k columns (idx, val [n_rows, k], sid_rows the
+ * queries' ids); axis 1: each column's top-k rows (idx, val [n_cols, k], sid_cols the queries' ids). */
+size_t mi_topk_matrix_workspace_bytes(int64_t n_rows, int64_t n_cols, int k, int axis);
+int mi_topk_matrix(const float* scores, int64_t n_rows, int64_t n_cols, const int64_t* sid_rows, const int64_t* sid_cols,
+                   int k, int axis, int32_t* idx, float* val, void* workspace, size_t workspace_bytes, void* stream);
+/* Bilinear S = (X W) Y^T (w == NULL: X Y^T, d_img == d_txt) of x [n_img, d_img] against y [n_txt, d_txt], n_img != n_txt
+ * allowed, on the forward half of the GEMM chain as mi_rank_bilinear: prep and T = X W once, then one score sweep per
+ * direction whose epilogue inserts into per-query key lists (image -> report: idx_i2t / val_i2t [n_img, k] index the
+ * reports; report -> image: idx_t2i / val_t2i [n_txt, k] index the images), then a small sort.  A direction whose two
+ * pointers are NULL is skipped; both directions NULL is MI_EINVAL.  No score matrix and no per-tile buffer: the workspace
+ * is the forward half's operand copies and T plus 8 (n_img + n_txt) k bytes of lists.  precision: MI_PREC_F32 (exact
+ * fp32 products), MI_PREC_BF16 / MI_PREC_BF16X3 (16-bit chain where n_img, n_txt and the widths are multiples of 8,
+ * generic kernels otherwise); MI_PREC_FP8 / F16 / F16X3 are rejected (MI_EINVAL). */
+size_t mi_topk_bilinear_workspace_bytes(int64_t n_img, int64_t n_txt, int64_t d_img, int64_t d_txt, int precision, int k);
+int mi_topk_bilinear(const float* x, const float* y, const float* w, const int64_t* sid_img, const int64_t* sid_txt,
+                     int64_t n_img, int64_t n_txt, int64_t d_img, int64_t d_txt, int precision, int k, int32_t* idx_i2t,
+                     float* val_i2t, int32_t* idx_t2i, float* val_t2i, void* workspace, size_t workspace_bytes,
+                     void* stream);
+/* separable S = (X Wg)(Y Wh)^T: projects first, then the w == NULL form on the projections, as mi_rank_separable */
+size_t mi_topk_separable_workspace_bytes(int64_t n_img, int64_t n_txt, int64_t d_img, int64_t d_txt, int64_t d_proj,
+                                         int precision, int k);
+int mi_topk_separable(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid_img,
+                      const int64_t* sid_txt, int64_t n_img, int64_t n_txt, int64_t d_img, int64_t d_txt, int64_t d_proj,
+                      int precision, int k, int32_t* idx_i2t, float* val_i2t, int32_t* idx_t2i, float* val_t2i,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -21,6 +21,7 @@
 #include "mi_nce.h"
 #include "mi_fdiv.h"
 #include "mi_rank.h"
+#include "mi_topk.h"
 
 namespace mi {
 
@@ -1471,6 +1472,20 @@ struct RankEst {
   static constexpr SepLabels kSep = {"rank separable A = X Wg", "rank separable C = Y Wh"};
 };
 
+// Top-k retrieval (mi_topk.h): the forward half again, the score GEMM's epilogue inserts into the
+// queries' key lists.  Rectangular (n_img x n_txt), no ids in prep / T, no mode, no gradient half.
+struct TopkEst {
+  using StatsOut = TopkOut;
+  using Stats = EpiTopkInsert;
+  using Stats16 = EpiTopkInsert;
+  static int check_mode(const char*, int) { return MI_OK; }
+  static constexpr const char* kName = "the top-k retrieval";
+  static constexpr const char* kT = "topk T = X W (generic)";
+  static constexpr const char* kScores = "topk score + inserts (generic)";
+  static constexpr const char* kScores16 = "topk score + inserts";
+  static constexpr SepLabels kSep = {"topk separable A = X Wg", "topk separable C = Y Wh"};
+};
+
 static bool chain_16bit_ok(int64_t br, int64_t b, int64_t dx, int64_t dy, int precision) {
   return (precision == MI_PREC_BF16 || precision == MI_PREC_BF16X3) && br % 8 == 0 && b % 8 == 0 && dx % 8 == 0 &&
          dy % 8 == 0;
@@ -1704,6 +1719,131 @@ static int rank_chain(const float* x, const float* y, const float* w, const int6
   }
   if (rc) return rc;
   return chain_sweep<RankEst>(x, y, w, b, b, dx, dy, precision, o, p, st);
+}
+
+// ------------------------------------------------------------------------------------------------ top-k retrieval
+// sizes and precision of a rectangular gallery call (chain_check ties b_rows to b: not for a gallery)
+static int topk_check(const char* fn, int64_t n_img, int64_t n_txt, int64_t dx, int64_t dy, int precision, int k) {
+  MI_CHECK_ARG(n_img >= 1 && n_txt >= 1 && dx >= 1 && dy >= 1, "%s: sizes must be >= 1 (n_img %lld, n_txt %lld, widths %lld, %lld)",
+               fn, (long long)n_img, (long long)n_txt, (long long)dx, (long long)dy);
+  const int64_t lim = (int64_t)1 << 31;
+  MI_CHECK_ARG(n_img < lim && n_txt < lim && dx < lim && dy < lim, "%s: sizes must be below 2^31", fn);
+  MI_CHECK_ARG(k >= 1 && k <= kTopkMaxK, "%s: k must be in [1, %d] (got %d)", fn, kTopkMaxK, k);
+  MI_CHECK_ARG(precision == MI_PREC_F32 || precision == MI_PREC_BF16 || precision == MI_PREC_BF16X3,
+               "%s: precision %d is not available for %s (f32, bf16, bf16x3)", fn, precision, TopkEst::kName);
+  return MI_OK;
+}
+
+// The forward half's buffers of an [n_img] x [n_txt] problem -- the operand copies and T of the 16-bit chain, or T and
+// the split-K slabs of the generic kernels -- and the key lists of both directions: O((n_img + n_txt) k) on top.
+struct TopkBilinearPlan {
+  BilinearPlan p;
+  topk_key_t* keys_i2t;  // [n_img][k]
+  topk_key_t* keys_t2i;  // [n_txt][k], directly behind keys_i2t
+  size_t bytes;
+};
+static TopkBilinearPlan plan_topk_bilinear(Workspace& ws, int64_t n_img, int64_t n_txt, int64_t dx, int64_t dy,
+                                           int precision, int k) {
+  TopkBilinearPlan n{};
+  BilinearPlan& p = n.p;
+  const int64_t x3 = precision == MI_PREC_BF16X3 ? 3 : 1;
+  p.x3 = (int)x3;
+  if (chain_16bit_ok(n_img, n_txt, dx, dy, precision)) {
+    p.xb = ws.take<bf16_t>(x3 * n_img * dx);
+    p.xtb = ws.take<bf16_t>(x3 * n_img * dx);
+    p.yb = ws.take<bf16_t>(x3 * n_txt * dy);
+    p.ytb = ws.take<bf16_t>(x3 * n_txt * dy);
+    p.wb = ws.take<bf16_t>(x3 * dx * dy);
+    p.wtb = ws.take<bf16_t>(x3 * dx * dy);
+    p.tb = ws.take<bf16_t>(x3 * n_img * dy);
+    p.ttb = ws.take<bf16_t>(x3 * n_img * dy);
+    p.path = MI_PATH_GEMMS;
+  } else {
+    p.t = ws.take<float>(n_img * dy);
+    p.gen_slab_floats = precision == MI_PREC_F32 ? generic_slab_floats(n_img, dy, dx) : 0;  // T = X W
+    p.gen_slab = p.gen_slab_floats > 0 ? ws.take<float>(p.gen_slab_floats) : nullptr;
+    p.path = MI_PATH_GENERIC;
+  }
+  n.keys_i2t = ws.take<topk_key_t>((n_img + n_txt) * k);
+  n.keys_t2i = n.keys_i2t ? n.keys_i2t + n_img * k : nullptr;
+  p.bytes = n.bytes = ws.off;
+  return n;
+}
+
+struct TopkSeparablePlan {
+  float *a, *c;  // the projections A = X Wg [n_img][k_proj], C = Y Wh [n_txt][k_proj]
+  TopkBilinearPlan n;
+  size_t bytes;
+};
+static TopkSeparablePlan plan_topk_separable(Workspace& ws, int64_t n_img, int64_t n_txt, int64_t k_proj, int precision,
+                                             int k) {
+  TopkSeparablePlan s{};
+  s.a = ws.take<float>(n_img * k_proj);
+  s.c = ws.take<float>(n_txt * k_proj);
+  s.n = plan_topk_bilinear(ws, n_img, n_txt, k_proj, k_proj, precision, k);
+  s.bytes = ws.off;
+  return s;
+}
+
+struct TopkDirs {
+  int32_t* idx_i2t;
+  float* val_i2t;
+  int32_t* idx_t2i;
+  float* val_t2i;
+};
+
+// One direction's sweep.  The lane-owned side of the accumulator tile (its columns, the GEMM's B operand) is the query
+// side: image -> report puts T (or X) there and streams Y as the A operand, report -> image the other way round.  Both
+// read the same T from the workspace.
+static int topk_sweep(bool i2t, const float* x, const float* y, const float* w, const int64_t* sid_img,
+                      const int64_t* sid_txt, int64_t n_img, int64_t n_txt, int64_t dx, int64_t dy, int precision, int k,
+                      const TopkBilinearPlan& n, hipStream_t st) {
+  const BilinearPlan& p = n.p;
+  const TopkOut o = i2t ? TopkOut{sid_img, sid_txt, n.keys_i2t, k} : TopkOut{sid_txt, sid_img, n.keys_t2i, k};
+  if (chain_16bit_ok(n_img, n_txt, dx, dy, precision)) {
+    const int64_t kk = p.x3 * dy;
+    const GemmBf16Args g = i2t ? one_problem(p.yb, kk, p.tb, kk, n_txt, n_img, kk) : one_problem(p.tb, kk, p.yb, kk, n_img, n_txt, kk);
+    return launch_gemm_bf16(g, 1, EpiTopkInsert{o}, st, TopkEst::kScores16);
+  }
+  return with_operand_type(precision == MI_PREC_BF16, [&](auto* op) {
+    using OpT = OperandOf<decltype(op)>;
+    const auto img = make_operand(w ? (const float*)p.t : x, dy, 1), txt = make_operand(y, dy, 1);
+    if (i2t) return launch_gemm<OpT>(txt, img, n_txt, n_img, dy, EpiTopkInsert{o}, st, TopkEst::kScores);
+    return launch_gemm<OpT>(img, txt, n_img, n_txt, dy, EpiTopkInsert{o}, st, TopkEst::kScores);
+  });
+}
+
+// prep / T without ids or a row offset (this plan has no fused stage, so no equal-id tile flags are written), the lists
+// emptied, one sweep and one finish per direction asked for
+static int topk_chain(const float* x, const float* y, const float* w, const int64_t* sid_img, const int64_t* sid_txt,
+                      int64_t n_img, int64_t n_txt, int64_t dx, int64_t dy, int precision, int k, const TopkDirs& d,
+                      const TopkBilinearPlan& n, hipStream_t st) {
+  int rc = chain_operands<TopkEst>(x, y, w, nullptr, nullptr, n_img, n_txt, 0, dx, dy, precision, n.p, st);
+  if (rc) return rc;
+  const bool i2t = d.idx_i2t != nullptr, t2i = d.idx_t2i != nullptr;
+  rc = topk_zero(i2t ? n.keys_i2t : n.keys_t2i, ((i2t ? n_img : 0) + (t2i ? n_txt : 0)) * k, st);
+  if (rc) return rc;
+  if (i2t) {
+    rc = topk_sweep(true, x, y, w, sid_img, sid_txt, n_img, n_txt, dx, dy, precision, k, n, st);
+    if (rc) return rc;
+    rc = topk_finish(n.keys_i2t, n_img, k, d.idx_i2t, d.val_i2t, st);
+    if (rc) return rc;
+  }
+  if (t2i) {
+    rc = topk_sweep(false, x, y, w, sid_img, sid_txt, n_img, n_txt, dx, dy, precision, k, n, st);
+    if (rc) return rc;
+    rc = topk_finish(n.keys_t2i, n_txt, k, d.idx_t2i, d.val_t2i, st);
+  }
+  return rc;
+}
+
+// the pointer rules shared by the two chain entry points
+static int topk_check_dirs(const char* fn, const int64_t* sid_img, const int64_t* sid_txt, const TopkDirs& d) {
+  MI_CHECK_ARG((sid_img == nullptr) == (sid_txt == nullptr), "%s: pass sid_img and sid_txt, or neither", fn);
+  MI_CHECK_ARG((d.idx_i2t == nullptr) == (d.val_i2t == nullptr) && (d.idx_t2i == nullptr) == (d.val_t2i == nullptr),
+               "%s: idx and val of a direction go together", fn);
+  MI_CHECK_ARG(d.idx_i2t || d.idx_t2i, "%s: pass the i2t outputs, the t2i outputs or both", fn);
+  return MI_OK;
 }
 
 }  // namespace mi
@@ -2069,6 +2209,87 @@ int mi_rank_separable(const float* x, const float* y, const float* wg, const flo
   rc = separable_project(RankEst::kSep, precision == MI_PREC_BF16, x, y, wg, wh, b, b, d_img, d_txt, k, sp.a, sp.c, st);
   if (rc) return rc;
   return rank_chain(sp.a, sp.c, nullptr, sid, b, k, k, precision, rank_i2t, rank_t2i, diag_out, sp.n, st);
+}
+
+// ------------------------------------------------------------------------------------------------ top-k retrieval
+size_t mi_topk_matrix_workspace_bytes(int64_t n_rows, int64_t n_cols, int k, int axis) {
+  if (n_rows <= 0 || n_cols <= 0 || k < 1 || k > kTopkMaxK || (axis != 0 && axis != 1)) return 0;
+  return (size_t)(axis == 0 ? n_rows : n_cols) * k * sizeof(topk_key_t) + 256;
+}
+
+int mi_topk_matrix(const float* scores, int64_t n_rows, int64_t n_cols, const int64_t* sid_rows, const int64_t* sid_cols,
+                   int k, int axis, int32_t* idx, float* val, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(scores && idx && val && workspace, "mi_topk_matrix: null pointer");
+  MI_CHECK_ARG(n_rows >= 1 && n_cols >= 1, "mi_topk_matrix: sizes must be >= 1 (got %lld x %lld)", (long long)n_rows,
+               (long long)n_cols);
+  MI_CHECK_ARG(n_rows < ((int64_t)1 << 31) && n_cols < ((int64_t)1 << 31), "mi_topk_matrix: sizes must be below 2^31");
+  MI_CHECK_ARG(k >= 1 && k <= kTopkMaxK, "mi_topk_matrix: k must be in [1, %d] (got %d)", kTopkMaxK, k);
+  MI_CHECK_ARG(axis == 0 || axis == 1, "mi_topk_matrix: axis must be 0 (rows' columns) or 1 (columns' rows), got %d", axis);
+  MI_CHECK_ARG((sid_rows == nullptr) == (sid_cols == nullptr), "mi_topk_matrix: pass sid_rows and sid_cols, or neither");
+  Workspace ws(workspace, workspace_bytes);
+  const int64_t n_q = axis == 0 ? n_rows : n_cols;
+  topk_key_t* keys = ws.take<topk_key_t>(n_q * k);
+  int rc = ws_fits(ws, "mi_topk_matrix");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  rc = topk_zero(keys, n_q * k, st);
+  if (rc) return rc;
+  rc = topk_matrix(scores, sid_rows, sid_cols, n_rows, n_cols, axis, keys, k, st);
+  if (rc) return rc;
+  return topk_finish(keys, n_q, k, idx, val, st);
+}
+
+size_t mi_topk_bilinear_workspace_bytes(int64_t n_img, int64_t n_txt, int64_t d_img, int64_t d_txt, int precision, int k) {
+  if (n_img <= 0 || n_txt <= 0 || d_img <= 0 || d_txt <= 0 || k < 1 || k > kTopkMaxK) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_topk_bilinear(ws, n_img, n_txt, d_img, d_txt, precision, k).bytes + 256;
+}
+
+int mi_topk_bilinear(const float* x, const float* y, const float* w, const int64_t* sid_img, const int64_t* sid_txt,
+                     int64_t n_img, int64_t n_txt, int64_t d_img, int64_t d_txt, int precision, int k, int32_t* idx_i2t,
+                     float* val_i2t, int32_t* idx_t2i, float* val_t2i, void* workspace, size_t workspace_bytes,
+                     void* stream) {
+  MI_CHECK_ARG(x && y && workspace, "mi_topk_bilinear: null pointer");
+  int rc = topk_check("mi_topk_bilinear", n_img, n_txt, d_img, d_txt, precision, k);
+  if (rc) return rc;
+  const TopkDirs d{idx_i2t, val_i2t, idx_t2i, val_t2i};
+  rc = topk_check_dirs("mi_topk_bilinear", sid_img, sid_txt, d);
+  if (rc) return rc;
+  MI_CHECK_ARG(w || d_img == d_txt, "mi_topk_bilinear: w == NULL (S = X Y^T) needs d_img == d_txt");
+  Workspace ws(workspace, workspace_bytes);
+  const TopkBilinearPlan n = plan_topk_bilinear(ws, n_img, n_txt, d_img, d_txt, precision, k);
+  rc = ws_fits(ws, "mi_topk_bilinear");
+  if (rc) return rc;
+  return topk_chain(x, y, w, sid_img, sid_txt, n_img, n_txt, d_img, d_txt, precision, k, d, n, (hipStream_t)stream);
+}
+
+size_t mi_topk_separable_workspace_bytes(int64_t n_img, int64_t n_txt, int64_t d_img, int64_t d_txt, int64_t d_proj,
+                                         int precision, int k) {
+  if (n_img <= 0 || n_txt <= 0 || d_img <= 0 || d_txt <= 0 || d_proj <= 0 || k < 1 || k > kTopkMaxK) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_topk_separable(ws, n_img, n_txt, d_proj, precision, k).bytes + 256;
+}
+
+int mi_topk_separable(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid_img,
+                      const int64_t* sid_txt, int64_t n_img, int64_t n_txt, int64_t d_img, int64_t d_txt, int64_t d_proj,
+                      int precision, int k, int32_t* idx_i2t, float* val_i2t, int32_t* idx_t2i, float* val_t2i,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && wg && wh && workspace, "mi_topk_separable: null pointer");
+  int rc = topk_check("mi_topk_separable", n_img, n_txt, d_img, d_txt, precision, k);
+  if (rc) return rc;
+  MI_CHECK_ARG(d_proj >= 1 && d_proj < ((int64_t)1 << 31), "mi_topk_separable: projection width must be in [1, 2^31)");
+  const TopkDirs d{idx_i2t, val_i2t, idx_t2i, val_t2i};
+  rc = topk_check_dirs("mi_topk_separable", sid_img, sid_txt, d);
+  if (rc) return rc;
+  Workspace ws(workspace, workspace_bytes);
+  const TopkSeparablePlan sp = plan_topk_separable(ws, n_img, n_txt, d_proj, precision, k);
+  rc = ws_fits(ws, "mi_topk_separable");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  rc = separable_project(TopkEst::kSep, precision == MI_PREC_BF16, x, y, wg, wh, n_img, n_txt, d_img, d_txt, d_proj, sp.a,
+                         sp.c, st);
+  if (rc) return rc;
+  return topk_chain(sp.a, sp.c, nullptr, sid_img, sid_txt, n_img, n_txt, d_proj, d_proj, precision, k, d, sp.n, st);
 }
 
 }  // extern "C"

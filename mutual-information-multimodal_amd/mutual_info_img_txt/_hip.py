@@ -185,7 +185,14 @@ SIGNATURES = {
     "mi_rank_bilinear": (c_int, [_P] * 4 + [_I64] * 3 + [_I] + [_P] * 4 + [_SZ, _P]),
     "mi_rank_separable_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I]),
     "mi_rank_separable": (c_int, [_P] * 5 + [_I64] * 4 + [_I] + [_P] * 4 + [_SZ, _P]),
+    "mi_topk_matrix_workspace_bytes": (_SZ, [_I64, _I64, _I, _I]),
+    "mi_topk_matrix": (c_int, [_P, _I64, _I64, _P, _P, _I, _I, _P, _P, _P, _SZ, _P]),
+    "mi_topk_bilinear_workspace_bytes": (_SZ, [_I64] * 4 + [_I, _I]),
+    "mi_topk_bilinear": (c_int, [_P] * 5 + [_I64] * 4 + [_I, _I] + [_P] * 5 + [_SZ, _P]),
+    "mi_topk_separable_workspace_bytes": (_SZ, [_I64] * 5 + [_I, _I]),
+    "mi_topk_separable": (c_int, [_P] * 6 + [_I64] * 5 + [_I, _I] + [_P] * 5 + [_SZ, _P]),
 }
+MI_TOPK_MAX_K = 32  # include/mi_critic.h
 
 _lib: Optional[ctypes.CDLL] = None
 

@@ -1,5 +1,5 @@
 """The one binding of the critic entry points of the C ABI (mi_bilinear_*, mi_separable_*, mi_concat_mlp_*, mi_nce_*,
-mi_fdiv_*, mi_rank_*), shared by ``mi_critics`` (eager autograd), ``graphed`` (hipGraph step) and ``distributed`` (sharded step).
+mi_fdiv_*, mi_rank_*, mi_topk_*), shared by ``mi_critics`` (eager autograd), ``graphed`` (hipGraph step) and ``distributed`` (sharded step).
 
 An ops object scores the row block ``x`` [b_rows, d_img] (starting at ``row_offset``) against all of ``y_all``
 [b, d_txt]; a whole batch is ``b_rows == b``, ``row_offset == 0``.  Each ``*_call`` method writes one entry point's
@@ -84,6 +84,23 @@ def rank_matrix(scores, sid, i2t=True, t2i=True):
     return ri, rt
 
 
+def topk_outputs(n_q, k, device):
+    """(idx int32 [n_q, k], val float32 [n_q, k]) of one top-k direction."""
+    return (torch.empty(n_q, k, dtype=torch.int32, device=device), torch.empty(n_q, k, dtype=torch.float32, device=device))
+
+
+def topk_matrix(scores, k, axis=0, sid_rows=None, sid_cols=None):
+    """Top-k of a float32 [n_rows, n_cols] score matrix (mi_topk_matrix): (idx, val) [n_rows, k] of each row's best
+    columns (``axis`` 0) or [n_cols, k] of each column's best rows (``axis`` 1); with the two id code tensors a candidate
+    whose code equals the query's is left out."""
+    (n_rows, n_cols), dev = scores.shape, scores.device
+    ws = _hip.workspace(_hip.load().mi_topk_matrix_workspace_bytes(n_rows, n_cols, k, axis), dev)
+    idx, val = topk_outputs(n_rows if axis == 0 else n_cols, k, dev)
+    _hip.call("mi_topk_matrix", dev, scores.data_ptr(), n_rows, n_cols, _p(sid_rows), _p(sid_cols), k, axis,
+              idx.data_ptr(), val.data_ptr(), ws.data_ptr(), ws.numel())
+    return idx, val
+
+
 class _HipOps:
     """The ops protocol of ``distributed.GlobalBatchCriticFn`` (forward / merge / backward) on the C ABI.  ``saved`` is
     (x, y_all, params, sid_rows, sid_all, row_offset, precision, scores, ws) for every critic."""
@@ -152,6 +169,16 @@ class _HipOps:
         diag = torch.empty(b, dtype=torch.float32, device=dev) if want_diag else None
         self.rank_call(x, y, params, sid, precision, ri, rt, diag, ws)()
         return (ri, rt, diag) if want_diag else (ri, rt)
+
+    def topk_step(self, x, y, params, sid_img, sid_txt, precision, k, i2t=True, t2i=True):
+        """Top-k retrieval of x [n_img, d_img] against y [n_txt, d_txt] in one call of ``mi_topk_<critic>`` (bilinear and
+        separable critics): ((idx, val) of image -> report or None, (idx, val) of report -> image or None)."""
+        (n_img, dx), (n_txt, dy), dev = x.shape, y.shape, x.device
+        ws = _hip.workspace(self.topk_workspace_bytes(n_img, n_txt, dx, dy, params, precision, k), dev)
+        out_i = topk_outputs(n_img, k, dev) if i2t else None
+        out_t = topk_outputs(n_txt, k, dev) if t2i else None
+        self.topk_call(x, y, params, sid_img, sid_txt, precision, k, out_i, out_t, ws)()
+        return out_i, out_t
 
     # ---------------------------------------------- per-sample InfoNCE on a row block (distributed.GlobalBatchNceFn)
     def nce_forward(self, x, y_all, params, sid_rows, sid_all, row_offset, mode, precision, need_grad=True):
@@ -247,6 +274,18 @@ class HipBilinearOps(_HipOps):
         return _call("mi_rank_bilinear", x.device, x.data_ptr(), y.data_ptr(), _p(params[0] if params else None),
                      sid.data_ptr(), x.shape[0], x.shape[1], y.shape[1], precision, _p(rank_i2t), _p(rank_t2i), _p(diag),
                      ws.data_ptr(), ws.numel())
+
+    @staticmethod
+    def topk_workspace_bytes(n_img, n_txt, dx, dy, params, precision, k):
+        return _hip.load().mi_topk_bilinear_workspace_bytes(n_img, n_txt, dx, dy, precision, k)
+
+    def topk_call(self, x, y, params, sid_img, sid_txt, precision, k, out_i2t, out_t2i, ws):
+        """Top-k retrieval over a gallery (mi_topk_bilinear); ``out_i2t`` / ``out_t2i`` are (idx int32, val float32)
+        pairs [n_img, k] / [n_txt, k] (either may be None), ``sid_img`` / ``sid_txt`` id codes or both None."""
+        (ii, vi), (it, vt) = out_i2t or (None, None), out_t2i or (None, None)
+        return _call("mi_topk_bilinear", x.device, x.data_ptr(), y.data_ptr(), _p(params[0] if params else None),
+                     _p(sid_img), _p(sid_txt), x.shape[0], y.shape[0], x.shape[1], y.shape[1], precision, k, _p(ii), _p(vi),
+                     _p(it), _p(vt), ws.data_ptr(), ws.numel())
 
     @staticmethod
     def nce_shard_workspace_bytes(br, b, dx, dy, params, precision):
@@ -414,6 +453,18 @@ class HipSeparableOps(_HipOps):
         return _call("mi_rank_separable", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
                      sid.data_ptr(), x.shape[0], x.shape[1], y.shape[1], wg.shape[1], precision, _p(rank_i2t),
                      _p(rank_t2i), _p(diag), ws.data_ptr(), ws.numel())
+
+    @staticmethod
+    def topk_workspace_bytes(n_img, n_txt, dx, dy, params, precision, k):
+        return _hip.load().mi_topk_separable_workspace_bytes(n_img, n_txt, dx, dy, params[0].shape[1], precision, k)
+
+    def topk_call(self, x, y, params, sid_img, sid_txt, precision, k, out_i2t, out_t2i, ws):
+        """Top-k retrieval over a gallery (mi_topk_separable), as ``HipBilinearOps.topk_call``."""
+        wg, wh = params
+        (ii, vi), (it, vt) = out_i2t or (None, None), out_t2i or (None, None)
+        return _call("mi_topk_separable", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(), _p(sid_img),
+                     _p(sid_txt), x.shape[0], y.shape[0], x.shape[1], y.shape[1], wg.shape[1], precision, k, _p(ii), _p(vi),
+                     _p(it), _p(vt), ws.data_ptr(), ws.numel())
 
     @staticmethod
     def nce_shard_workspace_bytes(br, b, dx, dy, params, precision):

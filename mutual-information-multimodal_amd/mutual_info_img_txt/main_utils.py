@@ -187,6 +187,16 @@ class MultiModalManager:
         ri, rt = retrieval.retrieval_ranks(embedding_img, embedding_txt, study_id, self.mi_discriminator, precision)
         return {"i2t": retrieval.retrieval_metrics(ri, ks), "t2i": retrieval.retrieval_metrics(rt, ks)}
 
+    def gallery_eval(self, embedding_img, img_ids, embedding_txt, txt_ids, ks=(1, 5, 10), precision: str = "f32"):
+        """Gallery retrieval under the manager's critic (``retrieval.retrieval_topk`` without exclusion): N images against
+        M reports, relevance by study id (a study may have several images).  ``{"i2t": metrics, "t2i": metrics}`` with
+        ``retrieval.gallery_recall`` of each direction (recall@K for each K of ``ks``, MRR of the first hit).  A make_mlp
+        critic takes N == M only.  Evaluation only: no gradients."""
+        from . import retrieval
+        top = retrieval.retrieval_topk(embedding_img, embedding_txt, self.mi_discriminator, max(int(k) for k in ks), precision)
+        return {"i2t": retrieval.gallery_recall(top["i2t"][0], img_ids, txt_ids, ks),
+                "t2i": retrieval.gallery_recall(top["t2i"][0], txt_ids, img_ids, ks)}
+
     # ------------------------------------------------------------------------------------------ batches
     def _build_loader(self, text_token_features, args):
         """Dataset + shuffling ``drop_last`` DataLoader of the reference (main_utils.py:123-129), built once per manager:
