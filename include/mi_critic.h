@@ -486,6 +486,46 @@ int mi_topk_separable(const float* x, const float* y, const float* wg, const flo
                       int precision, int k, int32_t* idx_i2t, float* val_i2t, int32_t* idx_t2i, float* val_t2i,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- hard-negative InfoNCE ---------------------------------------------------------------- */
+/* The per-sample InfoNCE above on each query's top-k negatives.  H_i = the image -> report list of mi_topk_* for row i of
+ * the square batch with sid on both sides (the first min(k, #negatives) negatives in "score descending, index
+ * ascending"), H'_j = the report -> image list of column j:
+ *   r_i = log(exp S[i, i] + sum_{j in H_i} exp S[i, j]),   c_j = log(exp S[j, j] + sum_{i in H'_j} exp S[i, j])
+ *   MI_NCE_ROWWISE:   L = (1/b) sum_i (r_i - S[i, i])
+ *   MI_NCE_SYMMETRIC: half of that plus half of (1/b) sum_j (c_j - S[j, j])
+ * The selection is a constant of the gradient (its derivative almost everywhere): dL/dS is nonzero exactly on the
+ * diagonal and at the listed indices.  A row or column without negatives contributes exactly 0; k >= every row's (and
+ * column's) negative count gives the loss of mi_nce_*.  A TRAINING LOSS, NOT AN MI BOUND: the candidates were chosen by
+ * score, so log(k + 1) - L bounds nothing.  Deterministic: integer selection, fixed-order reductions, no float atomics.
+ * k in [1, MI_TOPK_MAX_K]; precisions and paths as mi_nce_*_step (MI_PREC_FP8 / F16 / F16X3: MI_EINVAL).
+ * Outputs: loss_out [1]; optional lse_rows [b], idx_rows int32 [b, k] (H_i, tail -1); in the symmetric mode also the
+ * optional lse_cols [b], idx_cols [b, k] (H'_j) -- MI_NCE_ROWWISE takes no column side and leaves both untouched.
+ * Gradient pointers all NULL: the forward launches only, and the workspace query with with_grads == 0 (linear in b: no
+ * G) suffices; otherwise every gradient is written (of grad_out[0] * loss; grad_out NULL: 1) and the workspace is that of
+ * with_grads != 0 (the nce step's plus the lists: 8 k 2b bytes of keys, idx / val, O(b) floats). */
+size_t mi_hardnce_bilinear_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int precision, int k, int with_grads);
+int mi_hardnce_bilinear_step(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t d_img,
+                             int64_t d_txt, int mode, int precision, int k, const float* grad_out, float* loss_out,
+                             float* lse_rows, float* lse_cols, int32_t* idx_rows, int32_t* idx_cols, float* grad_x,
+                             float* grad_y, float* grad_w, void* workspace, size_t workspace_bytes, void* stream);
+size_t mi_hardnce_separable_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int precision, int k,
+                                            int with_grads);
+int mi_hardnce_separable_step(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid,
+                              int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int mode, int precision, int k,
+                              const float* grad_out, float* loss_out, float* lse_rows, float* lse_cols, int32_t* idx_rows,
+                              int32_t* idx_cols, float* grad_x, float* grad_y, float* grad_wg, float* grad_wh,
+                              void* workspace, size_t workspace_bytes, void* stream);
+/* on a caller's fp32 [b, b] score matrix (any critic): the lists by mi_topk_matrix's kernel on both axes.  The backward
+ * reads the forward's idx_rows and lse_rows (and idx_cols, lse_cols in the symmetric mode) and writes the dense
+ * grad_scores [b, b] = grad_out[0] * dloss/dS, zero outside the lists and the diagonal. */
+size_t mi_matrix_hardnce_workspace_bytes(int64_t b, int k);
+int mi_matrix_hardnce_fwd(const float* scores, const int64_t* sid, int64_t b, int mode, int k, float* loss_out,
+                          float* lse_rows, float* lse_cols, int32_t* idx_rows, int32_t* idx_cols, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int mi_matrix_hardnce_bwd(const float* scores, int64_t b, int mode, int k, const int32_t* idx_rows, const int32_t* idx_cols,
+                          const float* lse_rows, const float* lse_cols, const float* grad_out, float* grad_scores,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

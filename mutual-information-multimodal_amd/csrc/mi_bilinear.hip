@@ -22,6 +22,7 @@
 #include "mi_fdiv.h"
 #include "mi_rank.h"
 #include "mi_topk.h"
+#include "mi_hardnce.h"
 
 namespace mi {
 
@@ -1846,6 +1847,111 @@ static int topk_check_dirs(const char* fn, const int64_t* sid_img, const int64_t
   return MI_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ hard-negative InfoNCE
+// (mi_hardnce.h)  The top-k selection of the square batch with ids on both sides, the loss on the
+// lists, and the gradient half of the chain with an epilogue that keeps G on the lists and the diagonal:
+//   prep + T = X W -> lists emptied -> sweep image -> report (its epilogue also writes S[i, i]) + finish
+//   [symmetric] sweep report -> image + finish -> hardnce_rows_kernel + nce_loss_kernel
+//   [grads] G GEMM -> dT = G Y | dY = G^T T -> dW = X^T dT | dX = dT W^T
+struct HardNceEst {
+  using GradIn = HardNceGradIn;
+  template <typename TG>
+  using Grad = EpiHardNceGrad<TG>;
+  using Grad16 = EpiHardNceGrad2;
+  static int check_mode(const char* fn, int mode) { return NceEst::check_mode(fn, mode); }
+  static constexpr const char* kName = "the hard-negative InfoNCE";
+  static constexpr const char* kT = "hardnce T = X W (generic)";
+  static constexpr const char* kScores = "hardnce score + inserts (generic)";
+  static constexpr const char* kScores16 = "hardnce score + inserts";
+  static constexpr const char* kG = "hardnce G (generic)";
+  static constexpr const char* kG16 = "hardnce G";
+  static constexpr SepLabels kSep = {"hardnce separable A = X Wg",     "hardnce separable C = Y Wh",
+                                     "hardnce separable dX = dA Wg^T", "hardnce separable dWg = X^T dA",
+                                     "hardnce separable dY = dC Wh^T", "hardnce separable dWh = Y^T dC"};
+};
+
+static int hardnce_check(const char* fn, int64_t b, int64_t dx, int64_t dy, int mode, int precision, int k) {
+  const int rc = chain_check<HardNceEst>(fn, b, b, 0, dx, dy, mode, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(b < ((int64_t)1 << 31), "%s: b must be below 2^31", fn);
+  MI_CHECK_ARG(k >= 1 && k <= kTopkMaxK, "%s: k must be in [1, %d] (got %d)", fn, kTopkMaxK, k);
+  return MI_OK;
+}
+
+// grads: the nce step's plan (with G and G^T); forward only: the forward half's buffers alone, linear in b
+struct HardNceBilinearPlan {
+  BilinearPlan p;
+  float* diag;  // [b]
+  HardNceLists q;
+  size_t bytes;
+};
+static HardNceBilinearPlan plan_hardnce_bilinear(Workspace& ws, int64_t b, int64_t dx, int64_t dy, int precision, int k,
+                                                 bool grads) {
+  HardNceBilinearPlan n{};
+  if (grads) {
+    n.p = plan_bilinear(ws, b, b, dx, dy, precision, true, true);
+    n.diag = ws.take<float>(b);
+  } else {
+    const RankBilinearPlan f = plan_rank_bilinear(ws, b, dx, dy, precision);
+    n.p = f.p;
+    n.diag = f.diag;
+  }
+  n.q = plan_hardnce_lists(ws, b, k);
+  n.bytes = ws.off;
+  return n;
+}
+static SeparableChainPlan<HardNceBilinearPlan> plan_hardnce_separable(Workspace& ws, int64_t b, int64_t kp, int precision,
+                                                                      int k, bool grads) {
+  return plan_separable_chain(ws, b, b, kp, [&] { return plan_hardnce_bilinear(ws, b, kp, kp, precision, k, grads); });
+}
+
+// One direction's sweep on the square batch, operands as topk_sweep: the query side is the GEMM's B operand.
+static int hardnce_sweep(bool i2t, const float* x, const float* y, const float* w, const int64_t* sid, int64_t b,
+                         int64_t dx, int64_t dy, int precision, int k, const HardNceBilinearPlan& n, hipStream_t st) {
+  const BilinearPlan& p = n.p;
+  const EpiHardNceInsert e{TopkOut{sid, sid, i2t ? n.q.keys : n.q.keys + b * k, k}, i2t ? n.diag : nullptr};
+  if (chain_16bit_ok(b, b, dx, dy, precision)) {
+    const int64_t kk = p.x3 * dy;
+    const GemmBf16Args g = i2t ? one_problem(p.yb, kk, p.tb, kk, b, b, kk) : one_problem(p.tb, kk, p.yb, kk, b, b, kk);
+    return launch_gemm_bf16(g, 1, e, st, HardNceEst::kScores16);
+  }
+  return with_operand_type(precision == MI_PREC_BF16, [&](auto* op) {
+    using OpT = OperandOf<decltype(op)>;
+    const auto img = make_operand(w ? (const float*)p.t : x, dy, 1), txt = make_operand(y, dy, 1);
+    if (i2t) return launch_gemm<OpT>(txt, img, b, b, dy, e, st, HardNceEst::kScores);
+    return launch_gemm<OpT>(img, txt, b, b, dy, e, st, HardNceEst::kScores);
+  });
+}
+
+// The whole step on (x, y, w); idx_rows / idx_cols: the caller's copies of the lists or null (the workspace's are used)
+static int hardnce_chain(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t dx,
+                         int64_t dy, int mode, int precision, int k, const float* grad_out, float* loss_out,
+                         float* lse_rows, float* lse_cols, int32_t* idx_rows, int32_t* idx_cols, float* grad_x,
+                         float* grad_y, float* grad_w, bool any_grad, const HardNceBilinearPlan& n, hipStream_t st) {
+  const bool sym = mode == MI_NCE_SYMMETRIC;
+  const HardNceLists& q = n.q;
+  int32_t* ir = idx_rows ? idx_rows : q.idx;
+  int32_t* ic = idx_cols ? idx_cols : q.idx + b * k;
+  int rc = chain_operands<HardNceEst>(x, y, w, nullptr, nullptr, b, b, 0, dx, dy, precision, n.p, st);
+  if (rc) return rc;
+  rc = topk_zero(q.keys, (sym ? 2 : 1) * b * k, st);
+  if (rc) return rc;
+  rc = hardnce_sweep(true, x, y, w, sid, b, dx, dy, precision, k, n, st);
+  if (rc) return rc;
+  rc = topk_finish(q.keys, b, k, ir, q.val, st);
+  if (rc) return rc;
+  if (sym) {
+    rc = hardnce_sweep(false, x, y, w, sid, b, dx, dy, precision, k, n, st);
+    if (rc) return rc;
+    rc = topk_finish(q.keys + b * k, b, k, ic, q.val + b * k, st);
+    if (rc) return rc;
+  }
+  rc = hardnce_finish(q.val, q.val + b * k, n.diag, 1, b, k, mode, q, loss_out, lse_rows, lse_cols, st);
+  if (rc || !any_grad) return rc;
+  return chain_grads<HardNceEst>(x, y, w, b, b, dx, dy, precision, hardnce_grad_in(ir, ic, k, q.r, q.c, grad_out, b, mode),
+                                 grad_x, grad_y, grad_w, n.p, st);
+}
+
 }  // namespace mi
 
 extern "C" {
@@ -2290,6 +2396,122 @@ int mi_topk_separable(const float* x, const float* y, const float* wg, const flo
                          sp.c, st);
   if (rc) return rc;
   return topk_chain(sp.a, sp.c, nullptr, sid_img, sid_txt, n_img, n_txt, d_proj, d_proj, precision, k, d, sp.n, st);
+}
+
+// ------------------------------------------------------------------------------------------------ hard-negative InfoNCE
+size_t mi_hardnce_bilinear_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int precision, int k, int with_grads) {
+  if (b <= 0 || d_img <= 0 || d_txt <= 0 || k < 1 || k > kTopkMaxK) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_hardnce_bilinear(ws, b, d_img, d_txt, precision, k, with_grads != 0).bytes + 256;
+}
+
+int mi_hardnce_bilinear_step(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t d_img,
+                             int64_t d_txt, int mode, int precision, int k, const float* grad_out, float* loss_out,
+                             float* lse_rows, float* lse_cols, int32_t* idx_rows, int32_t* idx_cols, float* grad_x,
+                             float* grad_y, float* grad_w, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && sid && loss_out && workspace, "mi_hardnce_bilinear_step: null pointer");
+  int rc = hardnce_check("mi_hardnce_bilinear_step", b, d_img, d_txt, mode, precision, k);
+  if (rc) return rc;
+  MI_CHECK_ARG(w || d_img == d_txt, "mi_hardnce_bilinear_step: w == NULL (S = X Y^T) needs d_img == d_txt");
+  const bool any_grad = grad_x || grad_y || grad_w;
+  MI_CHECK_ARG(!any_grad || (grad_x && grad_y && (w ? grad_w != nullptr : grad_w == nullptr)),
+               "mi_hardnce_bilinear_step: pass grad_x, grad_y and (with w) grad_w, or none of them");
+  Workspace ws(workspace, workspace_bytes);
+  const HardNceBilinearPlan n = plan_hardnce_bilinear(ws, b, d_img, d_txt, precision, k, any_grad);
+  rc = ws_fits(ws, "mi_hardnce_bilinear_step");
+  if (rc) return rc;
+  return hardnce_chain(x, y, w, sid, b, d_img, d_txt, mode, precision, k, grad_out, loss_out, lse_rows, lse_cols, idx_rows,
+                       idx_cols, grad_x, grad_y, grad_w, any_grad, n, (hipStream_t)stream);
+}
+
+size_t mi_hardnce_separable_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int precision, int k,
+                                            int with_grads) {
+  if (b <= 0 || d_img <= 0 || d_txt <= 0 || d_proj <= 0 || k < 1 || k > kTopkMaxK) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_hardnce_separable(ws, b, d_proj, precision, k, with_grads != 0).bytes + 256;
+}
+
+int mi_hardnce_separable_step(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid,
+                              int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int mode, int precision, int k,
+                              const float* grad_out, float* loss_out, float* lse_rows, float* lse_cols, int32_t* idx_rows,
+                              int32_t* idx_cols, float* grad_x, float* grad_y, float* grad_wg, float* grad_wh,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && wg && wh && sid && loss_out && workspace, "mi_hardnce_separable_step: null pointer");
+  int rc = hardnce_check("mi_hardnce_separable_step", b, d_img, d_txt, mode, precision, k);
+  if (rc) return rc;
+  MI_CHECK_ARG(d_proj >= 1, "mi_hardnce_separable_step: projection width must be >= 1");
+  const bool any_grad = grad_x || grad_y || grad_wg || grad_wh;
+  MI_CHECK_ARG(!any_grad || (grad_x && grad_y && grad_wg && grad_wh),
+               "mi_hardnce_separable_step: pass all four gradients or none of them");
+  Workspace ws(workspace, workspace_bytes);
+  const auto sp = plan_hardnce_separable(ws, b, d_proj, precision, k, any_grad);
+  rc = ws_fits(ws, "mi_hardnce_separable_step");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t kp = d_proj;
+  const bool bf = precision == MI_PREC_BF16;
+  rc = separable_project(HardNceEst::kSep, bf, x, y, wg, wh, b, b, d_img, d_txt, kp, sp.a, sp.c, st);
+  if (rc) return rc;
+  rc = hardnce_chain(sp.a, sp.c, nullptr, sid, b, kp, kp, mode, precision, k, grad_out, loss_out, lse_rows, lse_cols,
+                     idx_rows, idx_cols, sp.da, sp.dc, nullptr, any_grad, sp.n, st);
+  if (rc || !any_grad) return rc;
+  return separable_project_back(HardNceEst::kSep, bf, x, y, wg, wh, b, b, d_img, d_txt, kp, sp.da, sp.dc, grad_x, grad_y,
+                                grad_wg, grad_wh, st);
+}
+
+size_t mi_matrix_hardnce_workspace_bytes(int64_t b, int k) {
+  if (b <= 0 || k < 1 || k > kTopkMaxK) return 0;
+  Workspace ws(nullptr, 0);
+  plan_hardnce_lists(ws, b, k);
+  return ws.off + 256;
+}
+
+int mi_matrix_hardnce_fwd(const float* scores, const int64_t* sid, int64_t b, int mode, int k, float* loss_out,
+                          float* lse_rows, float* lse_cols, int32_t* idx_rows, int32_t* idx_cols, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(scores && sid && loss_out && workspace, "mi_matrix_hardnce_fwd: null pointer");
+  MI_CHECK_ARG(b >= 1 && b < ((int64_t)1 << 31), "mi_matrix_hardnce_fwd: b must be in [1, 2^31)");
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || mode == MI_NCE_SYMMETRIC, "mi_matrix_hardnce_fwd: unknown mode %d", mode);
+  MI_CHECK_ARG(k >= 1 && k <= kTopkMaxK, "mi_matrix_hardnce_fwd: k must be in [1, %d] (got %d)", kTopkMaxK, k);
+  Workspace ws(workspace, workspace_bytes);
+  const HardNceLists q = plan_hardnce_lists(ws, b, k);
+  int rc = ws_fits(ws, "mi_matrix_hardnce_fwd");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const bool sym = mode == MI_NCE_SYMMETRIC;
+  rc = topk_zero(q.keys, (sym ? 2 : 1) * b * k, st);
+  if (rc) return rc;
+  rc = topk_matrix(scores, sid, sid, b, b, 0, q.keys, k, st);
+  if (rc) return rc;
+  rc = topk_finish(q.keys, b, k, idx_rows ? idx_rows : q.idx, q.val, st);
+  if (rc) return rc;
+  if (sym) {
+    rc = topk_matrix(scores, sid, sid, b, b, 1, q.keys + b * k, k, st);
+    if (rc) return rc;
+    rc = topk_finish(q.keys + b * k, b, k, idx_cols ? idx_cols : q.idx + b * k, q.val + b * k, st);
+    if (rc) return rc;
+  }
+  return hardnce_finish(q.val, q.val + b * k, scores, b + 1, b, k, mode, q, loss_out, lse_rows, lse_cols, st);
+}
+
+int mi_matrix_hardnce_bwd(const float* scores, int64_t b, int mode, int k, const int32_t* idx_rows, const int32_t* idx_cols,
+                          const float* lse_rows, const float* lse_cols, const float* grad_out, float* grad_scores,
+                          void* stream) {
+  MI_CHECK_ARG(scores && idx_rows && lse_rows && grad_scores, "mi_matrix_hardnce_bwd: null pointer");
+  MI_CHECK_ARG(b >= 1 && b < ((int64_t)1 << 31), "mi_matrix_hardnce_bwd: b must be in [1, 2^31)");
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || mode == MI_NCE_SYMMETRIC, "mi_matrix_hardnce_bwd: unknown mode %d", mode);
+  MI_CHECK_ARG(k >= 1 && k <= kTopkMaxK, "mi_matrix_hardnce_bwd: k must be in [1, %d] (got %d)", kTopkMaxK, k);
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || (idx_cols && lse_cols),
+               "mi_matrix_hardnce_bwd: the symmetric mode needs idx_cols and lse_cols");
+  const int64_t nt = (b + 63) / 64;
+  hipStream_t st = (hipStream_t)stream;
+  {
+    ProfScope prof_("hardnce_matrix_grad_kernel", st);
+    hipLaunchKernelGGL(hardnce_matrix_grad_kernel, dim3((unsigned)nt, (unsigned)nt), dim3(64), 0, st, scores, b,
+                       hardnce_grad_in(idx_rows, idx_cols, k, lse_rows, lse_cols, grad_out, b, mode), grad_scores);
+  }
+  MI_LAUNCH_CHECK("hardnce_matrix_grad_kernel");
+  return MI_OK;
 }
 
 }  // extern "C"

@@ -76,9 +76,12 @@ def train_mutual_information(args, device):
                         format='%(asctime)s - %(name)s %(message)s', datefmt='%m-%d %H:%M', force=True)
     logging.getLogger(__name__).info(f"args: {args}")
     critic = getattr(args, "critic", "concat_mlp")
+    # --hard_negatives K: the hard-negative form of the per-sample InfoNCE, validated with its estimator at construction
+    hard_k = getattr(args, "hard_negatives", None)
+    hard = {} if hard_k is None else dict(mi_estimator=getattr(args, "mi_estimator", None), hard_negatives=hard_k)
     if getattr(args, "synthetic", False):
         model_manager = MultiModalManager(d_img=args.embed_dim_img, d_txt=args.embed_dim_txt, critic=critic,
-                                          mi_estimator=getattr(args, "mi_estimator", None))
+                                          mi_estimator=getattr(args, "mi_estimator", None), hard_negatives=hard_k)
         source = synthetic_embedding_source(args, device)
     elif getattr(args, "synthetic_encoders", False):
         from mutual_info_img_txt.model import ResNet256_6_2_1, TextBert
@@ -86,14 +89,14 @@ def train_mutual_information(args, device):
         cfg = _small_bert_config(oc)
         model_manager = MultiModalManager(output_channels=oc, image_model=ResNet256_6_2_1(output_channels=oc),
                                           text_model=TextBert(cfg), bert_config=cfg, critic=critic,
-                                          embed_proj_dim=getattr(args, "embed_proj_dim", None))
+                                          embed_proj_dim=getattr(args, "embed_proj_dim", None), **hard)
         source = synthetic_encoder_batches(args, vocab_size=cfg.vocab_size)
     else:
         model_manager = MultiModalManager(bert_pretrained_dir=args.bert_pretrained_dir,
                                           bert_config_name=args.bert_config_name,
                                           output_channels=args.output_channels,
                                           image_model_name=args.image_model_name, critic=critic,
-                                          embed_proj_dim=getattr(args, "embed_proj_dim", None))
+                                          embed_proj_dim=getattr(args, "embed_proj_dim", None), **hard)
         source = getattr(args, "data_loader", None) or args.text_token_features
     print("Start training for ImageTextModelManager")
     model_manager.train(source, device=device, args=args)

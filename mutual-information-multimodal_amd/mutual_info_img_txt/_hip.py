@@ -191,6 +191,13 @@ SIGNATURES = {
     "mi_topk_bilinear": (c_int, [_P] * 5 + [_I64] * 4 + [_I, _I] + [_P] * 5 + [_SZ, _P]),
     "mi_topk_separable_workspace_bytes": (_SZ, [_I64] * 5 + [_I, _I]),
     "mi_topk_separable": (c_int, [_P] * 6 + [_I64] * 5 + [_I, _I] + [_P] * 5 + [_SZ, _P]),
+    "mi_hardnce_bilinear_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I, _I, _I]),
+    "mi_hardnce_bilinear_step": (c_int, [_P] * 4 + [_I64] * 3 + [_I, _I, _I] + [_P] * 10 + [_SZ, _P]),
+    "mi_hardnce_separable_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I, _I, _I]),
+    "mi_hardnce_separable_step": (c_int, [_P] * 5 + [_I64] * 4 + [_I, _I, _I] + [_P] * 11 + [_SZ, _P]),
+    "mi_matrix_hardnce_workspace_bytes": (_SZ, [_I64, _I]),
+    "mi_matrix_hardnce_fwd": (c_int, [_P, _P, _I64, _I, _I] + [_P] * 6 + [_SZ, _P]),
+    "mi_matrix_hardnce_bwd": (c_int, [_P, _I64, _I, _I] + [_P] * 7),
 }
 MI_TOPK_MAX_K = 32  # include/mi_critic.h
 

@@ -1,5 +1,5 @@
 """The one binding of the critic entry points of the C ABI (mi_bilinear_*, mi_separable_*, mi_concat_mlp_*, mi_nce_*,
-mi_fdiv_*, mi_rank_*, mi_topk_*), shared by ``mi_critics`` (eager autograd), ``graphed`` (hipGraph step) and ``distributed`` (sharded step).
+mi_fdiv_*, mi_rank_*, mi_topk_*, mi_hardnce_*), shared by ``mi_critics`` (eager autograd), ``graphed`` (hipGraph step) and ``distributed`` (sharded step).
 
 An ops object scores the row block ``x`` [b_rows, d_img] (starting at ``row_offset``) against all of ``y_all``
 [b, d_txt]; a whole batch is ``b_rows == b``, ``row_offset == 0``.  Each ``*_call`` method writes one entry point's
@@ -101,6 +101,28 @@ def topk_matrix(scores, k, axis=0, sid_rows=None, sid_cols=None):
     return idx, val
 
 
+def hardnce_matrix_fwd(scores, sid, mode, k):
+    """Hard-negative InfoNCE of a float32 [B, B] score matrix (mi_matrix_hardnce_fwd): (loss [1], lse_rows, lse_cols,
+    idx_rows, idx_cols); the column side is None in the row-wise mode."""
+    b, dev = scores.shape[0], scores.device
+    sym = mode == _hip.MI_NCE_SYMMETRIC
+    ws = _hip.workspace(_hip.load().mi_matrix_hardnce_workspace_bytes(b, k), dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    r, ir = torch.empty(b, dtype=torch.float32, device=dev), torch.empty(b, k, dtype=torch.int32, device=dev)
+    c, ic = (torch.empty_like(r), torch.empty_like(ir)) if sym else (None, None)
+    _hip.call("mi_matrix_hardnce_fwd", dev, scores.data_ptr(), sid.data_ptr(), b, mode, k, loss.data_ptr(), r.data_ptr(),
+              _p(c), ir.data_ptr(), _p(ic), ws.data_ptr(), ws.numel())
+    return loss, r, c, ir, ic
+
+
+def hardnce_matrix_bwd(scores, mode, k, r, c, idx_rows, idx_cols, grad_out):
+    """grad_scores [B, B] of grad_out[0] * loss (mi_matrix_hardnce_bwd) from the forward's lists and LSEs."""
+    g = torch.empty_like(scores)
+    _hip.call("mi_matrix_hardnce_bwd", scores.device, scores.data_ptr(), scores.shape[0], mode, k, idx_rows.data_ptr(),
+              _p(idx_cols), r.data_ptr(), _p(c), _p(grad_out), g.data_ptr())
+    return g
+
+
 class _HipOps:
     """The ops protocol of ``distributed.GlobalBatchCriticFn`` (forward / merge / backward) on the C ABI.  ``saved`` is
     (x, y_all, params, sid_rows, sid_all, row_offset, precision, scores, ws) for every critic."""
@@ -179,6 +201,21 @@ class _HipOps:
         out_t = topk_outputs(n_txt, k, dev) if t2i else None
         self.topk_call(x, y, params, sid_img, sid_txt, precision, k, out_i, out_t, ws)()
         return out_i, out_t
+
+    def hardnce_step(self, x, y, params, sid, mode, precision, k, need_grad):
+        """The hard-negative InfoNCE of the whole batch in one call of ``mi_hardnce_<critic>_step`` (bilinear and separable
+        critics), with the gradients of 1 * loss when ``need_grad``: (loss [1], lse_rows [B], lse_cols [B] or None,
+        idx_rows int32 [B, k], idx_cols or None, [grad_x, grad_y, grad_params...] or []).  The column side exists in
+        the symmetric mode only."""
+        b, dev = x.shape[0], x.device
+        ws = _hip.workspace(self.hardnce_workspace_bytes(b, x.shape[1], y.shape[1], params, precision, k, need_grad), dev)
+        sym = mode == _hip.MI_NCE_SYMMETRIC
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        r, ir = torch.empty(b, dtype=torch.float32, device=dev), torch.empty(b, k, dtype=torch.int32, device=dev)
+        c, ic = (torch.empty_like(r), torch.empty_like(ir)) if sym else (None, None)
+        grads = [torch.empty_like(t) for t in (x, y, *params)] if need_grad else []
+        self.hardnce_call(x, y, params, sid, mode, precision, k, loss, r, c, ir, ic, grads, ws)()
+        return loss, r, c, ir, ic, grads
 
     # ---------------------------------------------- per-sample InfoNCE on a row block (distributed.GlobalBatchNceFn)
     def nce_forward(self, x, y_all, params, sid_rows, sid_all, row_offset, mode, precision, need_grad=True):
@@ -286,6 +323,19 @@ class HipBilinearOps(_HipOps):
         return _call("mi_topk_bilinear", x.device, x.data_ptr(), y.data_ptr(), _p(params[0] if params else None),
                      _p(sid_img), _p(sid_txt), x.shape[0], y.shape[0], x.shape[1], y.shape[1], precision, k, _p(ii), _p(vi),
                      _p(it), _p(vt), ws.data_ptr(), ws.numel())
+
+    @staticmethod
+    def hardnce_workspace_bytes(b, dx, dy, params, precision, k, need_grad):
+        return _hip.load().mi_hardnce_bilinear_workspace_bytes(b, dx, dy, precision, k, int(bool(need_grad)))
+
+    def hardnce_call(self, x, y, params, sid, mode, precision, k, loss, r, c, idx_rows, idx_cols, grads, ws):
+        """Hard-negative InfoNCE step (mi_hardnce_bilinear_step); ``c`` / ``idx_cols`` None in the row-wise mode,
+        ``grads`` [] for the forward launches alone."""
+        w = params[0] if params else None
+        gx, gy, gw = (grads + [None] * 3)[:3]
+        return _call("mi_hardnce_bilinear_step", x.device, x.data_ptr(), y.data_ptr(), _p(w), sid.data_ptr(), x.shape[0],
+                     x.shape[1], y.shape[1], mode, precision, k, None, loss.data_ptr(), _p(r), _p(c), _p(idx_rows),
+                     _p(idx_cols), _p(gx), _p(gy), _p(gw), ws.data_ptr(), ws.numel())
 
     @staticmethod
     def nce_shard_workspace_bytes(br, b, dx, dy, params, precision):
@@ -465,6 +515,19 @@ class HipSeparableOps(_HipOps):
         return _call("mi_topk_separable", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(), _p(sid_img),
                      _p(sid_txt), x.shape[0], y.shape[0], x.shape[1], y.shape[1], wg.shape[1], precision, k, _p(ii), _p(vi),
                      _p(it), _p(vt), ws.data_ptr(), ws.numel())
+
+    @staticmethod
+    def hardnce_workspace_bytes(b, dx, dy, params, precision, k, need_grad):
+        return _hip.load().mi_hardnce_separable_workspace_bytes(b, dx, dy, params[0].shape[1], precision, k,
+                                                                int(bool(need_grad)))
+
+    def hardnce_call(self, x, y, params, sid, mode, precision, k, loss, r, c, idx_rows, idx_cols, grads, ws):
+        """Hard-negative InfoNCE step (mi_hardnce_separable_step), as ``HipBilinearOps.hardnce_call``."""
+        wg, wh = params
+        return _call("mi_hardnce_separable_step", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
+                     sid.data_ptr(), x.shape[0], x.shape[1], y.shape[1], wg.shape[1], mode, precision, k, None,
+                     loss.data_ptr(), _p(r), _p(c), _p(idx_rows), _p(idx_cols), *[_p(g) for g in grads or [None] * 4],
+                     ws.data_ptr(), ws.numel())
 
     @staticmethod
     def nce_shard_workspace_bytes(br, b, dx, dy, params, precision):

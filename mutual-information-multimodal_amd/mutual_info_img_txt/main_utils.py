@@ -102,7 +102,7 @@ class MultiModalManager:
     def __init__(self, bert_pretrained_dir=None, bert_config_name=None, output_channels=None, image_model_name=None, *,
                  d_img: int = 768, d_txt: int = 768, critic: str = "concat_mlp", hidden_dims=(1024, 512),
                  d_proj: int = 256, image_model=None, text_model=None, bert_config=None, embed_proj_dim=None,
-                 autocast_dtype=None, mi_estimator: Optional[str] = None):
+                 autocast_dtype=None, mi_estimator: Optional[str] = None, hard_negatives: Optional[int] = None):
         self.bert_pretrained_dir = bert_pretrained_dir
         self.bert_config_name = bert_config_name
         self.output_channels = output_channels
@@ -134,6 +134,15 @@ class MultiModalManager:
         self.critic_kind = critic
         if mi_estimator is not None:  # the per-sample InfoNCE needs the bilinear or separable critic
             mi_critics.check_estimator(mi_estimator, critic)
+        # hard-negative InfoNCE (hard_negatives.py): the row-wise / symmetric loss on each query's top-k negatives
+        self.hard_negatives = None
+        if hard_negatives is not None:
+            from .hard_negatives import check_k
+            if mi_estimator not in _hip.NCE_ESTIMATORS:
+                raise ValueError(f"hard_negatives is a parameter of the per-sample InfoNCE: it needs mi_estimator in "
+                                 f"{sorted(_hip.NCE_ESTIMATORS)} (got {mi_estimator!r})")
+            self.hard_negatives = check_k(hard_negatives)
+            self.hard_negatives_estimator = mi_estimator
         self.d_img, self.d_txt = d_img, d_txt
         self.training_loss = []
         self._graphed = None
@@ -157,8 +166,17 @@ class MultiModalManager:
         batches.  ``graph=True`` replays the fused step from hipGraphs (``graphed.GraphedMiStep``, built on first use for
         this batch shape; the training loop's setting) for the estimators that GraphedMiStep captures ("dv", "infonce");
         the others ("infonce_rowwise" / "infonce_symmetric", "jsd" / "nwj") always run eagerly through
-        ``fused_mi_bound``, and so does the separable critic."""
+        ``fused_mi_bound``, and so does the separable critic.  A manager built with ``hard_negatives=k`` runs
+        ``hard_negatives.hard_negative_infonce`` here, eagerly (a training loss, not an MI bound)."""
         est = mi_critics.check_estimator(mi_estimator, self.critic_kind)
+        if self.hard_negatives is not None:
+            if mi_estimator != self.hard_negatives_estimator:
+                raise ValueError(f"this manager trains the hard-negative form of {self.hard_negatives_estimator!r}; "
+                                 f"mi_step got mi_estimator={mi_estimator!r}")
+            from .hard_negatives import hard_negative_infonce
+            return hard_negative_infonce(embedding_img, embedding_txt, study_id, self.mi_discriminator,
+                                         self.hard_negatives, symmetric=mi_estimator == "infonce_symmetric",
+                                         precision=precision)
         if fused and graph and est.graphed and self.critic_kind != "separable":
             g = self._graphed
             key = (tuple(embedding_img.shape), tuple(embedding_txt.shape), mi_estimator, precision)

@@ -30,12 +30,21 @@ def construct_training_parameters(argv=None):
     p.add_argument('--embed_proj_dim', default=None, type=int)
     p.add_argument('--no_graph', dest='graph', action='store_false')
     p.add_argument('--seed', default=0, type=int)
+    # hard-negative InfoNCE: train the row-wise / symmetric loss on each query's top-K negatives (a loss, not an MI bound)
+    p.add_argument('--hard_negatives', default=None, type=int)
     return p.parse_args(argv)
 
 
 def check_training_parameters(args):
     """Eager validation of the flags that the reference only trips over inside the training step."""
     check_estimator(args.mi_estimator, args.critic)
+    if getattr(args, "hard_negatives", None) is not None:
+        from mutual_info_img_txt._hip import NCE_ESTIMATORS
+        from mutual_info_img_txt.hard_negatives import check_k
+        if args.mi_estimator not in NCE_ESTIMATORS:
+            raise ValueError(f"--hard_negatives needs --mi_estimator in {sorted(NCE_ESTIMATORS)} "
+                             f"(got {args.mi_estimator!r})")
+        check_k(args.hard_negatives)
     return args
 
 
