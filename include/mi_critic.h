@@ -526,6 +526,41 @@ int mi_matrix_hardnce_bwd(const float* scores, int64_t b, int mode, int k, const
                           const float* lse_rows, const float* lse_cols, const float* grad_out, float* grad_scores,
                           void* stream);
 
+/* Per-sample InfoNCE against a memory bank of past embeddings.  Batch x [b, d_img], y [b, d_txt],
+ * ids sid [b]; bank bank_x [m, d_img], bank_y [m, d_txt], ids bank_sid [m], m >= 1.  The bank is a constant: it gets no
+ * gradient.  S[i, j] = critic(img_i, txt_j) with the current parameters; index b + k is bank entry k on either side.
+ *   C_i = {i} u {j < b : sid_j != sid_i} u {b + k : bank_sid_k != sid_i},  r_i = log sum_{j in C_i} exp S[i, j]
+ *   R_j = {j} u {i < b : sid_i != sid_j} u {b + k : bank_sid_k != sid_j},  c_j = log sum_{i in R_j} exp S[i, j]
+ *   MI_NCE_ROWWISE:   loss = (1/b) sum_i (r_i - S[i,i])                  (reads bank_y only; bank_x may be NULL)
+ *   MI_NCE_SYMMETRIC: loss = 1/2 (1/b) sum_i (r_i - S[i,i]) + 1/2 (1/b) sum_j (c_j - S[j,j])
+ * A bank entry of the query's own study is never a candidate; bank entries have no row or column terms of their own; a
+ * row (column) whose only candidate is its positive contributes exactly 0.  With unique ids and bank entries drawn from
+ * the marginal, log(b + m) - loss(rowwise) is the InfoNCE bound with b + m candidates (ceiling log(b + m)); embeddings
+ * of a training queue are stale, then it is a training loss with that ceiling.
+ * Conventions of mi_nce_*_step: w == NULL is S = X Y^T (d_img == d_txt); all gradients NULL runs the forward launches
+ * alone; lse_rows / lse_cols are [b] and optional, lse_cols is not written in the row-wise mode; grad_out scales every
+ * gradient.  Bilinear: grad_w includes bank_x^T (G_left Y), grad_y includes G_left^T (bank_x W).  Separable: the bank's
+ * projections are recomputed in the call and grad_wg / grad_wh include the bank rows' share.
+ * precision: MI_PREC_F32 / BF16 / BF16X3; the 16-bit chain where b, m and the widths are multiples of 8, else the generic
+ * kernels; MI_PREC_FP8 / F16 / F16X3 give MI_EINVAL.  MI_EINVAL also for null required pointers, b < 1, m < 1, bank_x ==
+ * NULL in the symmetric mode, an unknown mode, a partial gradient set, b + m >= 2^31; MI_EWORKSPACE for a short workspace.
+ * The workspace holds G [b, b + m] (and [m, b] in the symmetric mode) in the chain's G type; everything else is linear in
+ * b + m.  No float atomics: two calls give identical bits. */
+size_t mi_banknce_bilinear_workspace_bytes(int64_t b, int64_t m, int64_t d_img, int64_t d_txt, int mode, int precision,
+                                           int with_grads);
+int mi_banknce_bilinear_step(const float* x, const float* y, const float* w, const int64_t* sid, const float* bank_x,
+                             const float* bank_y, const int64_t* bank_sid, int64_t b, int64_t m, int64_t d_img,
+                             int64_t d_txt, int mode, int precision, const float* grad_out, float* loss_out,
+                             float* lse_rows, float* lse_cols, float* grad_x, float* grad_y, float* grad_w, void* workspace,
+                             size_t workspace_bytes, void* stream);
+size_t mi_banknce_separable_workspace_bytes(int64_t b, int64_t m, int64_t d_img, int64_t d_txt, int64_t d_proj, int mode,
+                                            int precision, int with_grads);
+int mi_banknce_separable_step(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid,
+                              const float* bank_x, const float* bank_y, const int64_t* bank_sid, int64_t b, int64_t m,
+                              int64_t d_img, int64_t d_txt, int64_t d_proj, int mode, int precision, const float* grad_out,
+                              float* loss_out, float* lse_rows, float* lse_cols, float* grad_x, float* grad_y,
+                              float* grad_wg, float* grad_wh, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

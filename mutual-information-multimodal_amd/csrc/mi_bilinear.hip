@@ -23,6 +23,7 @@
 #include "mi_rank.h"
 #include "mi_topk.h"
 #include "mi_hardnce.h"
+#include "mi_banknce.h"
 
 namespace mi {
 
@@ -1952,6 +1953,376 @@ static int hardnce_chain(const float* x, const float* y, const float* w, const i
                                  grad_x, grad_y, grad_w, n.p, st);
 }
 
+// ------------------------------------------------------------------------------------------------ memory-bank InfoNCE
+// (mi_banknce.h)  The per-sample InfoNCE of the batch against the batch and a bank of past
+// embeddings: an L-shaped score matrix, a top block [b] x [b + m] (a row block of the chain: br = b, row_offset = 0, the
+// reports of batch and bank behind each other) and, in the symmetric mode, a left block [m] x [b] (bank images against the
+// batch's reports; the GEMM launchers take any m, so it runs as it lies, no transposed formulation).
+//   16-bit chain (bf16 / bf16x3; b, m and the widths multiples of 8):
+//     prep (batch and bank rows converted at their row offsets) -> T = X W [-> U = bank_x W]
+//     -> score GEMM top [-> score GEMM left] -> merge records -> loss
+//     [grads] G top [-> G left] -> dT = G Y_all | dY = G^T T [-> dT slabs -> bf16]
+//             [sym: dU = G_left Y | dY_left = G_left^T U -> dY = top + left (two slabs, fixed order)]
+//             -> dW = X^T dT | dX = dT W^T [sym: dW_bank = bank_x^T dU split-K behind slab 0 = the batch's dW -> reduce]
+//   generic kernels (other shapes, MI_PREC_F32): the same sequence on mi_gemm.h; the reports of batch and bank are
+//     gathered into one fp32 operand first (these kernels read the caller's fp32 rows directly), the two blocks'
+//     contributions to dY and dW are added by the store epilogue's accumulate slot, launch after launch
+// grad_bank_t / grad_bank_y: dS/d(bank image rows of T) and d/d(bank report rows), fp32 [m][dy], for the separable critic
+// whose bank projections depend on Wg, Wh; null for the bilinear critic (the bank is a constant).
+struct BankNceEst {
+  static constexpr const char* kName = "the memory-bank InfoNCE";
+  static constexpr SepLabels kSep = {"banknce separable A = X Wg",      "banknce separable C = Y Wh",
+                                     "banknce separable dX = dA Wg^T",  "banknce separable dWg = X^T dA",
+                                     "banknce separable dY = dC Wh^T",  "banknce separable dWh = Y^T dC"};
+};
+
+struct BankNcePlan {
+  BilinearPlan p;  // the top block: operand copies, T, G, G^T, dT and the slabs of a [b] x [b + m] row block
+  BankNceRecords q;
+  bool c16, sym;
+  float* yall;  // generic kernels: the reports of batch and bank, fp32 [b + m][dy]
+  // the bank's image side (symmetric mode): operand copies, U = bank_x W, G_left, dU
+  bf16_t *bxb, *bxtb, *ub, *utb, *ytb0, *glb, *gltb, *dub, *dutb;
+  float *u, *du;
+  void* gl;
+  float* dy_slab;   // [2][b][dy]: dY of the top and of the left block
+  float* dwb_slab;  // [1 + dwb_splits][dx][dy]: the batch's dW, then the split-K slabs of bank_x^T dU
+  int dwb_splits;
+  int64_t dwb_kchunk;
+  size_t bytes;
+};
+
+// The layout does not depend on w (the workspace query has none).  Forward only: the forward half's buffers alone.
+static BankNcePlan plan_banknce(Workspace& ws, int64_t b, int64_t m, int64_t dx, int64_t dy, int mode, int precision,
+                                bool grads) {
+  BankNcePlan n{};
+  const int64_t nn = b + m;
+  const int64_t x3 = precision == MI_PREC_BF16X3 ? 3 : 1;
+  n.sym = mode == MI_NCE_SYMMETRIC;
+  n.c16 = chain_16bit_ok(b, m, dx, dy, precision);
+  if (grads) {
+    n.p = plan_bilinear(ws, b, nn, dx, dy, precision, true, true);
+  } else {
+    BilinearPlan& p = n.p;
+    p.x3 = (int)x3;
+    if (n.c16) {
+      p.xb = ws.take<bf16_t>(x3 * b * dx);
+      p.xtb = ws.take<bf16_t>(x3 * b * dx);
+      p.yb = ws.take<bf16_t>(x3 * nn * dy);
+      p.ytb = ws.take<bf16_t>(x3 * nn * dy);
+      p.wb = ws.take<bf16_t>(x3 * dx * dy);
+      p.wtb = ws.take<bf16_t>(x3 * dx * dy);
+      p.tb = ws.take<bf16_t>(x3 * b * dy);
+      p.ttb = ws.take<bf16_t>(x3 * b * dy);
+    } else {
+      p.t = ws.take<float>(b * dy);
+      p.gen_slab_floats = precision == MI_PREC_F32 ? generic_slab_floats(b, dy, dx) : 0;
+      p.gen_slab = p.gen_slab_floats > 0 ? ws.take<float>(p.gen_slab_floats) : nullptr;
+    }
+  }
+  n.q = plan_banknce_records(ws, b, m, n.sym);
+  if (!n.c16) n.yall = ws.take<float>(nn * dy);
+  if (n.sym) {
+    if (n.c16) {
+      n.bxb = ws.take<bf16_t>(x3 * m * dx);
+      n.bxtb = ws.take<bf16_t>(x3 * m * dx);
+      n.ub = ws.take<bf16_t>(x3 * m * dy);
+      n.utb = ws.take<bf16_t>(x3 * m * dy);
+    } else {
+      n.u = ws.take<float>(m * dy);
+    }
+    if (grads && n.c16) {
+      n.ytb0 = ws.take<bf16_t>(x3 * b * dy);
+      n.glb = ws.take<bf16_t>(x3 * m * b);
+      n.gltb = ws.take<bf16_t>(x3 * m * b);
+      n.dub = ws.take<bf16_t>(x3 * m * dy);
+      n.dutb = ws.take<bf16_t>(x3 * m * dy);
+      n.dy_slab = ws.take<float>(2 * b * dy);
+      // split-K of dW_bank = bank_x^T dU as plan_bilinear's dW: ~128 workgroups, K chunks multiples of the K tile
+      const int64_t tiles = ((dx + kTile - 1) / kTile) * ((dy + kTile - 1) / kTile);
+      int64_t splits = (128 + tiles - 1) / tiles;
+      int64_t kchunk = (m + splits - 1) / splits;
+      kchunk = (kchunk + kG2KT - 1) / kG2KT * kG2KT;
+      splits = (m + kchunk - 1) / kchunk;
+      n.dwb_splits = (int)splits;
+      n.dwb_kchunk = kchunk;
+      n.dwb_slab = ws.take<float>((1 + splits) * dx * dy);
+    } else if (grads) {
+      if (precision == MI_PREC_BF16) n.gl = ws.take<bf16_t>(m * b);  // G_left in the operand type, as the top block's G
+      else n.gl = ws.take<float>(m * b);
+      n.du = ws.take<float>(m * dy);
+    }
+  }
+  n.bytes = ws.off;
+  return n;
+}
+
+static int banknce_check(const char* fn, int64_t b, int64_t m, int64_t dx, int64_t dy, int mode, int precision) {
+  MI_CHECK_ARG(b >= 1 && m >= 1 && dx >= 1 && dy >= 1, "%s: sizes must be >= 1 (b %lld, m %lld, widths %lld, %lld)", fn,
+               (long long)b, (long long)m, (long long)dx, (long long)dy);
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || mode == MI_NCE_SYMMETRIC, "%s: unknown mode %d", fn, mode);
+  MI_CHECK_ARG(precision == MI_PREC_F32 || precision == MI_PREC_BF16 || precision == MI_PREC_BF16X3,
+               "%s: precision %d is not available for %s (f32, bf16, bf16x3)", fn, precision, BankNceEst::kName);
+  const int64_t lim = (int64_t)1 << 31;
+  MI_CHECK_ARG(b < lim && m < lim && b + m < lim, "%s: b + m must be below 2^31", fn);
+  return MI_OK;
+}
+
+// The gradient half on the 16-bit chain, behind G, G^T (top) and G_left, G_left^T in the plan
+static int banknce_bwd16(bool has_w, int64_t b, int64_t m, int64_t dx, int64_t dy, float* grad_x, float* grad_y,
+                         float* grad_w, float* grad_bank_t, float* grad_bank_y, const BankNcePlan& n, hipStream_t st) {
+  const BilinearPlan& p = n.p;
+  const int64_t nn = b + m;
+  const int x3 = p.x3;
+  const int ra = x3 == 3 ? 1 : 0, rb = x3 == 3 ? 2 : 0;
+  int rc = MI_OK;
+  // problem 0: dT[i, c] = sum_j G[i, j] Y_all[j, c] (K = b + m); problem 1: dY[j, c] = sum_i G[i, j] T[i, c] for the
+  // batch's reports j < b alone (the first b rows of G^T): no dY of bank rows
+  GemmBf16Args two{};
+  two.p[0] = GemmBf16Problem{p.gb, x3 * nn, p.ytb, x3 * nn, b, dy, x3 * nn};
+  two.p[1] = GemmBf16Problem{p.gtb, x3 * b, p.ttb, x3 * b, b, dy, x3 * b};
+  two.n_problems = 2;
+  two.k_chunk = x3 * nn;
+  float* dy_top = n.sym ? n.dy_slab : grad_y;
+  EpiStoreMulti e2{};
+  e2.out[0] = has_w ? EpiOut{nullptr, 0, 0, p.dtb, dy, p.dttb, b, nullptr, ra, rb} : EpiOut{grad_x, dy, 0, nullptr, 0, nullptr, 0};
+  e2.out[1] = EpiOut{dy_top, dy, 0, nullptr, 0, nullptr, 0};
+  bool split_done = false;
+  if (p.dt_splits > 1 && x3 == 1 && has_w) {
+    // short, wide block: dT partial sums over K chunks into fp32 slabs beside dY, then one pass that adds the slabs in
+    // slab order and writes the two bf16 orientations of dT (bilinear_bwd_from_g's split)
+    EpiStoreMulti es{};
+    es.out[0] = EpiOut{p.dt_slab, dy, b * dy, nullptr, 0, nullptr, 0};
+    es.out[1] = e2.out[1];
+    const int sp[2] = {p.dt_splits, 1};
+    const int64_t ch[2] = {p.dt_kchunk, b};
+    rc = launch_gemm_bf16_flat(two, sp, ch, es, st, "banknce dT = G Y | dY = G^T T");
+    if (rc == MI_OK) {
+      CvtJobs jobs{};
+      jobs.j[0] = CvtJob{p.dt_slab, b, dy, p.dtb, p.dttb, p.dt_splits, b * dy};
+      rc = launch_cvt_transpose3(jobs, st, "banknce dT slabs -> bf16");
+      if (rc) return rc;
+      split_done = true;
+    } else if (rc != MI_EINVAL) {
+      return rc;
+    }
+  }
+  if (!split_done) {
+    rc = launch_gemm_bf16(two, 1, e2, st, "banknce dT = G Y | dY = G^T T");
+    if (rc) return rc;
+  }
+  if (grad_bank_y) {
+    // the bank reports' rows of G^T: dY_bank[mm, c] = sum_i G[i, b + mm] T[i, c]
+    EpiStoreMulti e{};
+    e.out[0] = EpiOut{grad_bank_y, dy, 0, nullptr, 0, nullptr, 0};
+    rc = launch_gemm_bf16(one_problem(p.gtb + b * x3 * b, x3 * b, p.ttb, x3 * b, m, dy, x3 * b), 1, e, st,
+                          "banknce dY_bank = G^T T");
+    if (rc) return rc;
+  }
+  const bool need_du = has_w || grad_bank_t != nullptr;
+  if (n.sym) {
+    // problem 0: dU[mm, c] = sum_j G_left[mm, j] Y[j, c] (K = b); problem 1: dY_left[j, c] = sum_mm G_left[mm, j] U[mm, c]
+    const EpiOut du_out = has_w ? EpiOut{nullptr, 0, 0, n.dub, dy, n.dutb, m, nullptr, ra, rb}
+                                : EpiOut{grad_bank_t, dy, 0, nullptr, 0, nullptr, 0};
+    const EpiOut dyl_out = EpiOut{n.dy_slab + b * dy, dy, 0, nullptr, 0, nullptr, 0};
+    EpiStoreMulti e{};
+    if (need_du) {
+      GemmBf16Args l{};
+      l.p[0] = GemmBf16Problem{n.glb, x3 * b, n.ytb0, x3 * b, m, dy, x3 * b};
+      l.p[1] = GemmBf16Problem{n.gltb, x3 * m, n.utb, x3 * m, b, dy, x3 * m};
+      l.n_problems = 2;
+      l.k_chunk = x3 * (b > m ? b : m);
+      e.out[0] = du_out;
+      e.out[1] = dyl_out;
+      rc = launch_gemm_bf16(l, 1, e, st, "banknce dU = G_left Y | dY_left = G_left^T U");
+    } else {
+      e.out[0] = dyl_out;
+      rc = launch_gemm_bf16(one_problem(n.gltb, x3 * m, n.utb, x3 * m, b, dy, x3 * m), 1, e, st,
+                            "banknce dY_left = G_left^T U");
+    }
+    if (rc) return rc;
+    rc = launch_slab_reduce_ld(n.dy_slab, 2, b, dy, grad_y, dy, st, "banknce dY = top + left");
+    if (rc) return rc;
+  }
+  if (!has_w) return MI_OK;
+  // dW = X^T dT | dX = dT W^T; symmetric: the batch's dW lands in slab 0 of the bank's slabs, which are reduced in order
+  rc = launch_dw_dx(DwDxPair{p.xtb, p.dttb, p.dtb, p.wb, b, dx, dy, x3, p.dw_slab, p.dw_splits, p.dw_kchunk}, grad_x,
+                    n.sym ? n.dwb_slab : grad_w, st,
+                    {"banknce dW = X^T dT | dX = dT W^T", "banknce dW = X^T dT", "banknce dX = dT W^T"});
+  if (rc || !n.sym) return rc;
+  EpiStoreMulti e{};
+  e.out[0] = EpiOut{n.dwb_slab + dx * dy, dy, dx * dy, nullptr, 0, nullptr, 0};
+  rc = launch_gemm_bf16(one_problem(n.bxtb, x3 * m, n.dutb, x3 * m, dx, dy, x3 * m, x3 * n.dwb_kchunk), n.dwb_splits, e, st,
+                        "banknce dW_bank = bank_x^T dU");
+  if (rc) return rc;
+  return launch_slab_reduce_ld(n.dwb_slab, 1 + n.dwb_splits, dx, dy, grad_w, dy, st, "banknce dW = batch + bank");
+}
+
+// The whole step.  w == nullptr: S = X Y^T (d_img == d_txt); then T is X, U is bank_x, dT is grad_x.
+static int banknce_chain(const float* x, const float* y, const float* w, const int64_t* sid, const float* bank_x,
+                         const float* bank_y, const int64_t* bank_sid, int64_t b, int64_t m, int64_t dx, int64_t dy,
+                         int mode, int precision, const float* grad_out, float* loss_out, float* lse_rows, float* lse_cols,
+                         float* grad_x, float* grad_y, float* grad_w, float* grad_bank_t, float* grad_bank_y, bool any_grad,
+                         const BankNcePlan& n, hipStream_t st) {
+  const BilinearPlan& p = n.p;
+  const BankNceRecords& q = n.q;
+  const int64_t nn = b + m;
+  const bool sym = n.sym;
+  const BankStatsOut so_top = banknce_stats_top(q, sid, bank_sid, b), so_left = banknce_stats_left(q, sid, bank_sid, b);
+  const BankGradIn gi_top = banknce_grad_top(q, sid, bank_sid, b, grad_out, mode);
+  const BankGradIn gi_left = banknce_grad_left(q, sid, bank_sid, b, grad_out);
+  int rc = MI_OK;
+  if (n.c16) {
+    const int x3 = p.x3;
+    const int ra = x3 == 3 ? 1 : 0, rb = x3 == 3 ? 2 : 0;
+    const int64_t kk = x3 * dy;
+    BankCvtJobs jobs{};
+    if (w) {
+      jobs.j[0] = BankCvtJob{x, b, nullptr, 0, dx, p.xb, p.xtb, ra, ra, nullptr};
+      jobs.j[2] = BankCvtJob{w, dx, nullptr, 0, dy, p.wb, p.wtb, rb, rb, nullptr};
+      if (sym) jobs.j[3] = BankCvtJob{bank_x, m, nullptr, 0, dx, n.bxb, n.bxtb, ra, ra, nullptr};
+    } else {
+      jobs.j[0] = BankCvtJob{x, b, nullptr, 0, dx, p.tb, p.ttb, ra, rb, nullptr};
+      if (sym) jobs.j[3] = BankCvtJob{bank_x, m, nullptr, 0, dx, n.ub, n.utb, ra, rb, nullptr};
+    }
+    jobs.j[1] = BankCvtJob{y, b, bank_y, m, dy, p.yb, p.ytb, rb, rb, nullptr};
+    if (sym && any_grad) jobs.j[4] = BankCvtJob{y, b, nullptr, 0, dy, nullptr, n.ytb0, 0, rb, nullptr};
+    rc = launch_bank_cvt(jobs, st, "banknce prep batch + bank");
+    if (rc) return rc;
+    if (w) {
+      // T[i, c] = sum_a X[i, a] W[a, c]: A = Xb [b][dx], B = W^T [dy][dx]; U likewise on the bank's images
+      EpiStoreMulti e{};
+      e.out[0] = EpiOut{nullptr, 0, 0, p.tb, dy, p.ttb, b, nullptr, ra, rb};
+      rc = launch_gemm_bf16(one_problem(p.xb, x3 * dx, p.wtb, x3 * dx, b, dy, x3 * dx), 1, e, st, "banknce T = X W");
+      if (rc) return rc;
+      if (sym) {
+        e.out[0] = EpiOut{nullptr, 0, 0, n.ub, dy, n.utb, m, nullptr, ra, rb};
+        rc = launch_gemm_bf16(one_problem(n.bxb, x3 * dx, p.wtb, x3 * dx, m, dy, x3 * dx), 1, e, st, "banknce U = bank_x W");
+        if (rc) return rc;
+      }
+    }
+    rc = launch_gemm_bf16(one_problem(p.tb, kk, p.yb, kk, b, nn, kk), 1, EpiBankStats<true>{so_top}, st,
+                          "banknce score + records (top)");
+    if (rc) return rc;
+    if (sym) {
+      rc = launch_gemm_bf16(one_problem(n.ub, kk, p.yb, kk, m, b, kk), 1, EpiBankStats<true>{so_left}, st,
+                            "banknce score + records (left)");
+      if (rc) return rc;
+    }
+    rc = banknce_finish(q, b, mode, loss_out, lse_rows, lse_cols, st);
+    if (rc || !any_grad) return rc;
+    rc = launch_gemm_bf16(one_problem(p.tb, kk, p.yb, kk, b, nn, kk), 1,
+                          EpiBankGrad2{gi_top, p.gb, p.gtb, grad_bank_y ? nn : b, x3 == 3 ? 1 : 0}, st, "banknce G (top)");
+    if (rc) return rc;
+    if (sym) {
+      rc = launch_gemm_bf16(one_problem(n.ub, kk, p.yb, kk, m, b, kk), 1,
+                            EpiBankGrad2{gi_left, n.glb, n.gltb, b, x3 == 3 ? 1 : 0}, st, "banknce G (left)");
+      if (rc) return rc;
+    }
+    return banknce_bwd16(w != nullptr, b, m, dx, dy, grad_x, grad_y, grad_w, grad_bank_t, grad_bank_y, n, st);
+  }
+  return with_operand_type(precision == MI_PREC_BF16, [&](auto* op) {
+    using OpT = OperandOf<decltype(op)>;  // G is stored in the operand type
+    BankCvtJobs jobs{};
+    jobs.j[0] = BankCvtJob{y, b, bank_y, m, dy, nullptr, nullptr, 0, 0, n.yall};
+    int rc = launch_bank_cvt(jobs, st, "banknce gather Y (generic)");
+    if (rc) return rc;
+    const float* t = x;
+    const float* u = bank_x;
+    if (w) {
+      rc = generic_gemm_store<OpT>(make_operand(x, dx, 1), make_operand(w, 1, dy), b, dy, dx, p.t, dy, p, st,
+                                   "banknce T = X W (generic)");
+      if (rc) return rc;
+      t = p.t;
+      if (sym) {
+        rc = generic_gemm_store<OpT>(make_operand(bank_x, dx, 1), make_operand(w, 1, dy), m, dy, dx, n.u, dy, p, st,
+                                     "banknce U = bank_x W (generic)");
+        if (rc) return rc;
+        u = n.u;
+      }
+    }
+    const auto top_a = make_operand(t, dy, 1), all_y = make_operand((const float*)n.yall, dy, 1);
+    rc = launch_gemm<OpT>(top_a, all_y, b, nn, dy, EpiBankStats<false>{so_top}, st, "banknce score + records (top, generic)");
+    if (rc) return rc;
+    if (sym) {
+      rc = launch_gemm<OpT>(make_operand(u, dy, 1), all_y, m, b, dy, EpiBankStats<false>{so_left}, st,
+                            "banknce score + records (left, generic)");
+      if (rc) return rc;
+    }
+    rc = banknce_finish(q, b, mode, loss_out, lse_rows, lse_cols, st);
+    if (rc || !any_grad) return rc;
+    OpT* g = (OpT*)p.g;
+    OpT* gl = (OpT*)n.gl;
+    rc = launch_gemm<OpT>(top_a, all_y, b, nn, dy, EpiBankGrad<OpT>{gi_top, g}, st, "banknce G (top, generic)");
+    if (rc) return rc;
+    if (sym) {
+      rc = launch_gemm<OpT>(make_operand(u, dy, 1), all_y, m, b, dy, EpiBankGrad<OpT>{gi_left, gl}, st,
+                            "banknce G (left, generic)");
+      if (rc) return rc;
+    }
+    // dT = G Y_all; dY = G^T T over the batch's reports [+ G_left^T U, accumulated]; dU = G_left Y
+    float* dt = w ? p.dt : grad_x;
+    rc = generic_gemm_store<OpT>(make_operand((const OpT*)g, nn, 1), make_operand((const float*)n.yall, 1, dy), b, dy, nn, dt,
+                                 dy, p, st, "banknce dT = G Y (generic)");
+    if (rc) return rc;
+    rc = generic_gemm_store<OpT>(make_operand((const OpT*)g, 1, nn), make_operand(t, 1, dy), b, dy, b, grad_y, dy, p, st,
+                                 "banknce dY = G^T T (generic)");
+    if (rc) return rc;
+    if (grad_bank_y) {
+      rc = generic_gemm_store<OpT>(make_operand((const OpT*)g + b, 1, nn), make_operand(t, 1, dy), m, dy, b, grad_bank_y, dy, p,
+                                   st, "banknce dY_bank = G^T T (generic)");
+      if (rc) return rc;
+    }
+    float* du = w ? n.du : grad_bank_t;
+    if (sym) {
+      rc = launch_gemm<OpT>(make_operand((const OpT*)gl, 1, b), make_operand(u, 1, dy), b, dy, m,
+                            EpiStore{grad_y, dy, nullptr, 1.0f, 1}, st, "banknce dY += G_left^T U (generic)");
+      if (rc) return rc;
+      if (du) {
+        rc = generic_gemm_store<OpT>(make_operand((const OpT*)gl, b, 1), make_operand((const float*)n.yall, 1, dy), m, dy, b,
+                                     du, dy, p, st, "banknce dU = G_left Y (generic)");
+        if (rc) return rc;
+      }
+    }
+    if (!w) return MI_OK;
+    rc = generic_gemm_store<OpT>(make_operand(x, 1, dx), make_operand((const float*)p.dt, 1, dy), dx, dy, b, grad_w, dy, p, st,
+                                 "banknce dW = X^T dT (generic)");
+    if (rc) return rc;
+    if (sym) {
+      rc = launch_gemm<OpT>(make_operand(bank_x, 1, dx), make_operand((const float*)n.du, 1, dy), dx, dy, m,
+                            EpiStore{grad_w, dy, nullptr, 1.0f, 1}, st, "banknce dW += bank_x^T dU (generic)");
+      if (rc) return rc;
+    }
+    return generic_gemm_store<OpT>(make_operand((const float*)p.dt, dy, 1), make_operand(w, dy, 1), b, dx, dy, grad_x, dx, p,
+                                   st, "banknce dX = dT W^T (generic)");
+  });
+}
+
+// The separable entry point's workspace: the projections of batch and bank and their gradients, then the chain's plan
+struct BankNceSeparablePlan {
+  float *a, *c, *ab, *cb, *da, *dc, *dab, *dcb;
+  BankNcePlan n;
+  size_t bytes;
+};
+static BankNceSeparablePlan plan_banknce_separable(Workspace& ws, int64_t b, int64_t m, int64_t kp, int mode, int precision,
+                                                   bool grads) {
+  BankNceSeparablePlan s{};
+  const bool sym = mode == MI_NCE_SYMMETRIC;
+  s.a = ws.take<float>(b * kp);
+  s.c = ws.take<float>(b * kp);
+  s.ab = sym ? ws.take<float>(m * kp) : nullptr;
+  s.cb = ws.take<float>(m * kp);
+  if (grads) {
+    s.da = ws.take<float>(b * kp);
+    s.dc = ws.take<float>(b * kp);
+    s.dab = sym ? ws.take<float>(m * kp) : nullptr;
+    s.dcb = ws.take<float>(m * kp);
+  }
+  s.n = plan_banknce(ws, b, m, kp, kp, mode, precision, grads);
+  s.bytes = ws.off;
+  return s;
+}
+
 }  // namespace mi
 
 extern "C" {
@@ -2512,6 +2883,96 @@ int mi_matrix_hardnce_bwd(const float* scores, int64_t b, int mode, int k, const
   }
   MI_LAUNCH_CHECK("hardnce_matrix_grad_kernel");
   return MI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ memory-bank InfoNCE
+size_t mi_banknce_bilinear_workspace_bytes(int64_t b, int64_t m, int64_t d_img, int64_t d_txt, int mode, int precision,
+                                           int with_grads) {
+  if (b <= 0 || m <= 0 || d_img <= 0 || d_txt <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_banknce(ws, b, m, d_img, d_txt, mode, precision, with_grads != 0).bytes + 256;
+}
+
+int mi_banknce_bilinear_step(const float* x, const float* y, const float* w, const int64_t* sid, const float* bank_x,
+                             const float* bank_y, const int64_t* bank_sid, int64_t b, int64_t m, int64_t d_img,
+                             int64_t d_txt, int mode, int precision, const float* grad_out, float* loss_out,
+                             float* lse_rows, float* lse_cols, float* grad_x, float* grad_y, float* grad_w, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && sid && bank_y && bank_sid && loss_out && workspace, "mi_banknce_bilinear_step: null pointer");
+  int rc = banknce_check("mi_banknce_bilinear_step", b, m, d_img, d_txt, mode, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(bank_x || mode == MI_NCE_ROWWISE, "mi_banknce_bilinear_step: the symmetric mode needs bank_x");
+  MI_CHECK_ARG(w || d_img == d_txt, "mi_banknce_bilinear_step: w == NULL (S = X Y^T) needs d_img == d_txt");
+  const bool any_grad = grad_x || grad_y || grad_w;
+  MI_CHECK_ARG(!any_grad || (grad_x && grad_y && (w ? grad_w != nullptr : grad_w == nullptr)),
+               "mi_banknce_bilinear_step: pass grad_x, grad_y and (with w) grad_w, or none of them");
+  Workspace ws(workspace, workspace_bytes);
+  const BankNcePlan n = plan_banknce(ws, b, m, d_img, d_txt, mode, precision, any_grad);
+  rc = ws_fits(ws, "mi_banknce_bilinear_step");
+  if (rc) return rc;
+  return banknce_chain(x, y, w, sid, bank_x, bank_y, bank_sid, b, m, d_img, d_txt, mode, precision, grad_out, loss_out,
+                       lse_rows, lse_cols, grad_x, grad_y, grad_w, nullptr, nullptr, any_grad, n, (hipStream_t)stream);
+}
+
+size_t mi_banknce_separable_workspace_bytes(int64_t b, int64_t m, int64_t d_img, int64_t d_txt, int64_t d_proj, int mode,
+                                            int precision, int with_grads) {
+  if (b <= 0 || m <= 0 || d_img <= 0 || d_txt <= 0 || d_proj <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_banknce_separable(ws, b, m, d_proj, mode, precision, with_grads != 0).bytes + 256;
+}
+
+int mi_banknce_separable_step(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid,
+                              const float* bank_x, const float* bank_y, const int64_t* bank_sid, int64_t b, int64_t m,
+                              int64_t d_img, int64_t d_txt, int64_t d_proj, int mode, int precision, const float* grad_out,
+                              float* loss_out, float* lse_rows, float* lse_cols, float* grad_x, float* grad_y,
+                              float* grad_wg, float* grad_wh, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && wg && wh && sid && bank_y && bank_sid && loss_out && workspace,
+               "mi_banknce_separable_step: null pointer");
+  int rc = banknce_check("mi_banknce_separable_step", b, m, d_img, d_txt, mode, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(bank_x || mode == MI_NCE_ROWWISE, "mi_banknce_separable_step: the symmetric mode needs bank_x");
+  MI_CHECK_ARG(d_proj >= 1, "mi_banknce_separable_step: projection width must be >= 1");
+  const bool any_grad = grad_x || grad_y || grad_wg || grad_wh;
+  MI_CHECK_ARG(!any_grad || (grad_x && grad_y && grad_wg && grad_wh),
+               "mi_banknce_separable_step: pass all four gradients or none of them");
+  Workspace ws(workspace, workspace_bytes);
+  const BankNceSeparablePlan sp = plan_banknce_separable(ws, b, m, d_proj, mode, precision, any_grad);
+  rc = ws_fits(ws, "mi_banknce_separable_step");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t k = d_proj;
+  const bool bf = precision == MI_PREC_BF16, sym = mode == MI_NCE_SYMMETRIC;
+  // the projections of the batch, then the bank's (recomputed every call: they depend on Wg, Wh)
+  rc = separable_project(BankNceEst::kSep, bf, x, y, wg, wh, b, b, d_img, d_txt, k, sp.a, sp.c, st);
+  if (rc) return rc;
+  rc = with_operand_type(bf, [&](auto* op) {
+    using OpT = OperandOf<decltype(op)>;
+    if (sym) {
+      const int r = launch_gemm<OpT>(make_operand(bank_x, d_img, 1), make_operand(wg, 1, k), m, k, d_img,
+                                     EpiStore{sp.ab, k, nullptr, 1.0f, 0}, st, "banknce separable A_bank = bank_x Wg");
+      if (r) return r;
+    }
+    return launch_gemm<OpT>(make_operand(bank_y, d_txt, 1), make_operand(wh, 1, k), m, k, d_txt,
+                            EpiStore{sp.cb, k, nullptr, 1.0f, 0}, st, "banknce separable C_bank = bank_y Wh");
+  });
+  if (rc) return rc;
+  rc = banknce_chain(sp.a, sp.c, nullptr, sid, sp.ab, sp.cb, bank_sid, b, m, k, k, mode, precision, grad_out, loss_out,
+                     lse_rows, lse_cols, sp.da, sp.dc, nullptr, sp.dab, sp.dcb, any_grad, sp.n, st);
+  if (rc || !any_grad) return rc;
+  rc = separable_project_back(BankNceEst::kSep, bf, x, y, wg, wh, b, b, d_img, d_txt, k, sp.da, sp.dc, grad_x, grad_y,
+                              grad_wg, grad_wh, st);
+  if (rc) return rc;
+  // the bank rows' share of dWg, dWh, added behind the batch's by the store epilogue's accumulate slot
+  return with_operand_type(bf, [&](auto* op) {
+    using OpT = OperandOf<decltype(op)>;
+    if (sym) {
+      const int r = launch_gemm<OpT>(make_operand(bank_x, 1, d_img), make_operand((const float*)sp.dab, 1, k), d_img, k, m,
+                                     EpiStore{grad_wg, k, nullptr, 1.0f, 1}, st, "banknce separable dWg += bank_x^T dA_bank");
+      if (r) return r;
+    }
+    return launch_gemm<OpT>(make_operand(bank_y, 1, d_txt), make_operand((const float*)sp.dcb, 1, k), d_txt, k, m,
+                            EpiStore{grad_wh, k, nullptr, 1.0f, 1}, st, "banknce separable dWh += bank_y^T dC_bank");
+  });
 }
 
 }  // extern "C"

@@ -79,9 +79,14 @@ def train_mutual_information(args, device):
     # --hard_negatives K: the hard-negative form of the per-sample InfoNCE, validated with its estimator at construction
     hard_k = getattr(args, "hard_negatives", None)
     hard = {} if hard_k is None else dict(mi_estimator=getattr(args, "mi_estimator", None), hard_negatives=hard_k)
+    # --memory_bank K: the same losses against the batch and a queue of the last K samples' embeddings
+    bank_k = getattr(args, "memory_bank", None)
+    if bank_k is not None:
+        hard = dict(hard, mi_estimator=getattr(args, "mi_estimator", None), memory_bank=bank_k)
     if getattr(args, "synthetic", False):
         model_manager = MultiModalManager(d_img=args.embed_dim_img, d_txt=args.embed_dim_txt, critic=critic,
-                                          mi_estimator=getattr(args, "mi_estimator", None), hard_negatives=hard_k)
+                                          mi_estimator=getattr(args, "mi_estimator", None), hard_negatives=hard_k,
+                                          memory_bank=bank_k)
         source = synthetic_embedding_source(args, device)
     elif getattr(args, "synthetic_encoders", False):
         from mutual_info_img_txt.model import ResNet256_6_2_1, TextBert

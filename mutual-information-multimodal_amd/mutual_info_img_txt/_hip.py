@@ -198,6 +198,10 @@ SIGNATURES = {
     "mi_matrix_hardnce_workspace_bytes": (_SZ, [_I64, _I]),
     "mi_matrix_hardnce_fwd": (c_int, [_P, _P, _I64, _I, _I] + [_P] * 6 + [_SZ, _P]),
     "mi_matrix_hardnce_bwd": (c_int, [_P, _I64, _I, _I] + [_P] * 7),
+    "mi_banknce_bilinear_workspace_bytes": (_SZ, [_I64] * 4 + [_I, _I, _I]),
+    "mi_banknce_bilinear_step": (c_int, [_P] * 7 + [_I64] * 4 + [_I, _I] + [_P] * 8 + [_SZ, _P]),
+    "mi_banknce_separable_workspace_bytes": (_SZ, [_I64] * 5 + [_I, _I, _I]),
+    "mi_banknce_separable_step": (c_int, [_P] * 8 + [_I64] * 5 + [_I, _I] + [_P] * 9 + [_SZ, _P]),
 }
 MI_TOPK_MAX_K = 32  # include/mi_critic.h
 

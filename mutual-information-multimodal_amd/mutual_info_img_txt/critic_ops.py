@@ -1,5 +1,5 @@
 """The one binding of the critic entry points of the C ABI (mi_bilinear_*, mi_separable_*, mi_concat_mlp_*, mi_nce_*,
-mi_fdiv_*, mi_rank_*, mi_topk_*, mi_hardnce_*), shared by ``mi_critics`` (eager autograd), ``graphed`` (hipGraph step) and ``distributed`` (sharded step).
+mi_fdiv_*, mi_rank_*, mi_topk_*, mi_hardnce_*, mi_banknce_*), shared by ``mi_critics`` (eager autograd), ``graphed`` (hipGraph step) and ``distributed`` (sharded step).
 
 An ops object scores the row block ``x`` [b_rows, d_img] (starting at ``row_offset``) against all of ``y_all``
 [b, d_txt]; a whole batch is ``b_rows == b``, ``row_offset == 0``.  Each ``*_call`` method writes one entry point's
@@ -217,6 +217,21 @@ class _HipOps:
         self.hardnce_call(x, y, params, sid, mode, precision, k, loss, r, c, ir, ic, grads, ws)()
         return loss, r, c, ir, ic, grads
 
+    def banknce_step(self, x, y, params, sid, bank_x, bank_y, bank_sid, mode, precision, need_grad):
+        """The per-sample InfoNCE of the batch against the batch and a memory bank in one call of
+        ``mi_banknce_<critic>_step`` (bilinear and separable critics), with the gradients of 1 * loss when ``need_grad``:
+        (loss [1], lse_rows [B], lse_cols [B] or None, [grad_x, grad_y, grad_params...] or []).  ``bank_x`` may be None in
+        the row-wise mode; the bank gets no gradient."""
+        b, m, dev = x.shape[0], bank_y.shape[0], x.device
+        ws = _hip.workspace(self.banknce_workspace_bytes(b, m, x.shape[1], y.shape[1], params, mode, precision, need_grad),
+                            dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        r = torch.empty(b, dtype=torch.float32, device=dev)
+        c = torch.empty_like(r) if mode == _hip.MI_NCE_SYMMETRIC else None
+        grads = [torch.empty_like(t) for t in (x, y, *params)] if need_grad else []
+        self.banknce_call(x, y, params, sid, bank_x, bank_y, bank_sid, mode, precision, loss, r, c, grads, ws)()
+        return loss, r, c, grads
+
     # ---------------------------------------------- per-sample InfoNCE on a row block (distributed.GlobalBatchNceFn)
     def nce_forward(self, x, y_all, params, sid_rows, sid_all, row_offset, mode, precision, need_grad=True):
         """The row block's part (``mi_nce_part_floats`` floats, gathered in rank order by the caller) and its row LSEs:
@@ -336,6 +351,19 @@ class HipBilinearOps(_HipOps):
         return _call("mi_hardnce_bilinear_step", x.device, x.data_ptr(), y.data_ptr(), _p(w), sid.data_ptr(), x.shape[0],
                      x.shape[1], y.shape[1], mode, precision, k, None, loss.data_ptr(), _p(r), _p(c), _p(idx_rows),
                      _p(idx_cols), _p(gx), _p(gy), _p(gw), ws.data_ptr(), ws.numel())
+
+    @staticmethod
+    def banknce_workspace_bytes(b, m, dx, dy, params, mode, precision, need_grad):
+        return _hip.load().mi_banknce_bilinear_workspace_bytes(b, m, dx, dy, mode, precision, int(bool(need_grad)))
+
+    def banknce_call(self, x, y, params, sid, bank_x, bank_y, bank_sid, mode, precision, loss, r, c, grads, ws):
+        """Memory-bank InfoNCE step (mi_banknce_bilinear_step); ``c`` None in the row-wise mode, ``grads`` [] for the
+        forward launches alone."""
+        w = params[0] if params else None
+        gx, gy, gw = (grads + [None] * 3)[:3]
+        return _call("mi_banknce_bilinear_step", x.device, x.data_ptr(), y.data_ptr(), _p(w), sid.data_ptr(), _p(bank_x),
+                     bank_y.data_ptr(), bank_sid.data_ptr(), x.shape[0], bank_y.shape[0], x.shape[1], y.shape[1], mode,
+                     precision, None, loss.data_ptr(), _p(r), _p(c), _p(gx), _p(gy), _p(gw), ws.data_ptr(), ws.numel())
 
     @staticmethod
     def nce_shard_workspace_bytes(br, b, dx, dy, params, precision):
@@ -528,6 +556,19 @@ class HipSeparableOps(_HipOps):
                      sid.data_ptr(), x.shape[0], x.shape[1], y.shape[1], wg.shape[1], mode, precision, k, None,
                      loss.data_ptr(), _p(r), _p(c), _p(idx_rows), _p(idx_cols), *[_p(g) for g in grads or [None] * 4],
                      ws.data_ptr(), ws.numel())
+
+    @staticmethod
+    def banknce_workspace_bytes(b, m, dx, dy, params, mode, precision, need_grad):
+        return _hip.load().mi_banknce_separable_workspace_bytes(b, m, dx, dy, params[0].shape[1], mode, precision,
+                                                                int(bool(need_grad)))
+
+    def banknce_call(self, x, y, params, sid, bank_x, bank_y, bank_sid, mode, precision, loss, r, c, grads, ws):
+        """Memory-bank InfoNCE step (mi_banknce_separable_step), as ``HipBilinearOps.banknce_call``."""
+        wg, wh = params
+        return _call("mi_banknce_separable_step", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
+                     sid.data_ptr(), _p(bank_x), bank_y.data_ptr(), bank_sid.data_ptr(), x.shape[0], bank_y.shape[0],
+                     x.shape[1], y.shape[1], wg.shape[1], mode, precision, None, loss.data_ptr(), _p(r), _p(c),
+                     *[_p(g) for g in grads or [None] * 4], ws.data_ptr(), ws.numel())
 
     @staticmethod
     def nce_shard_workspace_bytes(br, b, dx, dy, params, precision):

@@ -102,7 +102,8 @@ class MultiModalManager:
     def __init__(self, bert_pretrained_dir=None, bert_config_name=None, output_channels=None, image_model_name=None, *,
                  d_img: int = 768, d_txt: int = 768, critic: str = "concat_mlp", hidden_dims=(1024, 512),
                  d_proj: int = 256, image_model=None, text_model=None, bert_config=None, embed_proj_dim=None,
-                 autocast_dtype=None, mi_estimator: Optional[str] = None, hard_negatives: Optional[int] = None):
+                 autocast_dtype=None, mi_estimator: Optional[str] = None, hard_negatives: Optional[int] = None,
+                 memory_bank: Optional[int] = None):
         self.bert_pretrained_dir = bert_pretrained_dir
         self.bert_config_name = bert_config_name
         self.output_channels = output_channels
@@ -143,6 +144,20 @@ class MultiModalManager:
                                  f"{sorted(_hip.NCE_ESTIMATORS)} (got {mi_estimator!r})")
             self.hard_negatives = check_k(hard_negatives)
             self.hard_negatives_estimator = mi_estimator
+        # memory-bank InfoNCE (memory_bank.py): the row-wise / symmetric loss against the batch and a queue of the last
+        # `memory_bank` samples' detached embeddings (ceiling log(B + M); stale entries make it a training loss)
+        self.memory_bank = None
+        self.bank = None  # the EmbeddingQueue, built on first use on the embeddings' device; never checkpointed
+        if memory_bank is not None:
+            from .memory_bank import check_capacity
+            if mi_estimator not in _hip.NCE_ESTIMATORS:
+                raise ValueError(f"memory_bank is a parameter of the per-sample InfoNCE: it needs mi_estimator in "
+                                 f"{sorted(_hip.NCE_ESTIMATORS)} (got {mi_estimator!r})")
+            if hard_negatives is not None:
+                raise ValueError("memory_bank and hard_negatives cannot be combined (no hard-negative selection over "
+                                 "batch + bank)")
+            self.memory_bank = check_capacity(memory_bank)
+            self.memory_bank_estimator = mi_estimator
         self.d_img, self.d_txt = d_img, d_txt
         self.training_loss = []
         self._graphed = None
@@ -167,8 +182,19 @@ class MultiModalManager:
         this batch shape; the training loop's setting) for the estimators that GraphedMiStep captures ("dv", "infonce");
         the others ("infonce_rowwise" / "infonce_symmetric", "jsd" / "nwj") always run eagerly through
         ``fused_mi_bound``, and so does the separable critic.  A manager built with ``hard_negatives=k`` runs
-        ``hard_negatives.hard_negative_infonce`` here, eagerly (a training loss, not an MI bound)."""
+        ``hard_negatives.hard_negative_infonce`` here, eagerly (a training loss, not an MI bound).  A manager built with
+        ``memory_bank=K`` runs ``memory_bank.memory_bank_infonce`` against its queue ``self.bank`` here, eagerly; the
+        training loop pushes each batch's detached embeddings after the optimizer steps.  The queue is not checkpointed:
+        after a resume it is empty and refills."""
         est = mi_critics.check_estimator(mi_estimator, self.critic_kind)
+        if self.memory_bank is not None:
+            if mi_estimator != self.memory_bank_estimator:
+                raise ValueError(f"this manager trains the memory-bank form of {self.memory_bank_estimator!r}; "
+                                 f"mi_step got mi_estimator={mi_estimator!r}")
+            from .memory_bank import memory_bank_infonce
+            return memory_bank_infonce(embedding_img, embedding_txt, study_id, self.mi_discriminator,
+                                       self._bank_for(embedding_img, embedding_txt),
+                                       symmetric=mi_estimator == "infonce_symmetric", precision=precision)
         if self.hard_negatives is not None:
             if mi_estimator != self.hard_negatives_estimator:
                 raise ValueError(f"this manager trains the hard-negative form of {self.hard_negatives_estimator!r}; "
@@ -196,6 +222,14 @@ class MultiModalManager:
         mi_input = self.create_mi_pairs(embedding_img, embedding_txt, study_id, embedding_img.device)
         mi_output = self.mi_discriminator(mi_input)
         return getattr(mi_critics, est.logits)(mi_output, len(study_id), embedding_img.device)
+
+    def _bank_for(self, embedding_img, embedding_txt):
+        """The manager's queue, built on first use for these widths on the embeddings' device."""
+        if self.bank is None:
+            from .memory_bank import EmbeddingQueue
+            self.bank = EmbeddingQueue(self.memory_bank, embedding_img.shape[1], embedding_txt.shape[1],
+                                       embedding_img.device)
+        return self.bank
 
     def retrieval_eval(self, embedding_img, embedding_txt, study_id, ks=(1, 5, 10), precision: str = "f32"):
         """Cross-modal retrieval of the batch under the manager's critic (``retrieval.retrieval_ranks``):
@@ -349,6 +383,8 @@ class MultiModalManager:
                 if txt_optimizer is not None:
                     txt_optimizer.step()
                     scheduler.step()
+                if self.memory_bank is not None:  # behind the optimizer steps: the next batch scores against this one
+                    self._bank_for(embedding_img, embedding_txt).push(embedding_img, embedding_txt, study_id)
                 epoch_loss += loss.detach().sum()  # device-side accumulation; one sync per epoch
             epoch_loss = float(epoch_loss.item())
             training_loss.append(epoch_loss)

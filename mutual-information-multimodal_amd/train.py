@@ -32,6 +32,9 @@ def construct_training_parameters(argv=None):
     p.add_argument('--seed', default=0, type=int)
     # hard-negative InfoNCE: train the row-wise / symmetric loss on each query's top-K negatives (a loss, not an MI bound)
     p.add_argument('--hard_negatives', default=None, type=int)
+    # memory-bank InfoNCE: the row-wise / symmetric loss against the batch and a queue of the last K samples' embeddings
+    # (ceiling log(batch + K); not checkpointed: the queue refills after a resume)
+    p.add_argument('--memory_bank', default=None, type=int)
     return p.parse_args(argv)
 
 
@@ -45,6 +48,15 @@ def check_training_parameters(args):
             raise ValueError(f"--hard_negatives needs --mi_estimator in {sorted(NCE_ESTIMATORS)} "
                              f"(got {args.mi_estimator!r})")
         check_k(args.hard_negatives)
+    if getattr(args, "memory_bank", None) is not None:
+        from mutual_info_img_txt._hip import NCE_ESTIMATORS
+        from mutual_info_img_txt.memory_bank import check_capacity
+        if args.mi_estimator not in NCE_ESTIMATORS:
+            raise ValueError(f"--memory_bank needs --mi_estimator in {sorted(NCE_ESTIMATORS)} "
+                             f"(got {args.mi_estimator!r})")
+        if getattr(args, "hard_negatives", None) is not None:
+            raise ValueError("--memory_bank and --hard_negatives cannot be combined")
+        check_capacity(args.memory_bank)
     return args
 
 
