@@ -24,6 +24,8 @@
  *                            critic under the same masking rule; an evaluation, not an estimator
  *   mi_topk_*             <- an extension: the k best reports of an image and the k best images of a report over a
  *                            gallery (n_img != n_txt allowed), optionally without equal-id candidates; an evaluation too
+ *   mi_posnce_*, mi_matrix_posnce_* <- an extension: the per-sample InfoNCE with every same-study pair as a positive
+ *                            (the dataset pairs each image with its study's report, so such pairs are true matches)
  *
  * Conventions
  *   - every pointer is a DEVICE pointer unless the name ends in _host; all tensors are dense row-major
@@ -560,6 +562,52 @@ int mi_banknce_separable_step(const float* x, const float* y, const float* wg, c
                               int64_t d_img, int64_t d_txt, int64_t d_proj, int mode, int precision, const float* grad_out,
                               float* loss_out, float* lse_rows, float* lse_cols, float* grad_x, float* grad_y,
                               float* grad_wg, float* grad_wh, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- study-positive InfoNCE ---------------------------------------------------------------- */
+/* The per-sample InfoNCE with every same-study pair as a positive (multi-positive InfoNCE: SupCon's L_out, UniCL).
+ * Batch x [b, d_img], y [b, d_txt], id codes sid [b], S[i, j] = critic(img_i, txt_j):
+ *   P_i = {j : sid_j == sid_i} (contains i),  n_i = |P_i| >= 1
+ *   r_i = log sum_{j < b} exp S[i, j],  c_j = log sum_{i < b} exp S[i, j]                     (nothing is masked)
+ *   row term t_i = r_i - (1/n_i) sum_{p in P_i} S[i, p],  column term t'_j = c_j - (1/n_j) sum_{p in P_j} S[p, j]
+ *   MI_NCE_ROWWISE:   L = (1/b) sum_i t_i
+ *   MI_NCE_SYMMETRIC: L = 1/2 (1/b) sum_i t_i + 1/2 (1/b) sum_j t'_j
+ *   dL/dS[i, j] = w_r exp(S[i,j] - r_i) + w_c exp(S[i,j] - c_j) - (w_r + w_c) 1[sid_i == sid_j] / n_i,
+ *   (w_r, w_c) = (1/b, 0) or (1/(2b), 1/(2b)); each row's share of dL/dS sums to zero.
+ * With unique ids this IS the loss of mi_nce_*: same r, c, loss and gradients.  With duplicates it differs from it in two
+ * ways: same-study pairs enter the denominators, and they share the positive weight.  With all ids equal t_i = r_i -
+ * mean_j S[i, j] >= log b: the loss is not zero.  b == 1 gives loss exactly 0.0 and exact-zero gradients.
+ * A TRAINING LOSS, NOT AN MI BOUND: log b - L bounds nothing once some n_i > 1; `mode` codes are those of mi_nce_*, not
+ * estimator codes.  Only this averaged-outside form exists (in the image -> report direction the positives of a row are
+ * the same report repeated, so the log-of-sum-over-positives form gains nothing).  Whole batch only: no row-block form.
+ * Outputs: loss_out [1]; optional lse_rows [b], lse_cols [b] (r and c, both written in either mode), n_pos_out int32 [b]
+ * (n_i).  grad_out may be NULL (1).  Gradient pointers all NULL: the forward launches only, and the workspace query with
+ * with_grads == 0 (no G) suffices; otherwise every gradient is written and the workspace is that of with_grads != 0.
+ * w == NULL is S = X Y^T (d_img == d_txt, no grad_w).  precision: MI_PREC_BF16 / BF16X3 run the 16-bit GEMM chain where b
+ * and the widths are multiples of 8, every other shape and MI_PREC_F32 the generic kernels; MI_PREC_FP8 / F16 / F16X3:
+ * MI_EINVAL.  MI_EINVAL also for null required pointers, sizes < 1, b >= 2^31, an unknown mode, a partial gradient set;
+ * MI_EWORKSPACE for a short workspace.  Deterministic: records merged in tile order, no float atomics. */
+size_t mi_posnce_bilinear_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int precision, int with_grads);
+int mi_posnce_bilinear_step(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t d_img,
+                            int64_t d_txt, int mode, int precision, const float* grad_out, float* loss_out,
+                            float* lse_rows, float* lse_cols, int32_t* n_pos_out, float* grad_x, float* grad_y,
+                            float* grad_w, void* workspace, size_t workspace_bytes, void* stream);
+/* S = (X Wg)(Y Wh)^T: projects, runs the w == NULL form on the projections, projects the gradients back */
+size_t mi_posnce_separable_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int precision,
+                                           int with_grads);
+int mi_posnce_separable_step(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid,
+                             int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int mode, int precision,
+                             const float* grad_out, float* loss_out, float* lse_rows, float* lse_cols, int32_t* n_pos_out,
+                             float* grad_x, float* grad_y, float* grad_wg, float* grad_wh, void* workspace,
+                             size_t workspace_bytes, void* stream);
+/* on a caller's fp32 [b, b] score matrix (any critic, exact expf): the forward writes loss_out[0] and the optional
+ * lse_rows / lse_cols / n_pos; the backward reads lse_rows, n_pos (and lse_cols in the symmetric mode) and writes the
+ * dense grad_scores [b, b] = grad_out[0] * dloss/dS */
+size_t mi_matrix_posnce_workspace_bytes(int64_t b);
+int mi_matrix_posnce_fwd(const float* scores, const int64_t* sid, int64_t b, int mode, float* loss_out, float* lse_rows,
+                         float* lse_cols, int32_t* n_pos, void* workspace, size_t workspace_bytes, void* stream);
+int mi_matrix_posnce_bwd(const float* scores, const int64_t* sid, int64_t b, int mode, const float* lse_rows,
+                         const float* lse_cols, const int32_t* n_pos, const float* grad_out, float* grad_scores,
+                         void* stream);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,7 @@
 #include "mi_topk.h"
 #include "mi_hardnce.h"
 #include "mi_banknce.h"
+#include "mi_posnce.h"
 
 namespace mi {
 
@@ -1953,6 +1954,72 @@ static int hardnce_chain(const float* x, const float* y, const float* w, const i
                                  grad_x, grad_y, grad_w, n.p, st);
 }
 
+// ------------------------------------------------------------------------------------------------ study-positive InfoNCE
+// (mi_posnce.h)  The chain of the per-sample InfoNCE with the epilogues that take every same-study
+// pair as a positive; whole batch only:
+//   prep + T = X W -> score GEMM + records -> posnce_merge_kernel -> nce_loss_kernel
+//   [grads] G GEMM -> dT = G Y | dY = G^T T -> dW = X^T dT | dX = dT W^T
+struct PosNceEst {
+  using StatsOut = PosNceStatsOut;
+  using GradIn = PosNceGradIn;
+  using Stats = EpiPosNceStats<false>;
+  using Stats16 = EpiPosNceStats<true>;
+  template <typename TG>
+  using Grad = EpiPosNceGrad<TG>;
+  using Grad16 = EpiPosNceGrad2;
+  static int check_mode(const char* fn, int mode) { return NceEst::check_mode(fn, mode); }
+  static constexpr const char* kName = "the study-positive InfoNCE";
+  static constexpr const char* kT = "posnce T = X W (generic)";
+  static constexpr const char* kScores = "posnce score + records (generic)";
+  static constexpr const char* kScores16 = "posnce score + records";
+  static constexpr const char* kG = "posnce G (generic)";
+  static constexpr const char* kG16 = "posnce G";
+  static constexpr SepLabels kSep = {"posnce separable A = X Wg",     "posnce separable C = Y Wh",
+                                     "posnce separable dX = dA Wg^T", "posnce separable dWg = X^T dA",
+                                     "posnce separable dY = dC Wh^T", "posnce separable dWh = Y^T dC"};
+};
+
+static int posnce_check(const char* fn, int64_t b, int64_t dx, int64_t dy, int mode, int precision) {
+  const int rc = chain_check<PosNceEst>(fn, b, b, 0, dx, dy, mode, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(b < ((int64_t)1 << 31), "%s: b must be below 2^31", fn);
+  return MI_OK;
+}
+
+// grads: the nce step's buffers (with G and G^T); forward only: the forward half's buffers alone, no G
+struct PosNceBilinearPlan {
+  BilinearPlan p;
+  PosNcePlan q;
+  size_t bytes;
+};
+static PosNceBilinearPlan plan_posnce_bilinear(Workspace& ws, int64_t b, int64_t dx, int64_t dy, int precision,
+                                               bool grads) {
+  PosNceBilinearPlan n{};
+  n.p = grads ? plan_bilinear(ws, b, b, dx, dy, precision, true, true) : plan_rank_bilinear(ws, b, dx, dy, precision).p;
+  n.q = plan_posnce(ws, b);
+  n.bytes = ws.off;
+  return n;
+}
+static SeparableChainPlan<PosNceBilinearPlan> plan_posnce_separable(Workspace& ws, int64_t b, int64_t k, int precision,
+                                                                    bool grads) {
+  return plan_separable_chain(ws, b, b, k, [&] { return plan_posnce_bilinear(ws, b, k, k, precision, grads); });
+}
+
+// The whole step on (x, y, w); w == nullptr: S = X Y^T, dT is grad_x and there is no grad_w
+static int posnce_chain(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t dx,
+                        int64_t dy, int mode, int precision, const float* grad_out, float* loss_out, float* lse_rows,
+                        float* lse_cols, int32_t* n_pos_out, float* grad_x, float* grad_y, float* grad_w, bool any_grad,
+                        const PosNceBilinearPlan& n, hipStream_t st) {
+  int rc = chain_scores<PosNceEst>(x, y, w, nullptr, nullptr, b, b, 0, dx, dy, precision, posnce_stats_out(n.q, sid), n.p,
+                                   st);
+  if (rc) return rc;
+  rc = posnce_finish(n.q, b, mode, loss_out, lse_rows, lse_cols, n_pos_out, st);
+  if (rc || !any_grad) return rc;
+  return chain_grads<PosNceEst>(x, y, w, b, b, dx, dy, precision,
+                                posnce_grad_in(sid, n.q.r, n.q.c, n.q.inv_n, nullptr, grad_out, b, mode), grad_x, grad_y,
+                                grad_w, n.p, st);
+}
+
 // ------------------------------------------------------------------------------------------------ memory-bank InfoNCE
 // (mi_banknce.h)  The per-sample InfoNCE of the batch against the batch and a bank of past
 // embeddings: an L-shaped score matrix, a top block [b] x [b + m] (a row block of the chain: br = b, row_offset = 0, the
@@ -2882,6 +2949,111 @@ int mi_matrix_hardnce_bwd(const float* scores, int64_t b, int mode, int k, const
                        hardnce_grad_in(idx_rows, idx_cols, k, lse_rows, lse_cols, grad_out, b, mode), grad_scores);
   }
   MI_LAUNCH_CHECK("hardnce_matrix_grad_kernel");
+  return MI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ study-positive InfoNCE
+size_t mi_posnce_bilinear_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int precision, int with_grads) {
+  if (b <= 0 || d_img <= 0 || d_txt <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_posnce_bilinear(ws, b, d_img, d_txt, precision, with_grads != 0).bytes + 256;
+}
+
+int mi_posnce_bilinear_step(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t d_img,
+                            int64_t d_txt, int mode, int precision, const float* grad_out, float* loss_out,
+                            float* lse_rows, float* lse_cols, int32_t* n_pos_out, float* grad_x, float* grad_y,
+                            float* grad_w, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && sid && loss_out && workspace, "mi_posnce_bilinear_step: null pointer");
+  int rc = posnce_check("mi_posnce_bilinear_step", b, d_img, d_txt, mode, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(w || d_img == d_txt, "mi_posnce_bilinear_step: w == NULL (S = X Y^T) needs d_img == d_txt");
+  const bool any_grad = grad_x || grad_y || grad_w;
+  MI_CHECK_ARG(!any_grad || (grad_x && grad_y && (w ? grad_w != nullptr : grad_w == nullptr)),
+               "mi_posnce_bilinear_step: pass grad_x, grad_y and (with w) grad_w, or none of them");
+  Workspace ws(workspace, workspace_bytes);
+  const PosNceBilinearPlan n = plan_posnce_bilinear(ws, b, d_img, d_txt, precision, any_grad);
+  rc = ws_fits(ws, "mi_posnce_bilinear_step");
+  if (rc) return rc;
+  return posnce_chain(x, y, w, sid, b, d_img, d_txt, mode, precision, grad_out, loss_out, lse_rows, lse_cols, n_pos_out,
+                      grad_x, grad_y, grad_w, any_grad, n, (hipStream_t)stream);
+}
+
+size_t mi_posnce_separable_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int precision,
+                                           int with_grads) {
+  if (b <= 0 || d_img <= 0 || d_txt <= 0 || d_proj <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_posnce_separable(ws, b, d_proj, precision, with_grads != 0).bytes + 256;
+}
+
+int mi_posnce_separable_step(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid,
+                             int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int mode, int precision,
+                             const float* grad_out, float* loss_out, float* lse_rows, float* lse_cols, int32_t* n_pos_out,
+                             float* grad_x, float* grad_y, float* grad_wg, float* grad_wh, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && wg && wh && sid && loss_out && workspace, "mi_posnce_separable_step: null pointer");
+  int rc = posnce_check("mi_posnce_separable_step", b, d_img, d_txt, mode, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(d_proj >= 1, "mi_posnce_separable_step: projection width must be >= 1");
+  const bool any_grad = grad_x || grad_y || grad_wg || grad_wh;
+  MI_CHECK_ARG(!any_grad || (grad_x && grad_y && grad_wg && grad_wh),
+               "mi_posnce_separable_step: pass all four gradients or none of them");
+  Workspace ws(workspace, workspace_bytes);
+  const auto sp = plan_posnce_separable(ws, b, d_proj, precision, any_grad);
+  rc = ws_fits(ws, "mi_posnce_separable_step");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t k = d_proj;
+  const bool bf = precision == MI_PREC_BF16;
+  rc = separable_project(PosNceEst::kSep, bf, x, y, wg, wh, b, b, d_img, d_txt, k, sp.a, sp.c, st);
+  if (rc) return rc;
+  rc = posnce_chain(sp.a, sp.c, nullptr, sid, b, k, k, mode, precision, grad_out, loss_out, lse_rows, lse_cols, n_pos_out,
+                    sp.da, sp.dc, nullptr, any_grad, sp.n, st);
+  if (rc || !any_grad) return rc;
+  return separable_project_back(PosNceEst::kSep, bf, x, y, wg, wh, b, b, d_img, d_txt, k, sp.da, sp.dc, grad_x, grad_y,
+                                grad_wg, grad_wh, st);
+}
+
+size_t mi_matrix_posnce_workspace_bytes(int64_t b) {
+  if (b <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  plan_posnce(ws, b);
+  return ws.off + 256;
+}
+
+int mi_matrix_posnce_fwd(const float* scores, const int64_t* sid, int64_t b, int mode, float* loss_out, float* lse_rows,
+                         float* lse_cols, int32_t* n_pos, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(scores && sid && loss_out && workspace, "mi_matrix_posnce_fwd: null pointer");
+  MI_CHECK_ARG(b >= 1 && b < ((int64_t)1 << 31), "mi_matrix_posnce_fwd: b must be in [1, 2^31)");
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || mode == MI_NCE_SYMMETRIC, "mi_matrix_posnce_fwd: unknown mode %d", mode);
+  Workspace ws(workspace, workspace_bytes);
+  const PosNcePlan q = plan_posnce(ws, b);
+  const int rc = ws_fits(ws, "mi_matrix_posnce_fwd");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  {
+    ProfScope prof_("posnce_matrix_stats_kernel", st);
+    hipLaunchKernelGGL(posnce_matrix_stats_kernel, dim3((unsigned)q.n_t, (unsigned)q.n_t), dim3(64), 0, st, scores, b,
+                       posnce_stats_out(q, sid));
+  }
+  MI_LAUNCH_CHECK("posnce_matrix_stats_kernel");
+  return posnce_finish(q, b, mode, loss_out, lse_rows, lse_cols, n_pos, st);
+}
+
+int mi_matrix_posnce_bwd(const float* scores, const int64_t* sid, int64_t b, int mode, const float* lse_rows,
+                         const float* lse_cols, const int32_t* n_pos, const float* grad_out, float* grad_scores,
+                         void* stream) {
+  MI_CHECK_ARG(scores && sid && lse_rows && n_pos && grad_scores, "mi_matrix_posnce_bwd: null pointer");
+  MI_CHECK_ARG(b >= 1 && b < ((int64_t)1 << 31), "mi_matrix_posnce_bwd: b must be in [1, 2^31)");
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || mode == MI_NCE_SYMMETRIC, "mi_matrix_posnce_bwd: unknown mode %d", mode);
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || lse_cols, "mi_matrix_posnce_bwd: the symmetric mode needs lse_cols");
+  const int64_t nt = (b + 63) / 64;
+  hipStream_t st = (hipStream_t)stream;
+  {
+    ProfScope prof_("posnce_matrix_grad_kernel", st);
+    hipLaunchKernelGGL(posnce_matrix_grad_kernel, dim3((unsigned)nt, (unsigned)nt), dim3(64), 0, st, scores, b,
+                       posnce_grad_in(sid, lse_rows, lse_cols, nullptr, n_pos, grad_out, b, mode), grad_scores);
+  }
+  MI_LAUNCH_CHECK("posnce_matrix_grad_kernel");
   return MI_OK;
 }
 

@@ -83,10 +83,14 @@ def train_mutual_information(args, device):
     bank_k = getattr(args, "memory_bank", None)
     if bank_k is not None:
         hard = dict(hard, mi_estimator=getattr(args, "mi_estimator", None), memory_bank=bank_k)
+    # --study_positives: the same losses with every same-study pair as a positive
+    study_pos = bool(getattr(args, "study_positives", False))
+    if study_pos:
+        hard = dict(hard, mi_estimator=getattr(args, "mi_estimator", None), study_positives=True)
     if getattr(args, "synthetic", False):
         model_manager = MultiModalManager(d_img=args.embed_dim_img, d_txt=args.embed_dim_txt, critic=critic,
                                           mi_estimator=getattr(args, "mi_estimator", None), hard_negatives=hard_k,
-                                          memory_bank=bank_k)
+                                          memory_bank=bank_k, study_positives=study_pos)
         source = synthetic_embedding_source(args, device)
     elif getattr(args, "synthetic_encoders", False):
         from mutual_info_img_txt.model import ResNet256_6_2_1, TextBert

@@ -202,6 +202,13 @@ SIGNATURES = {
     "mi_banknce_bilinear_step": (c_int, [_P] * 7 + [_I64] * 4 + [_I, _I] + [_P] * 8 + [_SZ, _P]),
     "mi_banknce_separable_workspace_bytes": (_SZ, [_I64] * 5 + [_I, _I, _I]),
     "mi_banknce_separable_step": (c_int, [_P] * 8 + [_I64] * 5 + [_I, _I] + [_P] * 9 + [_SZ, _P]),
+    "mi_posnce_bilinear_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I, _I]),
+    "mi_posnce_bilinear_step": (c_int, [_P] * 4 + [_I64] * 3 + [_I, _I] + [_P] * 9 + [_SZ, _P]),
+    "mi_posnce_separable_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I, _I]),
+    "mi_posnce_separable_step": (c_int, [_P] * 5 + [_I64] * 4 + [_I, _I] + [_P] * 10 + [_SZ, _P]),
+    "mi_matrix_posnce_workspace_bytes": (_SZ, [_I64]),
+    "mi_matrix_posnce_fwd": (c_int, [_P, _P, _I64, _I] + [_P] * 5 + [_SZ, _P]),
+    "mi_matrix_posnce_bwd": (c_int, [_P, _P, _I64, _I] + [_P] * 6),
 }
 MI_TOPK_MAX_K = 32  # include/mi_critic.h
 

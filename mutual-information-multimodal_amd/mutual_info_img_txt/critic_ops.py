@@ -1,5 +1,5 @@
 """The one binding of the critic entry points of the C ABI (mi_bilinear_*, mi_separable_*, mi_concat_mlp_*, mi_nce_*,
-mi_fdiv_*, mi_rank_*, mi_topk_*, mi_hardnce_*, mi_banknce_*), shared by ``mi_critics`` (eager autograd), ``graphed`` (hipGraph step) and ``distributed`` (sharded step).
+mi_fdiv_*, mi_rank_*, mi_topk_*, mi_hardnce_*, mi_banknce_*, mi_posnce_*), shared by ``mi_critics`` (eager autograd), ``graphed`` (hipGraph step) and ``distributed`` (sharded step).
 
 An ops object scores the row block ``x`` [b_rows, d_img] (starting at ``row_offset``) against all of ``y_all``
 [b, d_txt]; a whole batch is ``b_rows == b``, ``row_offset == 0``.  Each ``*_call`` method writes one entry point's
@@ -123,6 +123,27 @@ def hardnce_matrix_bwd(scores, mode, k, r, c, idx_rows, idx_cols, grad_out):
     return g
 
 
+def posnce_matrix_fwd(scores, sid, mode):
+    """Study-positive InfoNCE of a float32 [B, B] score matrix (mi_matrix_posnce_fwd): (loss [1], lse_rows [B], lse_cols
+    [B], n_pos int32 [B]); both LSEs in either mode."""
+    b, dev = scores.shape[0], scores.device
+    ws = _hip.workspace(_hip.load().mi_matrix_posnce_workspace_bytes(b), dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    r, c = torch.empty(b, dtype=torch.float32, device=dev), torch.empty(b, dtype=torch.float32, device=dev)
+    n_pos = torch.empty(b, dtype=torch.int32, device=dev)
+    _hip.call("mi_matrix_posnce_fwd", dev, scores.data_ptr(), sid.data_ptr(), b, mode, loss.data_ptr(), r.data_ptr(),
+              c.data_ptr(), n_pos.data_ptr(), ws.data_ptr(), ws.numel())
+    return loss, r, c, n_pos
+
+
+def posnce_matrix_bwd(scores, sid, mode, r, c, n_pos, grad_out):
+    """grad_scores [B, B] of grad_out[0] * loss (mi_matrix_posnce_bwd) from the forward's LSEs and positive counts."""
+    g = torch.empty_like(scores)
+    _hip.call("mi_matrix_posnce_bwd", scores.device, scores.data_ptr(), sid.data_ptr(), scores.shape[0], mode,
+              r.data_ptr(), _p(c), n_pos.data_ptr(), _p(grad_out), g.data_ptr())
+    return g
+
+
 class _HipOps:
     """The ops protocol of ``distributed.GlobalBatchCriticFn`` (forward / merge / backward) on the C ABI.  ``saved`` is
     (x, y_all, params, sid_rows, sid_all, row_offset, precision, scores, ws) for every critic."""
@@ -231,6 +252,19 @@ class _HipOps:
         grads = [torch.empty_like(t) for t in (x, y, *params)] if need_grad else []
         self.banknce_call(x, y, params, sid, bank_x, bank_y, bank_sid, mode, precision, loss, r, c, grads, ws)()
         return loss, r, c, grads
+
+    def posnce_step(self, x, y, params, sid, mode, precision, need_grad):
+        """The study-positive InfoNCE of the whole batch in one call of ``mi_posnce_<critic>_step`` (bilinear and separable
+        critics), with the gradients of 1 * loss when ``need_grad``: (loss [1], lse_rows [B], lse_cols [B], n_pos int32
+        [B], [grad_x, grad_y, grad_params...] or [])."""
+        b, dev = x.shape[0], x.device
+        ws = _hip.workspace(self.posnce_workspace_bytes(b, x.shape[1], y.shape[1], params, precision, need_grad), dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        r, c = torch.empty(b, dtype=torch.float32, device=dev), torch.empty(b, dtype=torch.float32, device=dev)
+        n_pos = torch.empty(b, dtype=torch.int32, device=dev)
+        grads = [torch.empty_like(t) for t in (x, y, *params)] if need_grad else []
+        self.posnce_call(x, y, params, sid, mode, precision, loss, r, c, n_pos, grads, ws)()
+        return loss, r, c, n_pos, grads
 
     # ---------------------------------------------- per-sample InfoNCE on a row block (distributed.GlobalBatchNceFn)
     def nce_forward(self, x, y_all, params, sid_rows, sid_all, row_offset, mode, precision, need_grad=True):
@@ -364,6 +398,19 @@ class HipBilinearOps(_HipOps):
         return _call("mi_banknce_bilinear_step", x.device, x.data_ptr(), y.data_ptr(), _p(w), sid.data_ptr(), _p(bank_x),
                      bank_y.data_ptr(), bank_sid.data_ptr(), x.shape[0], bank_y.shape[0], x.shape[1], y.shape[1], mode,
                      precision, None, loss.data_ptr(), _p(r), _p(c), _p(gx), _p(gy), _p(gw), ws.data_ptr(), ws.numel())
+
+    @staticmethod
+    def posnce_workspace_bytes(b, dx, dy, params, precision, need_grad):
+        return _hip.load().mi_posnce_bilinear_workspace_bytes(b, dx, dy, precision, int(bool(need_grad)))
+
+    def posnce_call(self, x, y, params, sid, mode, precision, loss, r, c, n_pos, grads, ws):
+        """Study-positive InfoNCE step (mi_posnce_bilinear_step); ``r`` / ``c`` / ``n_pos`` may be None, ``grads`` [] for
+        the forward launches alone."""
+        w = params[0] if params else None
+        gx, gy, gw = (grads + [None] * 3)[:3]
+        return _call("mi_posnce_bilinear_step", x.device, x.data_ptr(), y.data_ptr(), _p(w), sid.data_ptr(), x.shape[0],
+                     x.shape[1], y.shape[1], mode, precision, None, loss.data_ptr(), _p(r), _p(c), _p(n_pos), _p(gx),
+                     _p(gy), _p(gw), ws.data_ptr(), ws.numel())
 
     @staticmethod
     def nce_shard_workspace_bytes(br, b, dx, dy, params, precision):
@@ -569,6 +616,19 @@ class HipSeparableOps(_HipOps):
                      sid.data_ptr(), _p(bank_x), bank_y.data_ptr(), bank_sid.data_ptr(), x.shape[0], bank_y.shape[0],
                      x.shape[1], y.shape[1], wg.shape[1], mode, precision, None, loss.data_ptr(), _p(r), _p(c),
                      *[_p(g) for g in grads or [None] * 4], ws.data_ptr(), ws.numel())
+
+    @staticmethod
+    def posnce_workspace_bytes(b, dx, dy, params, precision, need_grad):
+        return _hip.load().mi_posnce_separable_workspace_bytes(b, dx, dy, params[0].shape[1], precision,
+                                                               int(bool(need_grad)))
+
+    def posnce_call(self, x, y, params, sid, mode, precision, loss, r, c, n_pos, grads, ws):
+        """Study-positive InfoNCE step (mi_posnce_separable_step), as ``HipBilinearOps.posnce_call``."""
+        wg, wh = params
+        return _call("mi_posnce_separable_step", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
+                     sid.data_ptr(), x.shape[0], x.shape[1], y.shape[1], wg.shape[1], mode, precision, None,
+                     loss.data_ptr(), _p(r), _p(c), _p(n_pos), *[_p(g) for g in grads or [None] * 4], ws.data_ptr(),
+                     ws.numel())
 
     @staticmethod
     def nce_shard_workspace_bytes(br, b, dx, dy, params, precision):

@@ -103,7 +103,7 @@ class MultiModalManager:
                  d_img: int = 768, d_txt: int = 768, critic: str = "concat_mlp", hidden_dims=(1024, 512),
                  d_proj: int = 256, image_model=None, text_model=None, bert_config=None, embed_proj_dim=None,
                  autocast_dtype=None, mi_estimator: Optional[str] = None, hard_negatives: Optional[int] = None,
-                 memory_bank: Optional[int] = None):
+                 memory_bank: Optional[int] = None, study_positives: bool = False):
         self.bert_pretrained_dir = bert_pretrained_dir
         self.bert_config_name = bert_config_name
         self.output_channels = output_channels
@@ -158,6 +158,17 @@ class MultiModalManager:
                                  "batch + bank)")
             self.memory_bank = check_capacity(memory_bank)
             self.memory_bank_estimator = mi_estimator
+        # study-positive InfoNCE (study_positives.py): the row-wise / symmetric loss with every same-study pair as a
+        # positive (a training loss, not an MI bound)
+        self.study_positives = bool(study_positives)
+        if self.study_positives:
+            if mi_estimator not in _hip.NCE_ESTIMATORS:
+                raise ValueError(f"study_positives is a switch on the per-sample InfoNCE: it needs mi_estimator in "
+                                 f"{sorted(_hip.NCE_ESTIMATORS)} (got {mi_estimator!r})")
+            if hard_negatives is not None or memory_bank is not None:
+                raise ValueError("study_positives cannot be combined with hard_negatives or memory_bank (those losses "
+                                 "drop same-study pairs; this one trains on them)")
+            self.study_positives_estimator = mi_estimator
         self.d_img, self.d_txt = d_img, d_txt
         self.training_loss = []
         self._graphed = None
@@ -185,8 +196,16 @@ class MultiModalManager:
         ``hard_negatives.hard_negative_infonce`` here, eagerly (a training loss, not an MI bound).  A manager built with
         ``memory_bank=K`` runs ``memory_bank.memory_bank_infonce`` against its queue ``self.bank`` here, eagerly; the
         training loop pushes each batch's detached embeddings after the optimizer steps.  The queue is not checkpointed:
-        after a resume it is empty and refills."""
+        after a resume it is empty and refills.  A manager built with ``study_positives=True`` runs
+        ``study_positives.study_positive_infonce`` here, eagerly (a training loss, not an MI bound)."""
         est = mi_critics.check_estimator(mi_estimator, self.critic_kind)
+        if self.study_positives:
+            if mi_estimator != self.study_positives_estimator:
+                raise ValueError(f"this manager trains the study-positive form of {self.study_positives_estimator!r}; "
+                                 f"mi_step got mi_estimator={mi_estimator!r}")
+            from .study_positives import study_positive_infonce
+            return study_positive_infonce(embedding_img, embedding_txt, study_id, self.mi_discriminator,
+                                          symmetric=mi_estimator == "infonce_symmetric", precision=precision)
         if self.memory_bank is not None:
             if mi_estimator != self.memory_bank_estimator:
                 raise ValueError(f"this manager trains the memory-bank form of {self.memory_bank_estimator!r}; "

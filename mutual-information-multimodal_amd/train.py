@@ -35,6 +35,9 @@ def construct_training_parameters(argv=None):
     # memory-bank InfoNCE: the row-wise / symmetric loss against the batch and a queue of the last K samples' embeddings
     # (ceiling log(batch + K); not checkpointed: the queue refills after a resume)
     p.add_argument('--memory_bank', default=None, type=int)
+    # study-positive InfoNCE: the row-wise / symmetric loss with every same-study pair as a positive (a loss, not an MI
+    # bound)
+    p.add_argument('--study_positives', action='store_true')
     return p.parse_args(argv)
 
 
@@ -57,6 +60,13 @@ def check_training_parameters(args):
         if getattr(args, "hard_negatives", None) is not None:
             raise ValueError("--memory_bank and --hard_negatives cannot be combined")
         check_capacity(args.memory_bank)
+    if getattr(args, "study_positives", False):
+        from mutual_info_img_txt._hip import NCE_ESTIMATORS
+        if args.mi_estimator not in NCE_ESTIMATORS:
+            raise ValueError(f"--study_positives needs --mi_estimator in {sorted(NCE_ESTIMATORS)} "
+                             f"(got {args.mi_estimator!r})")
+        if getattr(args, "hard_negatives", None) is not None or getattr(args, "memory_bank", None) is not None:
+            raise ValueError("--study_positives cannot be combined with --hard_negatives or --memory_bank")
     return args
 
 
