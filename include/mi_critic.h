@@ -48,8 +48,8 @@
  * precision: MI_PREC_F32 = 0 (fp32-input MFMA, exact fp32 products, parity mode),
  *            MI_PREC_BF16 = 1 (bf16 MFMA operands, fp32 accumulate),
  *            MI_PREC_BF16X3 = 2 (bilinear critic with a weight matrix only: every operand split into two bf16 parts,
- *            three bf16 MFMAs per product, fp32 accumulate -- products good to ~2^-16 at a third of the bf16 rate; the
- *            separable critic runs its fp32 path under this code, the concat-MLP entry points reject it),
+ *            three bf16 MFMAs per product, fp32 accumulate -- products good to ~2^-16 at a third of the bf16 rate;
+ *            mi_separable_fwd / _bwd / _step and the concat-MLP entry points reject it),
  *            MI_PREC_FP8 = 3 (bilinear critic with a weight matrix only; widths multiples of 16: x, y, W and T = x W are
  *            quantised to OCP e4m3 with per-tensor scales absmax / 448 computed on the device, both forward products
  *            run on the fp8 MFMA with fp32 accumulation, the backward is straight-through on the quantised values
@@ -240,7 +240,11 @@ int mi_separable_path(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, i
 /* ---- fused separable critic: S = (X Wg)(Y Wh)^T, bound, all gradients ------------------------------- */
 /* BASELINE.json configs[1] (an extension: the reference has no separable critic; bound, masking and pair semantics are
  * the reference's).  X [b_rows, d_img], Y [b, d_txt], Wg [d_img, d_proj], Wh [d_txt, d_proj].  The projections run on
- * this library's MFMA kernels (no library GEMM).  Sharding arguments as for mi_bilinear_*. */
+ * this library's MFMA kernels (no library GEMM).  Sharding arguments as for mi_bilinear_*.
+ * precision: MI_PREC_F32 (exact fp32 products on the generic kernels) or MI_PREC_BF16 (the fused kernels where
+ * mi_separable_path says so, bf16 operands on the generic kernels otherwise).  mi_separable_fwd / _bwd / _step answer
+ * every other code with MI_EINVAL before anything touches the device; the two host queries still take the codes of the
+ * bilinear critic and report the generic plan for them. */
 size_t mi_separable_workspace_bytes(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj,
                                     int precision);
 int mi_separable_fwd(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid_rows,

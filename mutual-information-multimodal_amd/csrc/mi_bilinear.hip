@@ -1235,6 +1235,9 @@ static int check_separable(const char* fn, int64_t br, int64_t b, int64_t row_of
   int rc = check_common(fn, br, b, row_offset, dx, dy, precision);
   if (rc) return rc;
   MI_CHECK_ARG(k >= 1, "%s: projection width must be >= 1", fn);
+  // bf16x3 and fp8 exist for the bilinear critic only: the kernels below would run them as single-pass bf16
+  MI_CHECK_ARG(precision == MI_PREC_F32 || precision == MI_PREC_BF16,
+               "%s: precision %d is not available for the separable critic (f32, bf16)", fn, precision);
   return MI_OK;
 }
 
