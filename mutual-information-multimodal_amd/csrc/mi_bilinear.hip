@@ -263,12 +263,14 @@ static int fast_prep_and_t(const float* x, const float* y, const float* w, const
   if (fused) {
     // one launch: T tiles straight from the fp32 operands, the other conversions on the CUs the tiles leave free
     CvtJobs side{};
-    // (with the two-launch tail nobody reads X^T row-major any more: only its fragment-major form)
+    // (with the two-launch tail nobody reads X^T row-major any more: only its fragment-major form, which the T tiles of
+    // the whole step write themselves where the shape allows -- launch_prep_t drops job 0 then and X is read once)
     side.j[0] = CvtJob{x, br, dx, nullptr, p.tail ? nullptr : p.xtb, 0, 0, nullptr, 0, 0, p.xtfb};
     if (part == 0) side.j[1] = CvtJob{y, b, dy, p.yb, nullptr, 0, 0, p.yfb};
     side.j[2] = CvtJob{w, dx, dy, p.wb, nullptr, 0, 0, p.wfb};
     if (part == 0) side.dup = p.stage.dup_job(sid_rows, sid_cols, row_offset);
-    const int rc1 = launch_prep_t(x, w, br, dy, dx, p.tb, p.tfb, side, st, "bilinear prep + T = X W");
+    const int rc1 = launch_prep_t(x, w, br, dy, dx, p.tb, p.tfb, side, st, "bilinear prep + T = X W", false, nullptr, nullptr,
+                                  p.tail && part == 0);
     if (rc1 != MI_EINVAL) return rc1;
   }
   const int x3 = p.x3;

@@ -42,8 +42,17 @@ static inline void stamp_select(const char* what, hipStream_t st) {
     stamp_select(what, st);                                               \
     args.exp_mode = getenv("MI_EXP") ? atoi(getenv("MI_EXP")) : 0;        \
   } while (0)
+// where the workgroup runs and what it does: (tag << 40) | (XCC_ID << 32) | HW_ID (cu_id bits 8-11, sh_id 12, se_id 13-15)
+#define MI_STAMP_PLACE(slot, tag)                                                                                \
+  do {                                                                                                           \
+    if (threadIdx.x == 0 && g_stamps)                                                                            \
+      g_stamps[((size_t)blockIdx.x + gridDim.x * (blockIdx.y + (size_t)gridDim.y * blockIdx.z)) * 8 + (slot)] =  \
+          ((unsigned long long)(tag) << 40) | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | \
+          (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4);                                          \
+  } while (0)
 #else
 #define MI_STAMP(slot) do {} while (0)
+#define MI_STAMP_PLACE(slot, tag) do {} while (0)
 #define MI_STAMP_SELECT(what, st) do {} while (0)
 #endif
 
@@ -258,6 +267,33 @@ __device__ __forceinline__ void wave_tile_store_bf16(f32x16 (&acc)[2][2], char* 
       const int64_t gcol = nb + c_l, grow = mb + chunk * 8;
       if (gcol < N && grow < M) seam_store<SEAM>(reinterpret_cast<bf16x8*>(tr + gcol * ld_tr + grow), v);
     }
+  }
+}
+
+// The same store for a wave's 32 x 64 tile (the 64-row T tiles of bilinear_prep_t_kernel): row-major and fragment-major,
+// whole tiles only (no bounds: the caller takes this form for M % 64 == 0, N % 64 == 0).
+template <int SEAM = kSeamPlain>
+__device__ __forceinline__ void wave_tile_store_bf16_32(f32x16 (&acc)[1][2], char* lds, bf16_t* rm, int64_t ld_rm,
+                                                        int64_t mb, int64_t nb, int64_t N, bf16_t* frag) {
+  const int lane = threadIdx.x & 63;
+  const int col_l = lane & 31, half = lane >> 5;
+  const int srow = lane >> 3, chunk = lane & 7;
+  wave_lds_fence();
+#pragma unroll
+  for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row_l = (r & 3) + 8 * (r >> 2) + 4 * half;
+      *reinterpret_cast<bf16_t*>(lds + row_l * kEpiPitch + (tn * 32 + col_l) * 2) = (bf16_t)acc[0][tn][r];
+    }
+  wave_lds_fence();
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int row_l = it * 8 + srow;
+    const bf16x8 v = *reinterpret_cast<const bf16x8*>(lds + row_l * kEpiPitch + chunk * 16);
+    const int64_t grow = mb + row_l, gcol = nb + chunk * 8;
+    seam_store<SEAM>(reinterpret_cast<bf16x8*>(rm + grow * ld_rm + gcol), v);
+    if (frag) seam_store<SEAM>(reinterpret_cast<bf16x8*>(frag + frag_major_offset(grow, gcol, N)), v);
   }
 }
 
@@ -1516,15 +1552,31 @@ __device__ __forceinline__ void dup_flags_block(const DupFlagJob& J, int a, int 
     const int64_t* c = J.sid_cols + (int64_t)b * 32;
     // the block's main diagonal pairs samples with themselves iff the diagonal of the pair matrix runs through it aligned
     const bool diag_block = (J.row_offset & 31) == 0 && (int64_t)b * 32 == (int64_t)a * 32 + J.row_offset;
-    bool any = false, other = false;
-#pragma unroll 8
-    for (int j = 0; j < 32; ++j) {
-      const int64_t v = c[j];
+    // 256 64-bit compares per thread, and the 256 calls of the headline step hold a fifth of the prep launch's workgroup
+    // slots: one compare and one OR per pair, kept per group of 8 columns (4.2 us per call; 4.8 with the diagonal's
+    // exclusion tested at every pair); only a thread on the diagonal block then leaves its own group out and goes over
+    // that group's 56 off-diagonal pairs again (the pairs to exclude are column 8 q + e against row e).
+    bool grp[4] = {false, false, false, false};
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const bool eq = v == mine[e];
-        any |= eq;
-        other |= eq && !(diag_block && j == 8 * q + e);
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int jj = 0; jj < 8; ++jj) {
+        const int64_t v = c[8 * g + jj];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) grp[g] |= v == mine[e];
+      }
+    const bool any = grp[0] | grp[1] | grp[2] | grp[3];
+    bool other = any;
+    if (diag_block) {
+      other = false;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) other |= g != q && grp[g];
+#pragma unroll
+      for (int jj = 0; jj < 8; ++jj) {
+        const int64_t v = c[8 * q + jj];
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (e != jj) other |= v == mine[e];
       }
     }
     int f = other ? 2 : (any ? 1 : 0);
@@ -1699,10 +1751,11 @@ struct PrepTArgs {
   bf16_t* tfb;       // fragment-major copy (EpiOut::bf_frag) or null
   bf16_t* ttb;       // T^T [n][m] or null (the G-materialising path reads it as the B operand of dY = G^T T; m % 8 == 0)
   int n_t;           // blocks of the T role (tiles, padded to 8 x tiles-per-panel x ceil(panels / 8))
-  int job_begin[6];  // conversion blocks (counted from n_t): first block of job q; [4] = flags, [5] = end
+  int job_begin[6];  // conversion blocks (counted from n_t + n_t2): first block of job q; flag blocks: [4] .. [5] - 1
   int job_nx[4];     // 64-column tiles per tile row of job q
   CvtJobs jobs;
   int x_bf16;        // x points to bf16 data [m][k] (the bf16 boundary): the tile goes to LDS as it lies
+  bf16_t* xtfb;      // fragment-major X^T (the A operand of bilinear_dw_kernel) written by the T role itself, or null
   // an optional SECOND product in the same launch (separable critic: A = X Wg and C = Y Wh): blocks [n_t, n_t + n_t2)
   const float* x2;
   const float* w2;
@@ -1719,12 +1772,24 @@ struct PrepTSecond {
   bf16_t* tfb;
 };
 constexpr int kPrepTLdB = 160;  // W image row pitch in bf16 elements (128 columns + 32 of padding = 320 bytes)
-constexpr size_t kPrepTSmem = (2 * kTile * kG2LD + 2 * kG2KT * kPrepTLdB) * sizeof(bf16_t);  // 77,824 bytes
+// dynamic LDS of a launch with tm-row T tiles: 77,824 bytes (128 rows), 59,392 (64 rows); two workgroups per CU either way
+constexpr size_t prep_t_smem(int tm) { return (2 * tm * kG2LD + 2 * kG2KT * kPrepTLdB) * sizeof(bf16_t); }
 
 // XB16: x arrives as bf16 (a compile-time variant: as a run-time branch the second staging path cost the fp32 kernel 10
 // registers and 48 bytes of scratch)
-template <bool XB16>
+//
+// TM: rows of a T tile.  128: four waves of 64 x 64.  64: four waves of 32 x 64 -- twice the workgroups (one per CU at
+// B = 4096), each k-step stages half the X rows and issues half the MFMAs; the same MFMA and the same K order per output
+// element, so T keeps its bits.
+// XTW: the T role also writes the fragment-major X^T (PrepTArgs::xtfb) from the bf16 image of X it holds in LDS, and the
+// conversion job that read X a second time for it is gone.  A 1 KB block (32 features x 16 rows, MFMA operand lane order)
+// is what the transposing ds_read_b64_tr_b16 returns from the row-major image; the column tiles of a row panel share
+// the k-steps round-robin (tile nb writes the steps t with t % (n / 128) == nb), so every block is written once.
+template <bool XB16, int TM = kTile, bool XTW = false>
 static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArgs a) {
+  static_assert(TM == 64 || TM == 128, "T tiles have 64 or 128 rows");
+  static_assert(!(XB16 && XTW), "the bf16 boundary keeps its X^T conversion job");
+  constexpr int NTM = TM / 64;  // 32-row MFMA tiles per wave
   kernarg_prefetch<(int)sizeof(PrepTArgs)>();
   MI_WALL_SCOPE(kWallPrep);
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -1733,7 +1798,7 @@ static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArg
   if (blk >= a.n_t + a.n_t2) {  // ---- conversion roles
     float(*tile)[65] = reinterpret_cast<float(*)[65]>(smem_raw);
     const int c = blk - a.n_t - a.n_t2;
-    if (c >= a.job_begin[4]) {
+    if (c >= a.job_begin[4] && c < a.job_begin[5]) {
       const DupFlagJob& D = a.jobs.dup;
       const int chunks = (D.nb + 63) / 64, w = c - a.job_begin[4];
       if (w < D.na * chunks) dup_flags_block(D, w / chunks, (w % chunks) * 64, reinterpret_cast<int64_t*>(smem_raw));
@@ -1741,17 +1806,19 @@ static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArg
     }
     int q = 0;
     while (q < 3 && c >= a.job_begin[q + 1]) ++q;
+    MI_STAMP_PLACE(6, q + 1);
     const int t = c - a.job_begin[q];
     cvt_tile_block<kSeam_PREP_CVT>(a.jobs.j[q], t % a.job_nx[q], t / a.job_nx[q], tile);
     MI_STAMP(5);
     return;
   }
-  // ---- a 128 x 128 tile of T.  What bounds this role is bytes through the fabric (the fp32 operands are twice the
+  MI_STAMP_PLACE(6, 0);
+  // ---- a TM x 128 tile of T.  What bounds this role is bytes through the fabric (the fp32 operands are twice the
   // bf16 copies the plain GEMM reads, every X panel is wanted by n / 128 tiles): the tiles of one row panel run back to
   // back on ONE XCD (xcd_decode), so its L2 fetches the panel once and keeps W.  (A 128 x 64 tiling with a 128-deep
   // k-step -- twice the tiles, half the round trips -- moved 96 MB instead of 64 and took 22.9 us instead of 16.4.)
-  bf16_t* As = reinterpret_cast<bf16_t*>(smem_raw);  // [2][128 rows][72]: X as it lies, K-contiguous
-  bf16_t* Bs = As + 2 * kTile * kG2LD;               // [2][64 k][160]: W as it lies, n-contiguous; the B fragments come
+  bf16_t* As = reinterpret_cast<bf16_t*>(smem_raw);  // [2][TM rows][72]: X as it lies, K-contiguous
+  bf16_t* Bs = As + 2 * TM * kG2LD;                  // [2][64 k][160]: W as it lies, n-contiguous; the B fragments come
                                                      // out K-major through ds_read_b64_tr_b16 (320-byte rows: the four
                                                      // rows of a transposed read fall on disjoint quarters of the banks)
   // which product (the second one's blocks follow the first one's; both ranges are multiples of 8 long)
@@ -1762,8 +1829,8 @@ static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArg
   bf16_t* const ptb = second ? a.tb2 : a.tb;
   bf16_t* const ptfb = second ? a.tfb2 : a.tfb;
   int nb_, mb_;
-  if (!xcd_decode((int)(pn / kTile), (int)((pm + kTile - 1) / kTile), nb_, mb_, 0, second ? blk - a.n_t : blk)) return;
-  const int64_t m0 = (int64_t)mb_ * kTile, n0 = (int64_t)nb_ * kTile;
+  if (!xcd_decode((int)(pn / kTile), (int)((pm + TM - 1) / TM), nb_, mb_, 0, second ? blk - a.n_t : blk)) return;
+  const int64_t m0 = (int64_t)mb_ * TM, n0 = (int64_t)nb_ * kTile;
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   const int wm = wave >> 1, wn = wave & 1;
@@ -1774,19 +1841,21 @@ static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArg
   // and receives column (lane & 15) of its four rows; a lane's B fragment is rows 8 (lane >> 5) .. + 7 of column lane & 31
   const int tr_off = (8 * half + ((lane >> 2) & 3)) * (kPrepTLdB * 2) + (wn * 64 + 16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
 
-  f32x16 acc[2][2];
+  f32x16 acc[NTM][2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+  for (int i = 0; i < NTM; ++i)
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-  f32x4 rx[8], rw[8];
-  const float* xp[8];
+  constexpr int XQ = TM / 16;   // fp32 x: float4 loads per thread and k-step
+  constexpr int XBQ = TM / 32;  // bf16 x: 16-byte chunks per thread and k-step
+  f32x4 rx[XQ], rw[8];
+  const float* xp[XQ];
   if constexpr (!XB16) {
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
+    for (int q = 0; q < XQ; ++q) {
       int64_t row = m0 + xr + 16 * q;
       if (row >= pm) row = pm - 1;  // clamped rows only feed outputs the epilogue drops
       xp[q] = px + row * pk + 4 * xc;
@@ -1795,11 +1864,11 @@ static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArg
   const float* wp = pw + (int64_t)wk * pn + n0 + 4 * wc;
   // bf16 x: a 128 x 64 tile is 1024 chunks of 16 bytes, four per thread: rows (tid >> 3) + 32 q, chunk tid & 7; they
   // travel in rx[0..3] as raw bits
-  const bf16_t* xbp[4];
+  const bf16_t* xbp[XBQ];
   const int br_ = tid >> 3, bc_ = tid & 7;
   if constexpr (XB16) {
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
+    for (int q = 0; q < XBQ; ++q) {
       int64_t row = m0 + br_ + 32 * q;
       if (row >= pm) row = pm - 1;
       xbp[q] = reinterpret_cast<const bf16_t*>(px) + row * pk + 8 * bc_;
@@ -1808,10 +1877,10 @@ static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArg
   auto load_tile = [&](int64_t k0) {
     if constexpr (XB16) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) rx[q] = *reinterpret_cast<const f32x4*>(xbp[q] + k0);
+      for (int q = 0; q < XBQ; ++q) rx[q] = *reinterpret_cast<const f32x4*>(xbp[q] + k0);
     } else {
 #pragma unroll
-      for (int q = 0; q < 8; ++q) rx[q] = *reinterpret_cast<const f32x4*>(xp[q] + k0);
+      for (int q = 0; q < XQ; ++q) rx[q] = *reinterpret_cast<const f32x4*>(xp[q] + k0);
     }
 #pragma unroll
     for (int q = 0; q < 8; ++q) rw[q] = *reinterpret_cast<const f32x4*>(wp + (k0 + 8 * q) * pn);
@@ -1819,12 +1888,12 @@ static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArg
   auto store_tile = [&](int buf) {
     if constexpr (XB16) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) *reinterpret_cast<f32x4*>(&As[(buf * kTile + br_ + 32 * q) * kG2LD + 8 * bc_]) = rx[q];
+      for (int q = 0; q < XBQ; ++q) *reinterpret_cast<f32x4*>(&As[(buf * TM + br_ + 32 * q) * kG2LD + 8 * bc_]) = rx[q];
     } else {
 #pragma unroll
-      for (int q = 0; q < 8; ++q) {
+      for (int q = 0; q < XQ; ++q) {
         const bf16x4 o = {(bf16_t)rx[q][0], (bf16_t)rx[q][1], (bf16_t)rx[q][2], (bf16_t)rx[q][3]};
-        *reinterpret_cast<bf16x4*>(&As[(buf * kTile + xr + 16 * q) * kG2LD + 4 * xc]) = o;
+        *reinterpret_cast<bf16x4*>(&As[(buf * TM + xr + 16 * q) * kG2LD + 4 * xc]) = o;
       }
     }
 #pragma unroll
@@ -1835,6 +1904,9 @@ static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArg
   };
 
   const int nt = (int)(pk / kG2KT);
+  // X^T blocks (XTW): the same transposed read over the X image (144-byte rows), 16 rows x 32 features per block
+  [[maybe_unused]] const int ncol = (int)(pn / kTile);
+  [[maybe_unused]] const int xt_off = (8 * half + ((lane >> 2) & 3)) * (kG2LD * 2) + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
   load_tile(0);
   store_tile(0);
   __syncthreads();
@@ -1843,14 +1915,14 @@ static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArg
     const int buf = t & 1;
     const bool more = t + 1 < nt;
     if (more) load_tile((int64_t)(t + 1) * kG2KT);
-    const bf16_t* at = As + buf * kTile * kG2LD;
+    const bf16_t* at = As + buf * TM * kG2LD;
     const char* bt = reinterpret_cast<const char*>(Bs + buf * kG2KT * kPrepTLdB) + tr_off;
 #pragma unroll
     for (int kk = 0; kk < kG2KT / 16; ++kk) {
-      bf16x8 af[2], bfr[2];
+      bf16x8 af[NTM], bfr[2];
 #pragma unroll
-      for (int tm = 0; tm < 2; ++tm)
-        af[tm] = *reinterpret_cast<const bf16x8*>(&at[(wm * 64 + tm * 32 + r32) * kG2LD + kk * 16 + 8 * half]);
+      for (int tm = 0; tm < NTM; ++tm)
+        af[tm] = *reinterpret_cast<const bf16x8*>(&at[(wm * (32 * NTM) + tm * 32 + r32) * kG2LD + kk * 16 + 8 * half]);
 #pragma unroll
       for (int tn = 0; tn < 2; ++tn) {
         using lds_b4 = __attribute__((address_space(3))) bf16x4;
@@ -1860,10 +1932,28 @@ static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArg
         bfr[tn] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
       }
 #pragma unroll
-      for (int tm = 0; tm < 2; ++tm)
+      for (int tm = 0; tm < NTM; ++tm)
 #pragma unroll
         for (int tn = 0; tn < 2; ++tn)
           acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[tm], bfr[tn], acc[tm][tn], 0, 0, 0);
+    }
+    if constexpr (XTW) {
+      // this k-step's 64 features x TM rows of X^T, behind the MFMAs' issue: TM / 8 blocks, wave w takes w, w + 4, ...
+      // (lane 32 h + f of a block receives rows 8 h .. 8 h + 7 of feature f, as a B fragment above)
+      if (t % ncol == nb_) {
+        using lds_b4 = __attribute__((address_space(3))) bf16x4;
+        const char* xt = reinterpret_cast<const char*>(at) + xt_off;
+#pragma unroll
+        for (int j = 0; j < TM / 32; ++j) {
+          const int xb = wave + 4 * j, ab = xb & 1, ib = xb >> 1;
+          const char* pb = xt + ib * 16 * (kG2LD * 2) + ab * 64;
+          const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(pb));
+          const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(pb + 4 * (kG2LD * 2)));
+          const bf16x8 o = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+          seam_store<kSeam_PREP_CVT>(
+              reinterpret_cast<bf16x8*>(a.xtfb + (((int64_t)(2 * t + ab) * (pm >> 4) + (m0 >> 4) + ib) * 64 + lane) * 8), o);
+        }
+      }
     }
     if (t == 0) MI_STAMP(2);
     if (more) store_tile(buf ^ 1);
@@ -1871,17 +1961,35 @@ static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArg
     if (t == 0) MI_STAMP(3);
   }
   MI_STAMP(4);
-  wave_tile_store_bf16<kSeam_PREP_TILE>(acc, smem_raw + wave * kEpiLdsPerWave, ptb, pn, second ? nullptr : a.ttb, pm, m0 + wm * 64,
-                       n0 + wn * 64, pm, pn, ptfb);
+  if constexpr (TM == kTile)
+    wave_tile_store_bf16<kSeam_PREP_TILE>(acc, smem_raw + wave * kEpiLdsPerWave, ptb, pn, second ? nullptr : a.ttb, pm,
+                                          m0 + wm * 64, n0 + wn * 64, pm, pn, ptfb);
+  else  // whole tiles and no T^T (launch_prep_t takes this form for such calls only)
+    wave_tile_store_bf16_32<kSeam_PREP_TILE>(acc, smem_raw + wave * kEpiLdsPerWave, ptb, pn, m0 + wm * 32, n0 + wn * 64, pn, ptfb);
   MI_STAMP(5);
 }
 
 // conversions: up to four CvtJob (64 x 64 tiles each) + the flag job; returns MI_EINVAL for shapes the fused kernel does
 // not take (the caller then runs the conversion launch and the plain GEMM)
+template <bool XB16, int TM, bool XTW>
+static inline int launch_prep_t_form(const PrepTArgs& a, int n_cvt, hipStream_t st, const char* what) {
+  MI_SET_DYN_SMEM((bilinear_prep_t_kernel<XB16, TM, XTW>), prep_t_smem(TM), "hipFuncSetAttribute(bilinear_prep_t_kernel)");
+  ProfScope prof_(what, st);
+  hipLaunchKernelGGL((bilinear_prep_t_kernel<XB16, TM, XTW>), dim3((unsigned)(a.n_t + a.n_t2 + n_cvt)), dim3(256),
+                     prep_t_smem(TM), st, a);
+  return MI_OK;
+}
+
+// xt_from_tiles: the caller wants nothing of job 0 but the fragment-major X^T of this very x (the bilinear step with the
+// two-launch tail).  Where the shape allows -- fp32 x, m % 128 == 0, no T^T, no second product -- the T role writes it
+// (kernel form XTW) on 64-row tiles and job 0 is dropped: X is read once.  Every other call keeps the 128-row tiles and
+// its conversion jobs.
 static inline int launch_prep_t(const float* x, const float* w, int64_t m, int64_t n, int64_t k, bf16_t* tb, bf16_t* tfb,
                                 const CvtJobs& jobs, hipStream_t st, const char* what, bool x_bf16 = false,
-                                const PrepTSecond* second = nullptr, bf16_t* ttb = nullptr) {
+                                const PrepTSecond* second = nullptr, bf16_t* ttb = nullptr, bool xt_from_tiles = false) {
   static const bool off = getenv("MI_NO_PREP_T") != nullptr;  // A/B switch: separate conversion and GEMM launches
+  // A/B switch: 1 = the form before (128-row tiles, X^T from conversion job 0), 2 = 128-row tiles that write X^T
+  static const int tall = getenv("MI_PREP_T_TALL") ? atoi(getenv("MI_PREP_T_TALL")) : 0;
   if (off || k % 64 != 0 || n % kTile != 0 || m < 1 || (uintptr_t)x % 16 != 0 || (uintptr_t)w % 16 != 0 ||
       (uintptr_t)tb % 16 != 0 || (tfb && (m % 32 != 0 || (uintptr_t)tfb % 16 != 0)))
     return MI_EINVAL;
@@ -1890,7 +1998,17 @@ static inline int launch_prep_t(const float* x, const float* w, int64_t m, int64
   a.x_bf16 = x_bf16 ? 1 : 0;
   if (ttb && (m % 8 != 0 || (uintptr_t)ttb % 16 != 0)) return MI_EINVAL;
   a.ttb = ttb;
-  a.n_t = (int)(8 * (n / kTile) * (((m + kTile - 1) / kTile + 7) / 8));  // padded for the XCD mapping
+  a.jobs = jobs;
+  const CvtJob& j0 = jobs.j[0];
+  const bool xtw = xt_from_tiles && tall != 1 && !x_bf16 && !second && !ttb && m % kTile == 0 && j0.in == x && j0.R == m &&
+                   j0.C == k && j0.out_t_frag && (uintptr_t)j0.out_t_frag % 16 == 0 && !j0.out_rm && !j0.out_t &&
+                   !j0.out_frag && !j0.in_bf16 && j0.n_slab <= 1;
+  const int64_t tm = xtw && tall != 2 ? 64 : kTile;
+  if (xtw) {
+    a.xtfb = j0.out_t_frag;
+    a.jobs.j[0] = CvtJob{};
+  }
+  a.n_t = (int)(8 * (n / kTile) * (((m + tm - 1) / tm + 7) / 8));  // padded for the XCD mapping
   if (second) {
     const PrepTSecond& q = *second;
     if (x_bf16 || q.k % 64 != 0 || q.n % kTile != 0 || q.m < 1 || (uintptr_t)q.x % 16 != 0 || (uintptr_t)q.w % 16 != 0 ||
@@ -1899,10 +2017,14 @@ static inline int launch_prep_t(const float* x, const float* w, int64_t m, int64
     a.x2 = q.x; a.w2 = q.w; a.m2 = q.m; a.n2 = q.n; a.k2 = q.k; a.tb2 = q.tb; a.tfb2 = q.tfb;
     a.n_t2 = (int)(8 * (q.n / kTile) * (((q.m + kTile - 1) / kTile + 7) / 8));
   }
-  a.jobs = jobs;
-  int total = 0;
+  // The flag blocks come first behind the tiles (MI_PREP_T_TALL=1: last, as before): the workgroup slots of the launch
+  // are full from its start to its end, and what is dispatched last ends it -- a 64 x 64 conversion block is shorter
+  // than a flag block.
+  const int n_flag = jobs.dup.na > 0 ? jobs.dup.na * ((jobs.dup.nb + 63) / 64) : 0;
+  const bool flags_first = tall != 1;
+  int total = flags_first ? n_flag : 0;
   for (int q = 0; q < 4; ++q) {
-    const CvtJob& J = jobs.j[q];
+    const CvtJob& J = a.jobs.j[q];
     if (J.R > 0 && (J.R % 4 != 0 || J.C % 4 != 0 || (uintptr_t)J.in % (J.in_bf16 ? 8 : 16) != 0 || (uintptr_t)J.out_rm % 8 != 0 ||
                     (uintptr_t)J.out_t % 8 != 0 || J.n_slab > 1 || (J.out_frag && (J.R % 32 != 0 || J.C % 16 != 0)) ||
                     (J.out_t_frag && (J.C % 32 != 0 || J.R % 16 != 0))))
@@ -1911,21 +2033,17 @@ static inline int launch_prep_t(const float* x, const float* w, int64_t m, int64
     a.job_nx[q] = J.R > 0 ? (int)((J.C + 63) / 64) : 1;
     if (J.R > 0) total += a.job_nx[q] * (int)((J.R + 63) / 64);
   }
-  a.job_begin[4] = total;
-  if (jobs.dup.na > 0) total += jobs.dup.na * ((jobs.dup.nb + 63) / 64);
-  a.job_begin[5] = total;
+  a.job_begin[4] = flags_first ? 0 : total;
+  if (!flags_first) total += n_flag;
+  a.job_begin[5] = a.job_begin[4] + n_flag;
 #ifdef MI_STAMPS
   stamp_select(what, st);
 #endif
-  if (x_bf16) {
-    MI_SET_DYN_SMEM(bilinear_prep_t_kernel<true>, kPrepTSmem, "hipFuncSetAttribute(bilinear_prep_t_kernel)");
-    ProfScope prof_(what, st);
-    hipLaunchKernelGGL(bilinear_prep_t_kernel<true>, dim3((unsigned)(a.n_t + a.n_t2 + total)), dim3(256), kPrepTSmem, st, a);
-  } else {
-    MI_SET_DYN_SMEM(bilinear_prep_t_kernel<false>, kPrepTSmem, "hipFuncSetAttribute(bilinear_prep_t_kernel)");
-    ProfScope prof_(what, st);
-    hipLaunchKernelGGL(bilinear_prep_t_kernel<false>, dim3((unsigned)(a.n_t + a.n_t2 + total)), dim3(256), kPrepTSmem, st, a);
-  }
+  const int rc = x_bf16     ? launch_prep_t_form<true, kTile, false>(a, total, st, what)
+                 : !xtw     ? launch_prep_t_form<false, kTile, false>(a, total, st, what)
+                 : tm == 64 ? launch_prep_t_form<false, 64, true>(a, total, st, what)
+                            : launch_prep_t_form<false, kTile, true>(a, total, st, what);
+  if (rc) return rc;
   MI_LAUNCH_CHECK(what);
   return MI_OK;
 }
