@@ -15,7 +15,7 @@
 //         1 KB blocks, coalesced), and dT^T written fragment-major for (2).  No dT round trip through HBM for dX, no
 //         second orientation of dT, no separate launch.
 // (2) bilinear_dw_kernel: dW = X^T dT, one 32 x 32 tile per workgroup (256 of them at d = 512), the batch dimension
-//     split over the four WAVES of the workgroup and reduced through LDS in a fixed order: no split-K slabs in HBM, no
+//     split over the eight WAVES of the workgroup and reduced through LDS in a fixed order: no split-K slabs in HBM, no
 //     reduce launch, no float atomics.  Both operands are read as fragment-major 1 KB blocks.
 #pragma once
 #include "mi_bilinear_flash.h"
@@ -469,8 +469,9 @@ static inline int launch_flash_tail(FlashTailArgs a, int64_t d, bool slab_f16, b
 // ------------------------------------------------------------------------------------------------ dW = X^T dT
 // out[a][c] = sum_i X[i][a] dT[i][c].  A = X^T (rows a, K = i), B = dT^T (rows c, K = i), both fragment-major:
 //   xt_frag  block (a / 32, i / 16), dtt_frag block (c / 32, i / 16), 1 KB each in MFMA operand lane order.
-// One workgroup per 32 x 32 tile of dW; wave w sums i in [w K / 4, (w + 1) K / 4); the four partial tiles are added
-// through LDS in wave order.
+// One workgroup per 32 x 32 tile of dW; wave w of its kDwWaves = 8 sums the 16-deep blocks [w nkb / 8, (w + 1) nkb / 8) of
+// the batch (nkb = K / 16); the eight partial tiles are added through LDS in wave order.  K < 2^29: the kernel counts a
+// wave's blocks, and a block's element offset, in 32 bits (launch_bilinear_dw refuses more with MI_ESHAPE).
 struct DwArgs {
   const bf16_t* xt_frag;
   const bf16_t* dtt_frag;
@@ -487,24 +488,42 @@ struct DwArgs2 {
 };
 static __global__ __launch_bounds__(64 * kDwWaves, 1) void bilinear_dw_kernel(DwArgs2 a2) {
   __shared__ float part[kDwWaves - 1][32][33];
+  // Both problem records and the two switches are read in ONE batch before anything depends on one of them, and the
+  // problem is picked with scalar selects (as bilinear_flash_kernel does): all 256 workgroups start together on a cold
+  // kernel-argument segment, and "pick a problem, then read its fields group by group" was five dependent scalar-load
+  // round trips in front of the first operand load.
+  kernarg_prefetch<(int)sizeof(DwArgs2)>();
   MI_WALL_SCOPE(kWallDw);
-  const int prob = (int)blockIdx.x >= a2.n_tiles0 ? 1 : 0;
-  const DwArgs& a = a2.p[prob];
-  const int64_t tile_id = prob ? (int64_t)blockIdx.x - a2.n_tiles0 : (int64_t)blockIdx.x;
+  MI_STAMP(0);
+  const DwArgs A = a2.p[0], Bp = a2.p[1];
+  const int n_tiles0 = a2.n_tiles0, natural = a2.natural;
+  asm volatile("" ::"s"(A.xt_frag), "s"(A.dtt_frag), "s"(A.dx), "s"(A.dy), "s"(A.k), "s"(A.out), "s"(Bp.xt_frag),
+               "s"(Bp.dtt_frag), "s"(Bp.dx), "s"(Bp.dy), "s"(Bp.k), "s"(Bp.out), "s"(n_tiles0), "s"(natural));
+  const bool prob = (int)blockIdx.x >= n_tiles0;
+  DwArgs a;
+  a.xt_frag = prob ? Bp.xt_frag : A.xt_frag;
+  a.dtt_frag = prob ? Bp.dtt_frag : A.dtt_frag;
+  a.dx = prob ? Bp.dx : A.dx;
+  a.dy = prob ? Bp.dy : A.dy;
+  a.k = prob ? Bp.k : A.k;
+  a.out = prob ? Bp.out : A.out;
   // (readfirstlane: the wave index must be a SCALAR for hipcc -- an MFMA ignores EXEC, so a matrix instruction under a
   // condition hipcc takes for divergent, and lowers to an EXEC mask without a skip branch, would still execute)
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int64_t nct = a.dy / 32, nat = a.dx / 32;
-  int64_t at = tile_id / nct, ct = tile_id % nct;
+  // The tile decode is 32-bit: a grid holds fewer than 2^31 tiles, so the tile id and both tile counts fit (64-bit
+  // operands made `/ nct` and `% nct` ~170 instructions of software division); only the addresses are widened.
+  const unsigned tile_id = prob ? blockIdx.x - (unsigned)n_tiles0 : blockIdx.x;
+  const unsigned nct = (unsigned)(a.dy >> 5), nat = (unsigned)(a.dx >> 5);
   // Workgroups go to the 8 XCDs round-robin (mi_common.h, xcd_decode): in row-major order XCD x gets tile columns
   // {x, x + 8, ...} of EVERY row, so each private L2 pulls all of X^T.  Give XCD x one (nat / 4) x (nct / 2) block of
   // tiles instead -- 4 x 8 at d = 512: a quarter of X^T and half of dT^T per XCD.  Which workgroup computes which tile
   // changes, the tile's arithmetic does not.  (A problem must start at a multiple of 8 for b % 8 to be its XCD.)
-  if (!a2.natural && nat % 4 == 0 && nct % 2 == 0 && (prob == 0 || a2.n_tiles0 % 8 == 0)) {
-    const int64_t xcd = tile_id & 7, i = tile_id >> 3, br = nat / 4, bc = nct / 2;
-    at = br * (xcd >> 1) + i / bc;
-    ct = bc * (xcd & 1) + i % bc;
-  }
+  // One division serves both orders: tile_id by nct (natural), or the tile's index within its XCD by the block's width.
+  const bool blocks = !natural && nat % 4 == 0 && nct % 2 == 0 && (!prob || n_tiles0 % 8 == 0);
+  const unsigned num = blocks ? tile_id >> 3 : tile_id, den = blocks ? nct / 2 : nct;
+  const unsigned quo = num / den, rem = num - quo * den;
+  const unsigned xcd = blocks ? tile_id & 7 : 0;  // natural order: both block offsets below are zero
+  const int64_t at = (nat / 4) * (xcd >> 1) + quo, ct = den * (xcd & 1) + rem;
   const int64_t nkb = a.k / 16;                 // 16-deep blocks over the batch
   const int64_t kb0 = nkb * wave / kDwWaves, kb1 = nkb * (wave + 1) / kDwWaves;
   const bf16_t* ap = a.xt_frag + ((at * nkb + kb0) * 64 + lane) * 8;
@@ -514,24 +533,27 @@ static __global__ __launch_bounds__(64 * kDwWaves, 1) void bilinear_dw_kernel(Dw
   for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
   constexpr int PF = 16;
   bf16x8 af[PF], bfr[PF];
-  const int64_t n = kb1 - kb0;
+  const int n = (int)(kb1 - kb0);  // (a wave's share of the batch: 32-bit, as are the clamps and tests on it)
 #pragma unroll
   for (int p = 0; p < PF; ++p) {
-    const int64_t q = p < n ? p : n - 1;
+    const int q = p < n ? p : n - 1;
     af[p] = *reinterpret_cast<const bf16x8*>(ap + q * 512);
     bfr[p] = *reinterpret_cast<const bf16x8*>(bp + q * 512);
   }
-  for (int64_t q0 = 0; q0 < n; q0 += PF) {
+  MI_STAMP(1);  // (stamped build: 0 entry, 1 first operand loads issued, 2 first MFMA, 3 last MFMA, 4 tile stored)
+  for (int q0 = 0; q0 < n; q0 += PF) {
 #pragma unroll
     for (int p = 0; p < PF; ++p) {
       if (q0 + p < n) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[p], bfr[p], acc, 0, 0, 0);
-      const int64_t q = q0 + p + PF;
+      if (q0 == 0 && p == 0) MI_STAMP(2);
+      const int q = q0 + p + PF;
       if (q < n) {
         af[p] = *reinterpret_cast<const bf16x8*>(ap + q * 512);
         bfr[p] = *reinterpret_cast<const bf16x8*>(bp + q * 512);
       }
     }
   }
+  MI_STAMP(3);
   // acc: column (lane & 31) = c, rows 8 g + 4 h + e = a
   const int r = lane & 31, h = lane >> 5;
   if (wave > 0) {
@@ -553,10 +575,16 @@ static __global__ __launch_bounds__(64 * kDwWaves, 1) void bilinear_dw_kernel(Dw
         seam_store<kSeam_DW>(&a.out[(at * 32 + row) * a.dy + ct * 32 + r], v);
       }
   }
+  MI_STAMP(4);
 }
 
 // one launch for up to two products (the separable critic's dWg and dWh); b == null: one
 static inline int launch_bilinear_dw(const DwArgs& a, hipStream_t st, const char* what, const DwArgs* b = nullptr) {
+  // (the kernel counts a wave's share of the batch, and the element offset of a 16-deep block in it, in 32 bits)
+  if (a.k >= ((int64_t)1 << 29) || (b && b->k >= ((int64_t)1 << 29))) {
+    set_error("%s: batch blocks of 2^29 rows and more are not supported", what);
+    return MI_ESHAPE;
+  }
   DwArgs2 a2{};
   a2.p[0] = a;
   a2.p[1] = b ? *b : a;
@@ -564,6 +592,9 @@ static inline int launch_bilinear_dw(const DwArgs& a, hipStream_t st, const char
   static const int natural = getenv("MI_DW_XCD_NATURAL") ? 1 : 0;  // A/B switch
   a2.natural = natural;
   const unsigned grid = (unsigned)(a2.n_tiles0 + (b ? (b->dx / 32) * (b->dy / 32) : 0));
+#ifdef MI_STAMPS
+  stamp_select(what, st);
+#endif
   {
     ProfScope prof_(what, st);
     hipLaunchKernelGGL(bilinear_dw_kernel, dim3(grid), dim3(64 * kDwWaves), 0, st, a2);

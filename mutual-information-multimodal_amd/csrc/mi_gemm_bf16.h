@@ -1771,9 +1771,17 @@ struct PrepTSecond {
   bf16_t* tb;
   bf16_t* tfb;
 };
-constexpr int kPrepTLdB = 160;  // W image row pitch in bf16 elements (128 columns + 32 of padding = 320 bytes)
-// dynamic LDS of a launch with tm-row T tiles: 77,824 bytes (128 rows), 59,392 (64 rows); two workgroups per CU either way
+// W image: 256-byte rows (128 columns, no padding), the four 64-byte chunks of row k stored at chunk index c ^ (k & 3).
+// A ds_read_b64_tr_b16 addresses four consecutive rows k0 .. k0 + 3 (k0 % 4 == 0) at one 64-byte chunk c: they land on
+// chunks c, c ^ 1, c ^ 2, c ^ 3 -- the four disjoint quarters of the 64 banks, the property the padded 320-byte pitch
+// had (rows 80 dwords apart: banks 0, 16, 32, 48), in 8 KB less per buffer.  A staging store writes whole rows: every
+// bank once per row, under either layout.
+constexpr int kPrepTLdB = 128;  // W image row pitch in bf16 elements
+constexpr int prep_t_w_swz(int k_row, int col_byte) { return col_byte ^ ((k_row & 3) << 6); }
+// dynamic LDS of a launch with tm-row T tiles: 69,632 bytes (128 rows: two workgroups per CU), 51,200 (64 rows: three)
 constexpr size_t prep_t_smem(int tm) { return (2 * tm * kG2LD + 2 * kG2KT * kPrepTLdB) * sizeof(bf16_t); }
+static_assert(3 * prep_t_smem(64) <= 160 * 1024, "the 64-row form runs three workgroups per CU: LDS must allow it");
+static_assert(2 * prep_t_smem(128) <= 160 * 1024, "the 128-row forms run two workgroups per CU");
 
 // XB16: x arrives as bf16 (a compile-time variant: as a run-time branch the second staging path cost the fp32 kernel 10
 // registers and 48 bytes of scratch)
@@ -1785,8 +1793,10 @@ constexpr size_t prep_t_smem(int tm) { return (2 * tm * kG2LD + 2 * kG2KT * kPre
 // conversion job that read X a second time for it is gone.  A 1 KB block (32 features x 16 rows, MFMA operand lane order)
 // is what the transposing ds_read_b64_tr_b16 returns from the row-major image; the column tiles of a row panel share
 // the k-steps round-robin (tile nb writes the steps t with t % (n / 128) == nb), so every block is written once.
+// Launch bounds follow the form: three workgroups per CU for the 64-row tiles (<= 168 registers: an edit that needs more
+// spills visibly instead of silently dropping to two), two for the 128-row ones.
 template <bool XB16, int TM = kTile, bool XTW = false>
-static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArgs a) {
+static __global__ __launch_bounds__(256, TM == 64 ? 3 : 2) void bilinear_prep_t_kernel(PrepTArgs a) {
   static_assert(TM == 64 || TM == 128, "T tiles have 64 or 128 rows");
   static_assert(!(XB16 && XTW), "the bf16 boundary keeps its X^T conversion job");
   constexpr int NTM = TM / 64;  // 32-row MFMA tiles per wave
@@ -1818,9 +1828,10 @@ static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArg
   // back on ONE XCD (xcd_decode), so its L2 fetches the panel once and keeps W.  (A 128 x 64 tiling with a 128-deep
   // k-step -- twice the tiles, half the round trips -- moved 96 MB instead of 64 and took 22.9 us instead of 16.4.)
   bf16_t* As = reinterpret_cast<bf16_t*>(smem_raw);  // [2][TM rows][72]: X as it lies, K-contiguous
-  bf16_t* Bs = As + 2 * TM * kG2LD;                  // [2][64 k][160]: W as it lies, n-contiguous; the B fragments come
-                                                     // out K-major through ds_read_b64_tr_b16 (320-byte rows: the four
-                                                     // rows of a transposed read fall on disjoint quarters of the banks)
+  bf16_t* Bs = As + 2 * TM * kG2LD;                  // [2][64 k][128]: W as it lies, n-contiguous; the B fragments come
+                                                     // out K-major through ds_read_b64_tr_b16 (swizzled 256-byte rows,
+                                                     // kPrepTLdB: the four rows of a transposed read fall on disjoint
+                                                     // quarters of the banks)
   // which product (the second one's blocks follow the first one's; both ranges are multiples of 8 long)
   const bool second = blk >= a.n_t;
   const float* const px = second ? a.x2 : a.x;
@@ -1839,7 +1850,11 @@ static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArg
   const int wk = tid >> 5, wc = tid & 31;  // W staging: k rows wk + 8 q of the slice, float4 number wc of the 128 columns
   // transposed read (guide T10): lane 4 q + p of a 16-lane group addresses row q, columns 4 p .. 4 p + 3 of a 4 x 16 block
   // and receives column (lane & 15) of its four rows; a lane's B fragment is rows 8 (lane >> 5) .. + 7 of column lane & 31
-  const int tr_off = (8 * half + ((lane >> 2) & 3)) * (kPrepTLdB * 2) + (wn * 64 + 16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
+  // The lane's row is 8 half + q (+ 16 kk, + 4 for the second read): row & 3 == q in every read, so the swizzle is a
+  // per-lane constant; the wave's second 32-column tile (tn = 1, +64 bytes before the swizzle) has its own.
+  const int tr_row = 8 * half + ((lane >> 2) & 3), tr_col = (wn * 64 + 16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
+  const int tr_off[2] = {tr_row * (kPrepTLdB * 2) + prep_t_w_swz(tr_row, tr_col),
+                         tr_row * (kPrepTLdB * 2) + prep_t_w_swz(tr_row, tr_col + 64)};
 
   f32x16 acc[NTM][2];
 #pragma unroll
@@ -1899,7 +1914,8 @@ static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArg
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const bf16x4 o = {(bf16_t)rw[q][0], (bf16_t)rw[q][1], (bf16_t)rw[q][2], (bf16_t)rw[q][3]};
-      *reinterpret_cast<bf16x4*>(&Bs[(buf * kG2KT + wk + 8 * q) * kPrepTLdB + 4 * wc]) = o;
+      // (row wk + 8 q: (row & 3) == (wk & 3), one swizzled column per thread)
+      *reinterpret_cast<bf16x4*>(reinterpret_cast<char*>(Bs + (buf * kG2KT + wk + 8 * q) * kPrepTLdB) + prep_t_w_swz(wk, 8 * wc)) = o;
     }
   };
 
@@ -1916,7 +1932,7 @@ static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArg
     const bool more = t + 1 < nt;
     if (more) load_tile((int64_t)(t + 1) * kG2KT);
     const bf16_t* at = As + buf * TM * kG2LD;
-    const char* bt = reinterpret_cast<const char*>(Bs + buf * kG2KT * kPrepTLdB) + tr_off;
+    const char* bt = reinterpret_cast<const char*>(Bs + buf * kG2KT * kPrepTLdB);
 #pragma unroll
     for (int kk = 0; kk < kG2KT / 16; ++kk) {
       bf16x8 af[NTM], bfr[2];
@@ -1926,7 +1942,7 @@ static __global__ __launch_bounds__(256, 2) void bilinear_prep_t_kernel(PrepTArg
 #pragma unroll
       for (int tn = 0; tn < 2; ++tn) {
         using lds_b4 = __attribute__((address_space(3))) bf16x4;
-        const char* pb = bt + kk * 16 * (kPrepTLdB * 2) + tn * 64;
+        const char* pb = bt + kk * 16 * (kPrepTLdB * 2) + tr_off[tn];
         const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(pb));
         const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(pb + 4 * (kPrepTLdB * 2)));
         bfr[tn] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};

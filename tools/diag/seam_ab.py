@@ -3,7 +3,7 @@
 B = 4096, d = 512, bf16, fp32 boundary, the seeded inputs of bench.py) through each library in alternating rounds.
 
     python tools/diag/seam_ab.py parent=/path/to/parent/libmi_critic_hip.so branch=mutual-information-multimodal_amd/lib/libmi_critic_hip.so
-        [--rounds 9] [--steps 200] [--profile-steps 20] [--batch 4096] [--dim 512]
+        [--rounds 9] [--steps 200] [--profile-rounds 3] [--profile-steps 20] [--batch 4096] [--dim 512]
 
 NAME=PATH@VAR=1,VAR2=x sets environment switches for that library alone (e.g. branch_nat=...so@MI_DW_XCD_NATURAL=1): the
 library reads such switches once, on its first launch, so they are set around that build's first steps only; the same file
@@ -13,7 +13,9 @@ Boxes differ by ~4 % and a profiled run by ~8 %, so only this kind of timing may
 the median / min / max over the rounds of the whole step (HIP events around --steps back-to-back calls) and the median
 per launch from the library's own profiling hook (mi_profile_begin / mi_profile_end, rounds of their own: the events
 between the launches cost time).  The first library is the reference of the bitwise comparison of every output, and of
-the verdict line: "<name> slowest round < <reference> fastest round".  One JSON line at the end.
+the verdict line: "<name> slowest round < <reference> fastest round".  Per launch it also prints the median of every
+profiled round and, against the first library, the gain over that library's own round-to-round spread (max - min of its
+round medians): a launch counts as faster when the gain exceeds three spreads.  One JSON line at the end.
 """
 import argparse
 import ctypes
@@ -60,7 +62,7 @@ class Build:
         self.args = (x.data_ptr(), y.data_ptr(), w.data_ptr(), sid.data_ptr(), b, d, d, _hip.MI_INFONCE, _hip.MI_PREC_BF16,
                      self.go.data_ptr(), self.loss.data_ptr(), self.stats.data_ptr(), self.record.data_ptr(),
                      self.gx.data_ptr(), self.gy.data_ptr(), self.gw.data_ptr(), self.ws.data_ptr(), self.ws.numel())
-        self.step_ms, self.launch_ms = [], {}
+        self.step_ms, self.launch_ms, self.launch_rounds = [], {}, {}
 
     def step(self):
         rc = self.lib.mi_bilinear_step(*self.args, torch.cuda.current_stream().cuda_stream)
@@ -89,8 +91,12 @@ class Build:
         n = ctypes.c_int(0)
         assert self.lib.mi_profile_end(names, len(names), ms, cap, ctypes.byref(n)) == 0
         parts = names.raw.split(b"\0")
+        this = {}
         for k in range(n.value):
             self.launch_ms.setdefault(parts[k].decode(), []).append(float(ms[k]))
+            this.setdefault(parts[k].decode(), []).append(float(ms[k]))
+        for k, v in this.items():
+            self.launch_rounds.setdefault(k, []).append(statistics.median(v) * 1e3)
 
     def outputs(self):
         torch.cuda.synchronize()
@@ -103,10 +109,17 @@ def main():
     p.add_argument("--rounds", type=int, default=9)
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--profile-steps", type=int, default=20)
+    p.add_argument("--profile-rounds", type=int, default=3)
     p.add_argument("--batch", type=int, default=4096)
     p.add_argument("--dim", type=int, default=512)
     a = p.parse_args()
     dev = torch.device("cuda:0")
+    # which box this is: rows of different boxes differ by 2-4 % and must not be compared with each other
+    import hashlib
+    import socket
+    prop = torch.cuda.get_device_properties(0)
+    box = hashlib.sha1((socket.gethostname() + str(getattr(prop, "uuid", ""))).encode()).hexdigest()[:8]
+    print(f"device: {prop.name}, box id {box} (hash of host name and device uuid)")
     x, y, sid = bench.make_inputs(a.batch, a.dim, a.dim, 3, 0, 1, dev)
     x, y = x.bfloat16().float().contiguous(), y.bfloat16().float().contiguous()  # as bench.py: bf16-representable values
     w = bench.make_critic("bilinear", a.dim, a.dim, 3, dev).weight.detach().float().contiguous()
@@ -132,19 +145,29 @@ def main():
     for r in range(a.rounds):
         for bd in (builds if r % 2 == 0 else builds[::-1]):
             bd.timed(a.steps)
-    for r in range(3):
-        for bd in builds:
+    for r in range(a.profile_rounds):
+        for bd in (builds if r % 2 == 0 else builds[::-1]):
             bd.profiled(a.profile_steps)
 
-    out = {"shape": [a.batch, a.dim], "rounds": a.rounds, "steps": a.steps, "bits_equal": same, "builds": {}}
+    out = {"box": box, "shape": [a.batch, a.dim], "rounds": a.rounds, "steps": a.steps, "bits_equal": same, "builds": {}}
     base = builds[0]
     for bd in builds:
         t = bd.step_ms
         per = {k: round(statistics.median(v) * 1e3, 2) for k, v in bd.launch_ms.items()}
         out["builds"][bd.name] = {"step_us_median": round(statistics.median(t) * 1e3, 2), "step_us_min": round(min(t) * 1e3, 2),
-                                  "step_us_max": round(max(t) * 1e3, 2), "launch_us_median": per}
+                                  "step_us_max": round(max(t) * 1e3, 2), "step_us_rounds": [round(v * 1e3, 2) for v in t],
+                                  "launch_us_median": per,
+                                  "launch_us_rounds": {k: [round(x, 2) for x in v] for k, v in bd.launch_rounds.items()}}
         print(f"{bd.name:14s} step median {statistics.median(t) * 1e3:8.2f} us  min {min(t) * 1e3:8.2f}  max {max(t) * 1e3:8.2f}"
               f"   launches {per}")
+    for k, v in base.launch_rounds.items():
+        spread = max(v) - min(v)
+        print(f"{k}: {base.name} round medians {min(v):.2f} .. {max(v):.2f} us (spread {spread:.2f})")
+        for bd in builds[1:]:
+            w = bd.launch_rounds.get(k)
+            if w:
+                gain = statistics.median(v) - statistics.median(w)
+                print(f"    {bd.name}: {min(w):.2f} .. {max(w):.2f} us, gain {gain:+.2f} us = {gain / spread if spread > 0 else float('inf'):+.1f} spreads")
     for bd in builds[1:]:
         ok = max(bd.step_ms) < min(base.step_ms)
         out["builds"][bd.name]["slowest_below_reference_fastest"] = ok
