@@ -283,6 +283,25 @@ int mi_concat_mlp_bwd(const float* x, const float* y, const float* w1, const flo
                       const float* grad_out, const float* scores /* [b_rows,b] from fwd */, float* grad_x,
                       float* grad_y, float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2,
                       float* grad_w3, float* grad_b3, void* workspace, size_t workspace_bytes, void* stream);
+/* The critic as a differentiable score matrix: any loss on S, written in any framework, trains it on the fused kernels.
+ * The forward runs the score kernels alone (no study ids, no reduction, no loss) and writes scores_out [b_rows, b],
+ * b_rows <= b, local row i being sample i; with need_grad it leaves the sign-bit images and operand copies in the
+ * workspace (mi_concat_mlp_workspace_bytes) as the forward above does.  The backward takes grad_scores = dL/dS [b_rows, b]
+ * -- dropped pairs are whatever the caller put there, normally 0 -- and the workspace of a forward made with need_grad = 1
+ * (MI_EWORKSPACE otherwise), and writes the eight gradients.  stats_scratch: 64 bytes of device memory the call overwrites
+ * (max|grad_scores|, from which the fp16 modes derive the power-of-two scale of g; 0 or a non-finite maximum: scale 1).
+ * Deterministic: fixed reduction orders, no float atomics. */
+int mi_concat_mlp_scores_fwd(const float* x, const float* y, const float* w1, const float* b1, const float* w2,
+                             const float* b2, const float* w3, const float* b3, int64_t b_rows, int64_t b,
+                             int64_t d_img, int64_t d_txt, int64_t h1, int64_t h2, int precision, int need_grad,
+                             float* scores_out /* [b_rows,b] */, void* workspace, size_t workspace_bytes, void* stream);
+int mi_concat_mlp_bwd_from_g(const float* x, const float* y, const float* w1, const float* b1, const float* w2,
+                             const float* b2, const float* w3, const float* b3, int64_t b_rows, int64_t b,
+                             int64_t d_img, int64_t d_txt, int64_t h1, int64_t h2, int precision,
+                             const float* grad_scores /* [b_rows,b] */, mi_stats* stats_scratch /* 64 bytes */,
+                             float* grad_x, float* grad_y, float* grad_w1, float* grad_b1, float* grad_w2,
+                             float* grad_b2, float* grad_w3, float* grad_b3, void* workspace, size_t workspace_bytes,
+                             void* stream);
 
 /* ---- cross-rank merge of per-rank partial statistics (global-batch negatives) -------- */
 /* partials [n_ranks][4] = (neg_max, sum exp(s - neg_max), sum of positives, n_neg as float pair) gathered in

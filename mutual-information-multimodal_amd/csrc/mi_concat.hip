@@ -192,7 +192,8 @@ static int launch_concat_fwd(const float* u, const float* v, const OpT* w2, cons
 }
 
 // OpT = float (exact fp32 products), bf16_t, or f16_t (mi_concat_f16.h: scaled fp16 operands, packed generation).
-// R: gradient rule of the bound (mi_fdiv.h): kGradDV for DV / "infonce" / NWJ, kGradJSD for the Jensen-Shannon bound.
+// R: gradient rule of the bound (mi_fdiv.h): kGradDV for DV / "infonce" / NWJ, kGradJSD for the Jensen-Shannon bound,
+// kGradGiven for a caller's dL/dS (then `scores` holds it, sid_rows / sid_cols are null and never read).
 template <typename OpT, bool X3 = false, int R = kGradDV>
 static int concat_bwd_impl(const float* x, const float* y, const float* w1, const float* w2, const float* b2,
                            const float* w3, const int64_t* sid_rows, const int64_t* sid_cols, int64_t br, int64_t b,
@@ -554,6 +555,60 @@ int mi_concat_mlp_bwd(const float* x, const float* y, const float* w1, const flo
   return concat_bwd_dispatch<kGradDV>(x, y, w1, w2, b2, w3, sid_rows, sid_cols, b_rows, b, row_offset, d_img, d_txt,
                                       (int)h1, (int)h2, precision, stats, grad_out, scores, grad_x, grad_y, grad_w1,
                                       grad_b1, grad_w2, grad_b2, grad_w3, grad_b3, p, (hipStream_t)stream);
+}
+
+// ---- the critic as a differentiable [b_rows, b] score matrix: the forward without a bound, the backward from any dL/dS
+// (gradient rule kGradGiven: the kernels read g from the matrix they otherwise read the scores from)
+int mi_concat_mlp_scores_fwd(const float* x, const float* y, const float* w1, const float* b1, const float* w2,
+                             const float* b2, const float* w3, const float* b3, int64_t b_rows, int64_t b, int64_t d_img,
+                             int64_t d_txt, int64_t h1, int64_t h2, int precision, int need_grad, float* scores_out,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && w1 && b1 && w2 && b2 && w3 && b3 && scores_out && workspace,
+               "mi_concat_mlp_scores_fwd: null pointer");
+  int rc = check_concat_shape("mi_concat_mlp_scores_fwd", b_rows, b, 0, d_img, d_txt, h1, h2, precision);
+  if (rc) return rc;
+  Workspace ws(workspace, workspace_bytes);
+  ConcatPlan p = plan_concat(ws, b_rows, b, h1, h2, precision, need_grad, d_img > d_txt ? d_img : d_txt);
+  rc = ws_fits(ws, "mi_concat_mlp_scores_fwd");
+  if (rc) return rc;
+  return concat_fwd_scores(x, y, w1, b1, w2, b2, w3, b3, b_rows, b, d_img, d_txt, h1, h2, precision, need_grad, scores_out,
+                           p, (hipStream_t)stream);
+}
+
+int mi_concat_mlp_bwd_from_g(const float* x, const float* y, const float* w1, const float* b1, const float* w2,
+                             const float* b2, const float* w3, const float* b3, int64_t b_rows, int64_t b, int64_t d_img,
+                             int64_t d_txt, int64_t h1, int64_t h2, int precision, const float* grad_scores,
+                             mi_stats* stats_scratch, float* grad_x, float* grad_y, float* grad_w1, float* grad_b1,
+                             float* grad_w2, float* grad_b2, float* grad_w3, float* grad_b3, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+  (void)b1;
+  (void)b3;
+  MI_CHECK_ARG(x && y && w1 && w2 && b2 && w3 && grad_scores && stats_scratch && grad_x && grad_y && grad_w1 && grad_b1 &&
+                   grad_w2 && grad_b2 && grad_w3 && grad_b3 && workspace,
+               "mi_concat_mlp_bwd_from_g: null pointer");
+  int rc = check_concat_shape("mi_concat_mlp_bwd_from_g", b_rows, b, 0, d_img, d_txt, h1, h2, precision);
+  if (rc) return rc;
+  Workspace ws(workspace, workspace_bytes);
+  ConcatPlan p = plan_concat(ws, b_rows, b, h1, h2, precision, 1, d_img > d_txt ? d_img : d_txt);
+  rc = ws_fits(ws, "mi_concat_mlp_bwd_from_g", ": pass the workspace of the forward call made with need_grad = 1");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  // max|G| -> the statistics block (the fp16 modes' scale of g) together with the device-resident grad_out = 1.  The
+  // partial maxima borrow the head of col_part (64 x h1 floats, written next by the last launches of the backward).
+  static_assert(kGivenAbsmaxBlocks <= 64 * 64, "col_part holds at least 64 x 64 words");
+  unsigned* part = reinterpret_cast<unsigned*>(p.col_part);
+  {
+    ProfScope prof_("given absmax G", st);
+    hipLaunchKernelGGL(given_absmax_partial_kernel, dim3(kGivenAbsmaxBlocks), dim3(256), 0, st, grad_scores, b_rows * b,
+                       part);
+    hipLaunchKernelGGL(given_absmax_final_kernel, dim3(1), dim3(64), 0, st, (const unsigned*)part, kGivenAbsmaxBlocks,
+                       stats_scratch);
+  }
+  MI_LAUNCH_CHECK("given_absmax_kernel");
+  return concat_bwd_dispatch<kGradGiven>(x, y, w1, w2, b2, w3, nullptr, nullptr, b_rows, b, 0, d_img, d_txt, (int)h1,
+                                         (int)h2, precision, stats_scratch, &stats_scratch->reserved1, grad_scores, grad_x,
+                                         grad_y, grad_w1, grad_b1, grad_w2, grad_b2, grad_w3, grad_b3, p,
+                                         (hipStream_t)stream);
 }
 
 // ---- Jensen-Shannon and NWJ bounds (mi_fdiv.h): the same scores and sign-bit images, the fdiv reduction; the backward

@@ -19,10 +19,16 @@ namespace mi {
 
 // d loss / d score of pair (global row gi, column gj) times grad_out; 0 for dropped / out-of-range pairs.  R: the gradient
 // rule (mi_fdiv.h).  kGradDV serves DV, the reference's "infonce" and NWJ (whose statistics block holds lse = 1 + log
-// n_neg); kGradJSD: gpos sigma(-s) and gneg sigma(s), gneg = go / n_neg (fdiv_gneg).
+// n_neg); kGradJSD: gpos sigma(-s) and gneg sigma(s), gneg = go / n_neg (fdiv_gneg); kGradGiven: `score` is the caller's
+// dL/dS of the pair (the kernels' S argument holds that matrix), returned times go -- dropped pairs are whatever the
+// caller put there.
 template <int R = kGradDV>
 __device__ __forceinline__ float pair_grad(float score, int64_t gi, int64_t gj, int64_t sid_i, int64_t sid_j, float lse,
                                            float go, float gpos, float gneg = 0.0f) {
+  if constexpr (R == kGradGiven) {
+    (void)gi, (void)gj, (void)sid_i, (void)sid_j, (void)lse, (void)gpos, (void)gneg;
+    return go * score;
+  }
   const int kind = pair_kind(gi, gj, sid_i, sid_j);
   if constexpr (R == kGradJSD) {
     (void)lse;
@@ -36,6 +42,12 @@ __device__ __forceinline__ float pair_grad(float score, int64_t gi, int64_t gj, 
     if (kind == 2) return go * expf(score - lse);
     return 0.0f;
   }
+}
+// study id of sample i for pair_grad<R>; the given-g rule has no ids (its callers pass null arrays): nothing is read
+template <int R>
+__device__ __forceinline__ int64_t pair_sid(const int64_t* sid, int64_t i) {
+  if constexpr (R == kGradGiven) return 0;
+  else return sid[i];
 }
 // the negative-pair weight of the JSD rule for the kernel's grad_out factor go (0, unused, under the DV rule)
 template <int R>
@@ -97,8 +109,11 @@ __device__ __forceinline__ F16ScaleSet f16_scales(const F16Scales* sc) {
   r.s_uv3 = f16_pow2_scale(au + av, 13);
   return r;
 }
+// Under the given-g rule the statistics block is the one given_absmax_final_kernel wrote: max|G| sits in reserved0 (0 or
+// a non-finite value: scale 1) and the device-resident grad_out = 1.0f in reserved1.
 template <int R = kGradDV>
 __device__ __forceinline__ float f16_g_scale(const mi_stats* st, int lo_exp) {
+  if constexpr (R == kGradGiven) return f16_pow2_scale(st->reserved0, lo_exp);
   if constexpr (R == kGradJSD)  // n_neg == 0: 1 / 0 = inf, scale 1
     return f16_pow2_scale(fmaxf(1.0f / (float)st->n_pos, 1.0f / (float)st->n_neg), lo_exp);
   const float gneg = expf(st->neg_max - st->lse);  // neg_max = -inf (no negatives): 0
@@ -253,7 +268,8 @@ __global__ __launch_bounds__(512) void concat_bwd_duv_kernel(
       const int64_t li = i0 + il, gj = j + jl;
       float g = 0.0f;
       if (li < b_rows && gj < jhi)
-        g = gscale * pair_grad<R>(S[li * b + gj], row_offset + li, gj, sid_rows[li], sid_cols[gj], lse, go, gpos, gneg);
+        g = gscale * pair_grad<R>(S[li * b + gj], row_offset + li, gj, pair_sid<R>(sid_rows, li),
+                                      pair_sid<R>(sid_cols, gj), lse, go, gpos, gneg);
       gs[il * kDuvTJ + jl] = g;
       for (int e = tid; e < kDuvTJ * KC; e += 512) {
         const int jl2 = e / KC, kk = e % KC;
@@ -450,7 +466,8 @@ __global__ __launch_bounds__(512) void concat_bwd_dw2_kernel(
         const int64_t li = ib + il, gj = j0 + jl;
         float g = 0.0f;
         if (li < ihi && gj < b)
-          g = gscale * pair_grad<R>(S[li * b + gj], row_offset + li, gj, sid_rows[li], sid_cols[gj], lse, go, gpos, gneg);
+          g = gscale * pair_grad<R>(S[li * b + gj], row_offset + li, gj, pair_sid<R>(sid_rows, li),
+                                      pair_sid<R>(sid_cols, gj), lse, go, gpos, gneg);
         gs[e] = g;
       }
       __syncthreads();
@@ -595,10 +612,11 @@ __global__ __launch_bounds__(512) void concat_bwd_db2_kernel(const unsigned* __r
   float macc[2] = {0.0f, 0.0f};  // hidden units tid and tid + 512
   for (int64_t li = ilo; li < ihi; ++li) {
     __syncthreads();
-    const int64_t si = sid_rows[li];
+    const int64_t si = pair_sid<R>(sid_rows, li);
     for (int64_t gj = tid; gj < JB * 32; gj += 512) {
       float g = 0.0f;
-      if (gj < b) g = pair_grad<R>(S[li * b + gj], row_offset + li, gj, si, sid_cols[gj], lse, go, gpos, gneg);
+      if (gj < b)
+        g = pair_grad<R>(S[li * b + gj], row_offset + li, gj, si, pair_sid<R>(sid_cols, gj), lse, go, gpos, gneg);
       grow[gj] = g;
       gtot += g;
     }

@@ -68,6 +68,48 @@ static __global__ __launch_bounds__(256) void f16_absmax_kernel(F16AbsmaxJobs J)
   }
 }
 
+// max|G| of the caller's dL/dS [n] for the given-g rule (kGradGiven), in two launches without atomics: kGivenAbsmaxBlocks
+// workgroups write one partial each, then one wave folds them in a fixed order and writes the WHOLE 64-byte statistics
+// block the backward kernels read: reserved0 = max|G| (f16_g_scale<kGradGiven>), reserved1 = 1.0f (the device-resident
+// grad_out), n_pos = n_neg = 1, everything else 0.  The maximum is taken over the bit patterns of |g| as unsigned
+// integers: finite values order as their magnitudes and a NaN or an infinity anywhere in G comes out on top, so the
+// scale falls back to 1 (f16_pow2_scale) instead of being derived from the finite rest.
+constexpr int kGivenAbsmaxBlocks = 256;
+static __global__ __launch_bounds__(256) void given_absmax_partial_kernel(const float* __restrict__ g, int64_t n,
+                                                                         unsigned* __restrict__ part) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  unsigned m = 0u;
+  if ((n & 3) == 0 && ((uintptr_t)g & 15) == 0) {
+    const u32x4* g4 = reinterpret_cast<const u32x4*>(g);
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n / 4; e += stride) {
+      const u32x4 v = g4[e] & 0x7FFFFFFFu;
+      m = max(max(m, max(v[0], v[1])), max(v[2], v[3]));
+    }
+  } else {
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += stride)
+      m = max(m, __float_as_uint(g[e]) & 0x7FFFFFFFu);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
+  __shared__ unsigned red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = max(max(red[0], red[1]), max(red[2], red[3]));
+}
+static __global__ __launch_bounds__(64) void given_absmax_final_kernel(const unsigned* __restrict__ part, int n_part,
+                                                                      mi_stats* __restrict__ stats) {
+  unsigned m = 0u;
+  for (int k = threadIdx.x; k < n_part; k += 64) m = max(m, part[k]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
+  if (threadIdx.x != 0) return;
+  stats->lse = stats->pos_mean = stats->loss_dv = stats->loss_infonce = stats->log_n_neg = stats->neg_max = 0.0f;
+  stats->reserved0 = __uint_as_float(m);
+  stats->reserved1 = 1.0f;
+  stats->n_neg = stats->n_pos = 1;
+  stats->reserved2 = stats->reserved3 = 0;
+}
+
 // Uh, Vh, W2h (forward operands) and, when the backward will run, Upk[i][k] = {Uh, Uh} (one dword per element: the dW2
 // kernel adds it to a PAIR of columns) and VhT [H1][b] (the dW2 kernel stages [k][column] tiles).
 struct F16PrepArgs {
@@ -615,7 +657,8 @@ __global__ __launch_bounds__(512) void concat_bwd_dw2_f16_kernel(
         const int64_t li = ib + il, gj = j0 + jl;
         float g = 0.0f;
         if (li < ihi && gj < b)
-          g = gscale * pair_grad<R>(S[li * b + gj], row_offset + li, gj, sid_rows[li], sid_cols[gj], lse, 1.0f, gpos, gneg);
+          g = gscale * pair_grad<R>(S[li * b + gj], row_offset + li, gj, pair_sid<R>(sid_rows, li),
+                                      pair_sid<R>(sid_cols, gj), lse, 1.0f, gpos, gneg);
         gs[e] = (f16_t)g;
       }
       __syncthreads();
@@ -744,10 +787,11 @@ __global__ __launch_bounds__(512) void concat_bwd_db2_f16_kernel(const unsigned*
   float macc[2] = {0.0f, 0.0f};  // hidden units tid and tid + 512
   for (int64_t li = ilo; li < ihi; ++li) {
     __syncthreads();
-    const int64_t si = sid_rows[li];
+    const int64_t si = pair_sid<R>(sid_rows, li);
     for (int64_t gj = tid; gj < JB * 32; gj += 512) {
       float g = 0.0f;
-      if (gj < b) g = pair_grad<R>(S[li * b + gj], row_offset + li, gj, si, sid_cols[gj], lse, 1.0f, gpos, gneg);
+      if (gj < b)
+        g = pair_grad<R>(S[li * b + gj], row_offset + li, gj, si, pair_sid<R>(sid_cols, gj), lse, 1.0f, gpos, gneg);
       grow[gj] = (f16_t)(g * gscale);
       gtot += g;
     }
@@ -907,7 +951,7 @@ __global__ __launch_bounds__(256, 2) void concat_bwd_duv3_kernel(
   }
   const int64_t grow = lrow[h];  // the pair whose g this lane COMPUTES: tile m = h, row c of it
   const bool grow_ok = lrow_ok[h];
-  const int64_t gsid = sid_rows[grow];
+  const int64_t gsid = pair_sid<R>(sid_rows, grow);
   auto load_words = [&](unsigned long long (&w)[2][4], int pw, int64_t jw) __attribute__((always_inline)) {
     int64_t gj = jw + (c & 3);
     if (gj >= b) gj = b - 1;
@@ -924,7 +968,7 @@ __global__ __launch_bounds__(256, 2) void concat_bwd_duv3_kernel(
     const int64_t gj = jlo + (c & 3);
     if (grow_ok && gj < jhi) {
       s_next = S[grow * b + gj];
-      sidc_next = sid_cols[gj];
+      sidc_next = pair_sid<R>(sid_cols, gj);
     }
   }
   __syncthreads();
@@ -940,7 +984,7 @@ __global__ __launch_bounds__(256, 2) void concat_bwd_duv3_kernel(
       const int64_t gjn = gj + kDuv3TJ;
       if (grow_ok && gjn < jhi) {
         s_next = S[grow * b + gjn];
-        sidc_next = sid_cols[gjn];
+        sidc_next = pair_sid<R>(sid_cols, gjn);
       }
     }
     // ---- E[pair, k] = sum_n M[pair, n] W2w[n, k] on MFMA ------------------------------------------------------------

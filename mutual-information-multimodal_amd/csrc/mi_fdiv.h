@@ -30,6 +30,9 @@ __device__ __forceinline__ float fdiv_sigmoid(float x) {
 // gradient rules of the bound kernels (template argument of the concat-MLP backward kernels)
 constexpr int kGradDV = 0;   // DV, the reference's "infonce" and NWJ (normaliser from the statistics block)
 constexpr int kGradJSD = 1;  // Jensen-Shannon: sigma(-s) / n_pos, sigma(s) / n_neg
+// g is given: the kernels' score-matrix argument holds the caller's dL/dS [b_rows, b]; no pair kinds, no study ids, no
+// exponential (mi_concat_mlp_bwd_from_g)
+constexpr int kGradGiven = 2;
 
 // d loss / d score of one pair of kind 1 (positive) / 2 (negative) / 0 (dropped), given the mode's constants
 struct FdivGrad {

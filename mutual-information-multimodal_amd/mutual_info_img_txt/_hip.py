@@ -151,6 +151,8 @@ SIGNATURES = {
     "mi_concat_mlp_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I64, _I64, _I, _I]),
     "mi_concat_mlp_fwd": (c_int, [_P] * 10 + [_I64] * 7 + [_I, _I, _I] + [_P] * 5 + [_SZ, _P]),
     "mi_concat_mlp_bwd": (c_int, [_P] * 10 + [_I64] * 7 + [_I] + [_P] * 12 + [_SZ, _P]),
+    "mi_concat_mlp_scores_fwd": (c_int, [_P] * 8 + [_I64] * 6 + [_I, _I] + [_P] * 2 + [_SZ, _P]),
+    "mi_concat_mlp_bwd_from_g": (c_int, [_P] * 8 + [_I64] * 6 + [_I] + [_P] * 11 + [_SZ, _P]),
     "mi_merge_partials": (c_int, [_P, _I64, _I64, _I, _P, _P, _P]),
     "mi_nce_bilinear_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I]),
     "mi_nce_bilinear_step": (c_int, [_P] * 4 + [_I64] * 3 + [_I, _I] + [_P] * 8 + [_SZ, _P]),

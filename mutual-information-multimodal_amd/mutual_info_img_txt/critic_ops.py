@@ -23,14 +23,17 @@ def _precision_code(precision: str) -> int:
     return PRECISIONS[precision]
 
 
+NOT_MAKE_MLP = ("the fused concat-MLP path supports make_mlp(input_dim, [h1, h2]) critics "
+                "(Linear-ReLU-Linear-ReLU-Linear(->1)); use create_mi_pairs + the critic module otherwise")
+
+
 def _concat_params(critic):
     """(W1,b1,W2,b2,W3,b3) of an nn.Sequential built by make_mlp(input_dim,[h1,h2]) (reference model.py:18-32)."""
     mods = list(critic)
     lin = [m for m in mods if isinstance(m, torch.nn.Linear)]
     act = [m for m in mods if not isinstance(m, torch.nn.Linear)]
     if len(lin) != 3 or len(mods) != 5 or not all(isinstance(a, torch.nn.ReLU) for a in act) or lin[2].out_features != 1:
-        raise ValueError("the fused concat-MLP path supports make_mlp(input_dim, [h1, h2]) critics "
-                         "(Linear-ReLU-Linear-ReLU-Linear(->1)); use create_mi_pairs + the critic module otherwise")
+        raise ValueError(NOT_MAKE_MLP)
     return lin[0].weight, lin[0].bias, lin[1].weight, lin[1].bias, lin[2].weight, lin[2].bias
 
 
@@ -701,5 +704,31 @@ class HipConcatMlpOps(_HipOps):
                   scores.data_ptr(), gx.data_ptr(), gy.data_ptr(), *[g.data_ptr() for g in gp], ws.data_ptr(), ws.numel())
         return gx, gy, gp
 
+    # ---------------------------------------------- the critic as a differentiable score matrix (fused_scores.py)
+    def scores_forward(self, x, y_all, params, precision, need_grad):
+        """(scores [b_rows, b], saved) of the rows ``x`` against all of ``y_all`` (mi_concat_mlp_scores_fwd: the score
+        kernels alone, no study ids and no loss); ``saved`` = (x, y_all, params, precision, ws) for ``scores_backward``,
+        which needs ``need_grad``."""
+        flags = int(bool(need_grad))
+        ws = _hip.workspace(self.workspace_bytes(x.shape[0], y_all.shape[0], x.shape[1], y_all.shape[1], params, precision,
+                                                 flags), x.device)
+        scores = self._scores(x, y_all)
+        _hip.call("mi_concat_mlp_scores_fwd", x.device, x.data_ptr(), y_all.data_ptr(), *[p.data_ptr() for p in params],
+                  x.shape[0], y_all.shape[0], x.shape[1], y_all.shape[1], params[0].shape[0], params[2].shape[0], precision,
+                  flags, scores.data_ptr(), ws.data_ptr(), ws.numel())
+        return scores, (x, y_all, list(params), precision, ws)
 
-OPS = {"bilinear": HipBilinearOps, "separable": HipSeparableOps, "concat_mlp": HipConcatMlpOps}
+    def scores_backward(self, saved, grad_scores):
+        """(grad_x, grad_y, [grad_params...]) of sum(grad_scores * scores) for a contiguous float32 ``grad_scores``
+        [b_rows, b] (mi_concat_mlp_bwd_from_g).  The workspace is read, not consumed: the call can be repeated."""
+        x, y, params, precision, ws = saved
+        gx, gy, gp = torch.empty_like(x), torch.empty_like(y), [torch.empty_like(p) for p in params]
+        stats = _hip.new_stats(x.device)  # scratch of the call: max|grad_scores| and the kernels' grad_out = 1
+        _hip.call("mi_concat_mlp_bwd_from_g", x.device, x.data_ptr(), y.data_ptr(), *[p.data_ptr() for p in params],
+                  x.shape[0], y.shape[0], x.shape[1], y.shape[1], params[0].shape[0], params[2].shape[0], precision,
+                  grad_scores.data_ptr(), stats.data_ptr(), gx.data_ptr(), gy.data_ptr(),
+                  *[g.data_ptr() for g in gp], ws.data_ptr(), ws.numel())
+        return gx, gy, gp
+
+
+OPS ={"bilinear": HipBilinearOps, "separable": HipSeparableOps, "concat_mlp": HipConcatMlpOps}

@@ -102,8 +102,9 @@ def hard_negative_infonce(embedding_img: torch.Tensor, embedding_txt: torch.Tens
     with the ids (image -> report; in the symmetric mode also report -> image), a small kernel that forms the loss from
     the lists, and -- when an input needs a gradient -- the G GEMM whose epilogue keeps G on the lists and the diagonal
     followed by the backward products of the per-sample InfoNCE.  The backward pass only scales the saved gradients.  A
-    ``make_mlp`` critic has no GEMM form and raises ValueError: apply it to the pairs yourself and call
-    ``matrix_hard_negative_infonce(scores, study_id, k)``.
+    ``make_mlp`` critic has no GEMM form and raises ValueError: take its differentiable score matrix from
+    ``fused_scores.fused_critic_scores`` (the fused kernels, no pair matrix) and call
+    ``matrix_hard_negative_infonce(scores, study_id, k)`` -- ``fused_scores.concat_hard_negative_infonce`` does both.
 
     ``k`` in [1, 32].  ``precision`` as for the per-sample InfoNCE of ``fused_mi_bound``: "f32" (bf16x3 on the bilinear
     critic where every size is a multiple of 8, exact fp32 products otherwise), "f32_exact", "bf16", "bf16x3"; "fp8",

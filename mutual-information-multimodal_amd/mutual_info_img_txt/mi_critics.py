@@ -290,7 +290,8 @@ def fused_mi_bound(embedding_img: torch.Tensor, embedding_txt: torch.Tensor, stu
     ``estimator`` = "infonce_rowwise" / "infonce_symmetric" (BilinearCritic, SeparableCritic): the per-sample InfoNCE
     (DESIGN.md section 8), loss of shape [], precisions "f32" / "f32_exact" / "bf16" / "bf16x3";
     ``return_stats=True`` then gives ``(lse_rows, lse_cols)``, the row and column log-sum-exps.  A make_mlp critic raises
-    ValueError: apply it to the pairs yourself and call ``matrix_bound_loss(scores, study_id, estimator)``.
+    ValueError: take its differentiable score matrix from ``fused_scores.fused_critic_scores`` (the fused kernels, no pair
+    matrix) and call ``matrix_bound_loss(scores, study_id, estimator)`` -- ``fused_scores.concat_infonce`` does both.
 
     ``estimator`` = "jsd" / "nwj" (every critic): the Jensen-Shannon and NWJ bounds, loss of shape
     []; ``return_stats=True`` then gives ``(positive-pair term, negative-pair term)``, two 0-d tensors whose sum is the loss.

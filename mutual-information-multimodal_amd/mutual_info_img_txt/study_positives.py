@@ -99,8 +99,9 @@ def study_positive_infonce(embedding_img: torch.Tensor, embedding_txt: torch.Ten
     whose epilogue writes the row / column records (LSE parts over every column, sums and counts over the same-study
     ones), the merge, the loss, and -- when an input needs a gradient -- the G GEMM whose epilogue applies the formula
     above, followed by the backward products of the per-sample InfoNCE.  The backward pass only scales the saved
-    gradients.  A ``make_mlp`` critic has no GEMM form and raises ValueError: apply it to the pairs yourself and call
-    ``matrix_study_positive_infonce(scores, study_id)``.
+    gradients.  A ``make_mlp`` critic has no GEMM form and raises ValueError: take its differentiable score matrix from
+    ``fused_scores.fused_critic_scores`` (the fused kernels, no pair matrix) and call
+    ``matrix_study_positive_infonce(scores, study_id)`` -- ``fused_scores.concat_study_positive_infonce`` does both.
 
     ``precision`` as for the per-sample InfoNCE of ``fused_mi_bound``: "f32" (bf16x3 on the bilinear critic where every
     size is a multiple of 8, exact fp32 products otherwise), "f32_exact", "bf16", "bf16x3"; "fp8", "f16" and "f16x3"
