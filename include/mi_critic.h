@@ -26,6 +26,9 @@
  *                            gallery (n_img != n_txt allowed), optionally without equal-id candidates; an evaluation too
  *   mi_posnce_*, mi_matrix_posnce_* <- an extension: the per-sample InfoNCE with every same-study pair as a positive
  *                            (the dataset pairs each image with its study's report, so such pairs are true matches)
+ *   mi_softnce_*, mi_matrix_softnce_* <- an extension: the per-sample InfoNCE with soft targets from the CheXpert /
+ *                            NegBio finding labels of the dataset's label table (the reference ships the table; no
+ *                            loss of it reads it)
  *
  * Conventions
  *   - every pointer is a DEVICE pointer unless the name ends in _host; all tensors are dense row-major
@@ -631,6 +634,64 @@ int mi_matrix_posnce_fwd(const float* scores, const int64_t* sid, int64_t b, int
 int mi_matrix_posnce_bwd(const float* scores, const int64_t* sid, int64_t b, int mode, const float* lse_rows,
                          const float* lse_cols, const int32_t* n_pos, const float* grad_out, float* grad_scores,
                          void* stream);
+
+/* ---- soft-target InfoNCE from finding-label bit masks --------------------------------------- */
+/* The row-wise / symmetric InfoNCE with soft targets: the target distribution of row i puts weight on every report in
+ * proportion to how similar its finding set is to that of image i (SoftCLIP, label-aware contrast).  Batch x [b, d_img],
+ * y [b, d_txt], one label mask per sample label_mask [b] (int64; the low MI_SOFTNCE_MAX_LABELS bits are a multi-hot set
+ * of findings; bit 63 cannot be checked on the host and is IGNORED -- masked off -- on the device), floats tau > 0 and
+ * mix in [0, 1]; no study ids.  S[i, j] = critic(img_i, txt_j):
+ *   n_i   = popcount(lab_i)
+ *   a_ij  = popcount(lab_i & lab_j) / sqrt(n_i n_j)   (0 where n_i n_j = 0);  a_ii := 1 always
+ *   k_ij  = exp((a_ij - 1) / tau)                      (<= 1, k_ii = 1, k_ij == k_ji bit for bit)
+ *   z_i   = sum_j k_ij                                 (>= 1; serves rows and, k being symmetric, columns)
+ *   qr_ij = (1 - mix) delta_ij + mix k_ij / z_i        qc_ij = (1 - mix) delta_ij + mix k_ij / z_j
+ *   r_i = log sum_{j < b} exp S[i, j],  c_j = log sum_{i < b} exp S[i, j]                     (nothing is masked)
+ *   row term t_i = r_i - sum_j qr_ij S[i, j],  column term t'_j = c_j - sum_i qc_ij S[i, j]
+ *   MI_NCE_ROWWISE:   L = (1/b) sum_i t_i
+ *   MI_NCE_SYMMETRIC: L = 1/2 (1/b) sum_i t_i + 1/2 (1/b) sum_j t'_j
+ *   dL/dS[i, j] = w_r (exp(S[i,j] - r_i) - qr_ij) + w_c (exp(S[i,j] - c_j) - qc_ij),
+ *   (w_r, w_c) = (1/b, 0) or (1/(2b), 1/(2b)); each row's share of dL/dS sums to zero.
+ * a_ij is formed in fp32 as popcount * (rs_i * rs_j), rs = 1 / sqrt(n).  mix = 0 IS the loss of mi_nce_* on unique ids.
+ * Every mask equal and mix = 1: the loss of mi_posnce_* with all ids equal.  One distinct bit per study, mix = 1 and a
+ * small tau (0.02): the loss of mi_posnce_* with those ids.  All masks zero: uniform smoothing of weight exp(-1/tau) off
+ * the diagonal.  b == 1 gives loss exactly 0.0 and exact-zero gradients.
+ * A TRAINING LOSS, NOT AN MI BOUND: log b - L bounds nothing once mix > 0; `mode` codes are those of mi_nce_*, not
+ * estimator codes.  Whole batch only: no row-block form.  No b x b target matrix exists: both GEMM epilogues recompute
+ * the pair weights from the masks and the per-sample z and rs that one launch ahead of the score GEMM writes.
+ * Outputs: loss_out [1]; optional lse_rows [b], lse_cols [b] (r and c, both written in either mode), target_norm [b]
+ * (z).  grad_out may be NULL (1).  Gradient pointers all NULL: the forward launches only, and the workspace query with
+ * with_grads == 0 (no G) suffices; otherwise every gradient is written and the workspace is that of with_grads != 0.
+ * w == NULL is S = X Y^T (d_img == d_txt, no grad_w).  precision: MI_PREC_BF16 / BF16X3 run the 16-bit GEMM chain where b
+ * and the widths are multiples of 8, every other shape and MI_PREC_F32 the generic kernels; MI_PREC_FP8 / F16 / F16X3:
+ * MI_EINVAL.  MI_EINVAL also for null required pointers, sizes < 1, b >= 2^31, an unknown mode, a partial gradient set,
+ * tau not finite or <= 0, mix outside [0, 1] or NaN; MI_EWORKSPACE for a short workspace; all before anything touches
+ * the device.  Deterministic: z summed and records merged in fixed order, no float atomics. */
+#define MI_SOFTNCE_MAX_LABELS 63
+size_t mi_softnce_bilinear_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int precision, int with_grads);
+int mi_softnce_bilinear_step(const float* x, const float* y, const float* w, const int64_t* label_mask, int64_t b,
+                             int64_t d_img, int64_t d_txt, int mode, int precision, float tau, float mix,
+                             const float* grad_out, float* loss_out, float* lse_rows, float* lse_cols, float* target_norm,
+                             float* grad_x, float* grad_y, float* grad_w, void* workspace, size_t workspace_bytes,
+                             void* stream);
+/* S = (X Wg)(Y Wh)^T: projects, runs the w == NULL form on the projections, projects the gradients back */
+size_t mi_softnce_separable_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int precision,
+                                            int with_grads);
+int mi_softnce_separable_step(const float* x, const float* y, const float* wg, const float* wh, const int64_t* label_mask,
+                              int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int mode, int precision, float tau,
+                              float mix, const float* grad_out, float* loss_out, float* lse_rows, float* lse_cols,
+                              float* target_norm, float* grad_x, float* grad_y, float* grad_wg, float* grad_wh,
+                              void* workspace, size_t workspace_bytes, void* stream);
+/* on a caller's fp32 [b, b] score matrix (any critic, exact expf): the forward writes loss_out[0] and the optional
+ * lse_rows / lse_cols / target_norm; the backward reads lse_rows, target_norm (required: MI_EINVAL without it; and
+ * lse_cols in the symmetric mode) and writes the dense grad_scores [b, b] = grad_out[0] * dloss/dS */
+size_t mi_matrix_softnce_workspace_bytes(int64_t b);
+int mi_matrix_softnce_fwd(const float* scores, const int64_t* label_mask, int64_t b, int mode, float tau, float mix,
+                          float* loss_out, float* lse_rows, float* lse_cols, float* target_norm, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int mi_matrix_softnce_bwd(const float* scores, const int64_t* label_mask, int64_t b, int mode, float tau, float mix,
+                          const float* lse_rows, const float* lse_cols, const float* target_norm, const float* grad_out,
+                          float* grad_scores, void* stream);
 
 #ifdef __cplusplus
 }

@@ -25,6 +25,7 @@
 #include "mi_hardnce.h"
 #include "mi_banknce.h"
 #include "mi_posnce.h"
+#include "mi_softnce.h"
 
 namespace mi {
 
@@ -2025,6 +2026,83 @@ static int posnce_chain(const float* x, const float* y, const float* w, const in
                                 grad_w, n.p, st);
 }
 
+// ------------------------------------------------------------------------------------------------ soft-target InfoNCE
+// (mi_softnce.h)  The chain of the per-sample InfoNCE with the epilogues that weigh every pair by
+// the similarity of its finding sets; whole batch only:
+//   softnce_label_norm_kernel -> prep + T = X W -> score GEMM + records -> softnce_merge_kernel -> nce_loss_kernel
+//   [grads] G GEMM -> dT = G Y | dY = G^T T -> dW = X^T dT | dX = dT W^T
+struct SoftNceEst {
+  using StatsOut = SoftNceStatsOut;
+  using GradIn = SoftNceGradIn;
+  using Stats = EpiSoftNceStats<false>;
+  using Stats16 = EpiSoftNceStats<true>;
+  template <typename TG>
+  using Grad = EpiSoftNceGrad<TG>;
+  using Grad16 = EpiSoftNceGrad2;
+  static int check_mode(const char* fn, int mode) { return NceEst::check_mode(fn, mode); }
+  static constexpr const char* kName = "the soft-target InfoNCE";
+  static constexpr const char* kT = "softnce T = X W (generic)";
+  static constexpr const char* kScores = "softnce score + records (generic)";
+  static constexpr const char* kScores16 = "softnce score + records";
+  static constexpr const char* kG = "softnce G (generic)";
+  static constexpr const char* kG16 = "softnce G";
+  static constexpr SepLabels kSep = {"softnce separable A = X Wg",     "softnce separable C = Y Wh",
+                                     "softnce separable dX = dA Wg^T", "softnce separable dWg = X^T dA",
+                                     "softnce separable dY = dC Wh^T", "softnce separable dWh = Y^T dC"};
+};
+
+// b, mode, tau and mix of every soft-target entry point (NaN fails both range tests)
+static int softnce_check_targets(const char* fn, int64_t b, int mode, float tau, float mix) {
+  MI_CHECK_ARG(b >= 1 && b < ((int64_t)1 << 31), "%s: b must be in [1, 2^31)", fn);
+  const int rc = SoftNceEst::check_mode(fn, mode);
+  if (rc) return rc;
+  MI_CHECK_ARG(std::isfinite(tau) && tau > 0.0f, "%s: tau must be finite and > 0 (got %g)", fn, (double)tau);
+  MI_CHECK_ARG(mix >= 0.0f && mix <= 1.0f, "%s: mix must be in [0, 1] (got %g)", fn, (double)mix);
+  return MI_OK;
+}
+
+static int softnce_check(const char* fn, int64_t b, int64_t dx, int64_t dy, int mode, int precision, float tau, float mix) {
+  const int rc = chain_check<SoftNceEst>(fn, b, b, 0, dx, dy, mode, precision);
+  if (rc) return rc;
+  return softnce_check_targets(fn, b, mode, tau, mix);
+}
+
+// grads: the nce step's buffers (with G and G^T); forward only: the forward half's buffers alone, no G
+struct SoftNceBilinearPlan {
+  BilinearPlan p;
+  SoftNcePlan q;
+  size_t bytes;
+};
+static SoftNceBilinearPlan plan_softnce_bilinear(Workspace& ws, int64_t b, int64_t dx, int64_t dy, int precision,
+                                                 bool grads) {
+  SoftNceBilinearPlan n{};
+  n.p = grads ? plan_bilinear(ws, b, b, dx, dy, precision, true, true) : plan_rank_bilinear(ws, b, dx, dy, precision).p;
+  n.q = plan_softnce(ws, b);
+  n.bytes = ws.off;
+  return n;
+}
+static SeparableChainPlan<SoftNceBilinearPlan> plan_softnce_separable(Workspace& ws, int64_t b, int64_t k, int precision,
+                                                                      bool grads) {
+  return plan_separable_chain(ws, b, b, k, [&] { return plan_softnce_bilinear(ws, b, k, k, precision, grads); });
+}
+
+// The whole step on (x, y, w); w == nullptr: S = X Y^T, dT is grad_x and there is no grad_w
+static int softnce_chain(const float* x, const float* y, const float* w, const int64_t* lab, int64_t b, int64_t dx,
+                         int64_t dy, int mode, int precision, float tau, float mix, const float* grad_out, float* loss_out,
+                         float* lse_rows, float* lse_cols, float* target_norm, float* grad_x, float* grad_y, float* grad_w,
+                         bool any_grad, const SoftNceBilinearPlan& n, hipStream_t st) {
+  int rc = softnce_label_norm(lab, b, tau, chain_16bit_ok(b, b, dx, dy, precision), n.q, target_norm, st);
+  if (rc) return rc;
+  rc = chain_scores<SoftNceEst>(x, y, w, nullptr, nullptr, b, b, 0, dx, dy, precision,
+                                softnce_stats_out(n.q, lab, tau, mix), n.p, st);
+  if (rc) return rc;
+  rc = softnce_finish(n.q, b, mode, loss_out, lse_rows, lse_cols, st);
+  if (rc || !any_grad) return rc;
+  return chain_grads<SoftNceEst>(x, y, w, b, b, dx, dy, precision,
+                                 softnce_grad_in(lab, n.q.rs, n.q.inv_z, nullptr, n.q.r, n.q.c, grad_out, b, mode, tau, mix),
+                                 grad_x, grad_y, grad_w, n.p, st);
+}
+
 // ------------------------------------------------------------------------------------------------ memory-bank InfoNCE
 // (mi_banknce.h)  The per-sample InfoNCE of the batch against the batch and a bank of past
 // embeddings: an L-shaped score matrix, a top block [b] x [b + m] (a row block of the chain: br = b, row_offset = 0, the
@@ -3059,6 +3137,118 @@ int mi_matrix_posnce_bwd(const float* scores, const int64_t* sid, int64_t b, int
                        posnce_grad_in(sid, lse_rows, lse_cols, nullptr, n_pos, grad_out, b, mode), grad_scores);
   }
   MI_LAUNCH_CHECK("posnce_matrix_grad_kernel");
+  return MI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ soft-target InfoNCE
+size_t mi_softnce_bilinear_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int precision, int with_grads) {
+  if (b <= 0 || d_img <= 0 || d_txt <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_softnce_bilinear(ws, b, d_img, d_txt, precision, with_grads != 0).bytes + 256;
+}
+
+int mi_softnce_bilinear_step(const float* x, const float* y, const float* w, const int64_t* label_mask, int64_t b,
+                             int64_t d_img, int64_t d_txt, int mode, int precision, float tau, float mix,
+                             const float* grad_out, float* loss_out, float* lse_rows, float* lse_cols, float* target_norm,
+                             float* grad_x, float* grad_y, float* grad_w, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+  MI_CHECK_ARG(x && y && label_mask && loss_out && workspace, "mi_softnce_bilinear_step: null pointer");
+  int rc = softnce_check("mi_softnce_bilinear_step", b, d_img, d_txt, mode, precision, tau, mix);
+  if (rc) return rc;
+  MI_CHECK_ARG(w || d_img == d_txt, "mi_softnce_bilinear_step: w == NULL (S = X Y^T) needs d_img == d_txt");
+  const bool any_grad = grad_x || grad_y || grad_w;
+  MI_CHECK_ARG(!any_grad || (grad_x && grad_y && (w ? grad_w != nullptr : grad_w == nullptr)),
+               "mi_softnce_bilinear_step: pass grad_x, grad_y and (with w) grad_w, or none of them");
+  Workspace ws(workspace, workspace_bytes);
+  const SoftNceBilinearPlan n = plan_softnce_bilinear(ws, b, d_img, d_txt, precision, any_grad);
+  rc = ws_fits(ws, "mi_softnce_bilinear_step");
+  if (rc) return rc;
+  return softnce_chain(x, y, w, label_mask, b, d_img, d_txt, mode, precision, tau, mix, grad_out, loss_out, lse_rows,
+                       lse_cols, target_norm, grad_x, grad_y, grad_w, any_grad, n, (hipStream_t)stream);
+}
+
+size_t mi_softnce_separable_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int precision,
+                                            int with_grads) {
+  if (b <= 0 || d_img <= 0 || d_txt <= 0 || d_proj <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_softnce_separable(ws, b, d_proj, precision, with_grads != 0).bytes + 256;
+}
+
+int mi_softnce_separable_step(const float* x, const float* y, const float* wg, const float* wh, const int64_t* label_mask,
+                              int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int mode, int precision, float tau,
+                              float mix, const float* grad_out, float* loss_out, float* lse_rows, float* lse_cols,
+                              float* target_norm, float* grad_x, float* grad_y, float* grad_wg, float* grad_wh,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && wg && wh && label_mask && loss_out && workspace, "mi_softnce_separable_step: null pointer");
+  int rc = softnce_check("mi_softnce_separable_step", b, d_img, d_txt, mode, precision, tau, mix);
+  if (rc) return rc;
+  MI_CHECK_ARG(d_proj >= 1, "mi_softnce_separable_step: projection width must be >= 1");
+  const bool any_grad = grad_x || grad_y || grad_wg || grad_wh;
+  MI_CHECK_ARG(!any_grad || (grad_x && grad_y && grad_wg && grad_wh),
+               "mi_softnce_separable_step: pass all four gradients or none of them");
+  Workspace ws(workspace, workspace_bytes);
+  const auto sp = plan_softnce_separable(ws, b, d_proj, precision, any_grad);
+  rc = ws_fits(ws, "mi_softnce_separable_step");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t k = d_proj;
+  const bool bf = precision == MI_PREC_BF16;
+  rc = separable_project(SoftNceEst::kSep, bf, x, y, wg, wh, b, b, d_img, d_txt, k, sp.a, sp.c, st);
+  if (rc) return rc;
+  rc = softnce_chain(sp.a, sp.c, nullptr, label_mask, b, k, k, mode, precision, tau, mix, grad_out, loss_out, lse_rows,
+                     lse_cols, target_norm, sp.da, sp.dc, nullptr, any_grad, sp.n, st);
+  if (rc || !any_grad) return rc;
+  return separable_project_back(SoftNceEst::kSep, bf, x, y, wg, wh, b, b, d_img, d_txt, k, sp.da, sp.dc, grad_x, grad_y,
+                                grad_wg, grad_wh, st);
+}
+
+size_t mi_matrix_softnce_workspace_bytes(int64_t b) {
+  if (b <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  plan_softnce(ws, b);
+  return ws.off + 256;
+}
+
+int mi_matrix_softnce_fwd(const float* scores, const int64_t* label_mask, int64_t b, int mode, float tau, float mix,
+                          float* loss_out, float* lse_rows, float* lse_cols, float* target_norm, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(scores && label_mask && loss_out && workspace, "mi_matrix_softnce_fwd: null pointer");
+  int rc = softnce_check_targets("mi_matrix_softnce_fwd", b, mode, tau, mix);
+  if (rc) return rc;
+  Workspace ws(workspace, workspace_bytes);
+  const SoftNcePlan q = plan_softnce(ws, b);
+  rc = ws_fits(ws, "mi_matrix_softnce_fwd");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  rc = softnce_label_norm(label_mask, b, tau, false, q, target_norm, st);
+  if (rc) return rc;
+  {
+    ProfScope prof_("softnce_matrix_stats_kernel", st);
+    hipLaunchKernelGGL(softnce_matrix_stats_kernel, dim3((unsigned)q.n_t, (unsigned)q.n_t), dim3(64), 0, st, scores, b,
+                       softnce_stats_out(q, label_mask, tau, mix));
+  }
+  MI_LAUNCH_CHECK("softnce_matrix_stats_kernel");
+  return softnce_finish(q, b, mode, loss_out, lse_rows, lse_cols, st);
+}
+
+int mi_matrix_softnce_bwd(const float* scores, const int64_t* label_mask, int64_t b, int mode, float tau, float mix,
+                          const float* lse_rows, const float* lse_cols, const float* target_norm, const float* grad_out,
+                          float* grad_scores, void* stream) {
+  MI_CHECK_ARG(scores && label_mask && lse_rows && grad_scores, "mi_matrix_softnce_bwd: null pointer");
+  MI_CHECK_ARG(target_norm, "mi_matrix_softnce_bwd: target_norm (the forward's z) is required");
+  const int rc = softnce_check_targets("mi_matrix_softnce_bwd", b, mode, tau, mix);
+  if (rc) return rc;
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || lse_cols, "mi_matrix_softnce_bwd: the symmetric mode needs lse_cols");
+  const int64_t nt = (b + 63) / 64;
+  hipStream_t st = (hipStream_t)stream;
+  {
+    ProfScope prof_("softnce_matrix_grad_kernel", st);
+    hipLaunchKernelGGL(softnce_matrix_grad_kernel, dim3((unsigned)nt, (unsigned)nt), dim3(64), 0, st, scores, b,
+                       softnce_grad_in(label_mask, nullptr, nullptr, target_norm, lse_rows, lse_cols, grad_out, b, mode,
+                                       tau, mix),
+                       grad_scores);
+  }
+  MI_LAUNCH_CHECK("softnce_matrix_grad_kernel");
   return MI_OK;
 }
 

@@ -87,10 +87,16 @@ def train_mutual_information(args, device):
     study_pos = bool(getattr(args, "study_positives", False))
     if study_pos:
         hard = dict(hard, mi_estimator=getattr(args, "mi_estimator", None), study_positives=True)
+    # --soft_targets CSV: the same losses with soft targets from the studies' finding labels
+    soft = {}
+    if getattr(args, "soft_targets", None) is not None:
+        soft = dict(soft_targets=args.soft_targets, soft_tau=args.soft_tau, soft_mix=args.soft_mix,
+                    soft_uncertain_positive=bool(getattr(args, "soft_uncertain_positive", False)))
+        hard = dict(hard, mi_estimator=getattr(args, "mi_estimator", None), **soft)
     if getattr(args, "synthetic", False):
         model_manager = MultiModalManager(d_img=args.embed_dim_img, d_txt=args.embed_dim_txt, critic=critic,
                                           mi_estimator=getattr(args, "mi_estimator", None), hard_negatives=hard_k,
-                                          memory_bank=bank_k, study_positives=study_pos)
+                                          memory_bank=bank_k, study_positives=study_pos, **soft)
         source = synthetic_embedding_source(args, device)
     elif getattr(args, "synthetic_encoders", False):
         from mutual_info_img_txt.model import ResNet256_6_2_1, TextBert

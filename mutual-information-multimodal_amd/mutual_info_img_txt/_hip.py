@@ -211,8 +211,16 @@ SIGNATURES = {
     "mi_matrix_posnce_workspace_bytes": (_SZ, [_I64]),
     "mi_matrix_posnce_fwd": (c_int, [_P, _P, _I64, _I] + [_P] * 5 + [_SZ, _P]),
     "mi_matrix_posnce_bwd": (c_int, [_P, _P, _I64, _I] + [_P] * 6),
+    "mi_softnce_bilinear_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I, _I]),
+    "mi_softnce_bilinear_step": (c_int, [_P] * 4 + [_I64] * 3 + [_I, _I, c_float, c_float] + [_P] * 9 + [_SZ, _P]),
+    "mi_softnce_separable_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I, _I]),
+    "mi_softnce_separable_step": (c_int, [_P] * 5 + [_I64] * 4 + [_I, _I, c_float, c_float] + [_P] * 10 + [_SZ, _P]),
+    "mi_matrix_softnce_workspace_bytes": (_SZ, [_I64]),
+    "mi_matrix_softnce_fwd": (c_int, [_P, _P, _I64, _I, c_float, c_float] + [_P] * 5 + [_SZ, _P]),
+    "mi_matrix_softnce_bwd": (c_int, [_P, _P, _I64, _I, c_float, c_float] + [_P] * 6),
 }
 MI_TOPK_MAX_K = 32  # include/mi_critic.h
+MI_SOFTNCE_MAX_LABELS = 63  # include/mi_critic.h
 
 _lib: Optional[ctypes.CDLL] = None
 

@@ -1,5 +1,5 @@
 """The one binding of the critic entry points of the C ABI (mi_bilinear_*, mi_separable_*, mi_concat_mlp_*, mi_nce_*,
-mi_fdiv_*, mi_rank_*, mi_topk_*, mi_hardnce_*, mi_banknce_*, mi_posnce_*), shared by ``mi_critics`` (eager autograd), ``graphed`` (hipGraph step) and ``distributed`` (sharded step).
+mi_fdiv_*, mi_rank_*, mi_topk_*, mi_hardnce_*, mi_banknce_*, mi_posnce_*, mi_softnce_*), shared by ``mi_critics`` (eager autograd), ``graphed`` (hipGraph step) and ``distributed`` (sharded step).
 
 An ops object scores the row block ``x`` [b_rows, d_img] (starting at ``row_offset``) against all of ``y_all``
 [b, d_txt]; a whole batch is ``b_rows == b``, ``row_offset == 0``.  Each ``*_call`` method writes one entry point's
@@ -147,6 +147,26 @@ def posnce_matrix_bwd(scores, sid, mode, r, c, n_pos, grad_out):
     return g
 
 
+def softnce_matrix_fwd(scores, lab, mode, tau, mix):
+    """Soft-target InfoNCE of a float32 [B, B] score matrix (mi_matrix_softnce_fwd): (loss [1], lse_rows [B], lse_cols
+    [B], target_norm [B]); both LSEs in either mode."""
+    b, dev = scores.shape[0], scores.device
+    ws = _hip.workspace(_hip.load().mi_matrix_softnce_workspace_bytes(b), dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    r, c, z = (torch.empty(b, dtype=torch.float32, device=dev) for _ in range(3))
+    _hip.call("mi_matrix_softnce_fwd", dev, scores.data_ptr(), lab.data_ptr(), b, mode, tau, mix, loss.data_ptr(),
+              r.data_ptr(), c.data_ptr(), z.data_ptr(), ws.data_ptr(), ws.numel())
+    return loss, r, c, z
+
+
+def softnce_matrix_bwd(scores, lab, mode, tau, mix, r, c, z, grad_out):
+    """grad_scores [B, B] of grad_out[0] * loss (mi_matrix_softnce_bwd) from the forward's LSEs and target norms."""
+    g = torch.empty_like(scores)
+    _hip.call("mi_matrix_softnce_bwd", scores.device, scores.data_ptr(), lab.data_ptr(), scores.shape[0], mode, tau, mix,
+              r.data_ptr(), _p(c), z.data_ptr(), _p(grad_out), g.data_ptr())
+    return g
+
+
 class _HipOps:
     """The ops protocol of ``distributed.GlobalBatchCriticFn`` (forward / merge / backward) on the C ABI.  ``saved`` is
     (x, y_all, params, sid_rows, sid_all, row_offset, precision, scores, ws) for every critic."""
@@ -268,6 +288,18 @@ class _HipOps:
         grads = [torch.empty_like(t) for t in (x, y, *params)] if need_grad else []
         self.posnce_call(x, y, params, sid, mode, precision, loss, r, c, n_pos, grads, ws)()
         return loss, r, c, n_pos, grads
+
+    def softnce_step(self, x, y, params, lab, mode, precision, tau, mix, need_grad):
+        """The soft-target InfoNCE of the whole batch in one call of ``mi_softnce_<critic>_step`` (bilinear and separable
+        critics), with the gradients of 1 * loss when ``need_grad``: (loss [1], lse_rows [B], lse_cols [B], target_norm
+        [B], [grad_x, grad_y, grad_params...] or [])."""
+        b, dev = x.shape[0], x.device
+        ws = _hip.workspace(self.softnce_workspace_bytes(b, x.shape[1], y.shape[1], params, precision, need_grad), dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        r, c, z = (torch.empty(b, dtype=torch.float32, device=dev) for _ in range(3))
+        grads = [torch.empty_like(t) for t in (x, y, *params)] if need_grad else []
+        self.softnce_call(x, y, params, lab, mode, precision, tau, mix, loss, r, c, z, grads, ws)()
+        return loss, r, c, z, grads
 
     # ---------------------------------------------- per-sample InfoNCE on a row block (distributed.GlobalBatchNceFn)
     def nce_forward(self, x, y_all, params, sid_rows, sid_all, row_offset, mode, precision, need_grad=True):
@@ -413,6 +445,19 @@ class HipBilinearOps(_HipOps):
         gx, gy, gw = (grads + [None] * 3)[:3]
         return _call("mi_posnce_bilinear_step", x.device, x.data_ptr(), y.data_ptr(), _p(w), sid.data_ptr(), x.shape[0],
                      x.shape[1], y.shape[1], mode, precision, None, loss.data_ptr(), _p(r), _p(c), _p(n_pos), _p(gx),
+                     _p(gy), _p(gw), ws.data_ptr(), ws.numel())
+
+    @staticmethod
+    def softnce_workspace_bytes(b, dx, dy, params, precision, need_grad):
+        return _hip.load().mi_softnce_bilinear_workspace_bytes(b, dx, dy, precision, int(bool(need_grad)))
+
+    def softnce_call(self, x, y, params, lab, mode, precision, tau, mix, loss, r, c, z, grads, ws):
+        """Soft-target InfoNCE step (mi_softnce_bilinear_step); ``r`` / ``c`` / ``z`` may be None, ``grads`` [] for the
+        forward launches alone."""
+        w = params[0] if params else None
+        gx, gy, gw = (grads + [None] * 3)[:3]
+        return _call("mi_softnce_bilinear_step", x.device, x.data_ptr(), y.data_ptr(), _p(w), lab.data_ptr(), x.shape[0],
+                     x.shape[1], y.shape[1], mode, precision, tau, mix, None, loss.data_ptr(), _p(r), _p(c), _p(z), _p(gx),
                      _p(gy), _p(gw), ws.data_ptr(), ws.numel())
 
     @staticmethod
@@ -631,6 +676,19 @@ class HipSeparableOps(_HipOps):
         return _call("mi_posnce_separable_step", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
                      sid.data_ptr(), x.shape[0], x.shape[1], y.shape[1], wg.shape[1], mode, precision, None,
                      loss.data_ptr(), _p(r), _p(c), _p(n_pos), *[_p(g) for g in grads or [None] * 4], ws.data_ptr(),
+                     ws.numel())
+
+    @staticmethod
+    def softnce_workspace_bytes(b, dx, dy, params, precision, need_grad):
+        return _hip.load().mi_softnce_separable_workspace_bytes(b, dx, dy, params[0].shape[1], precision,
+                                                                int(bool(need_grad)))
+
+    def softnce_call(self, x, y, params, lab, mode, precision, tau, mix, loss, r, c, z, grads, ws):
+        """Soft-target InfoNCE step (mi_softnce_separable_step), as ``HipBilinearOps.softnce_call``."""
+        wg, wh = params
+        return _call("mi_softnce_separable_step", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
+                     lab.data_ptr(), x.shape[0], x.shape[1], y.shape[1], wg.shape[1], mode, precision, tau, mix, None,
+                     loss.data_ptr(), _p(r), _p(c), _p(z), *[_p(g) for g in grads or [None] * 4], ws.data_ptr(),
                      ws.numel())
 
     @staticmethod

@@ -3,16 +3,17 @@
 ``fused_critic_scores(embedding_img, embedding_txt, critic)`` returns S [n_img, n_txt], S[i, j] = critic([img_i ; txt_j]),
 without materialising the [n_img * n_txt, d_img + d_txt] pair matrix, and carries autograd: whatever loss is applied to S
 -- the matrix functions of this package (``matrix_bound_loss``, ``matrix_hard_negative_infonce``,
-``matrix_study_positive_infonce``) or plain torch -- its dL/dS goes back through the fused backward kernels to both
-embeddings and the six parameters of the critic (mi_concat_mlp_scores_fwd / mi_concat_mlp_bwd_from_g, DESIGN.md section
-15).  The DV, "infonce", JSD and NWJ bounds of this critic stay with ``fused_mi_bound``, which forms their gradient inside
-the kernels and never reads a [B, B] gradient matrix.
+``matrix_study_positive_infonce``, ``matrix_soft_target_infonce``) or plain torch -- its dL/dS goes back through the
+fused backward kernels to both embeddings and the six parameters of the critic (mi_concat_mlp_scores_fwd /
+mi_concat_mlp_bwd_from_g).  The DV, "infonce", JSD and NWJ bounds of this critic stay with
+``fused_mi_bound``, which forms their gradient inside the kernels and never reads a [B, B] gradient matrix.
 
-Three one-line compositions for the losses ``fused_mi_bound`` and its siblings do not take for this critic:
+Four one-line compositions for the losses ``fused_mi_bound`` and its siblings do not take for this critic:
 
 * ``concat_infonce``                 -- per-sample InfoNCE (row-wise / symmetric), or any estimator of ``matrix_bound_loss``
 * ``concat_hard_negative_infonce``   -- hard-negative InfoNCE on each query's top-k negatives
 * ``concat_study_positive_infonce``  -- same-study pairs as positives
+* ``concat_soft_target_infonce``     -- soft targets from the studies' finding-label masks
 """
 from __future__ import annotations
 
@@ -22,9 +23,11 @@ from . import _hip
 from .critic_ops import NOT_MAKE_MLP, HipConcatMlpOps, resolve_critic
 from .hard_negatives import matrix_hard_negative_infonce
 from .mi_critics import _critic_kind, _f32_inputs, matrix_bound_loss
+from .soft_targets import matrix_soft_target_infonce
 from .study_positives import matrix_study_positive_infonce
 
-__all__ = ["fused_critic_scores", "concat_infonce", "concat_hard_negative_infonce", "concat_study_positive_infonce"]
+__all__ = ["fused_critic_scores", "concat_infonce", "concat_hard_negative_infonce", "concat_study_positive_infonce",
+           "concat_soft_target_infonce"]
 
 
 class _ScoresFn(torch.autograd.Function):
@@ -99,3 +102,10 @@ def concat_study_positive_infonce(embedding_img, embedding_txt, study_id, critic
     """``matrix_study_positive_infonce`` on the fused scores of a make_mlp critic; a batch: n_img == n_txt."""
     return matrix_study_positive_infonce(fused_critic_scores(embedding_img, embedding_txt, critic, precision), study_id,
                                          symmetric=symmetric, return_stats=return_stats)
+
+
+def concat_soft_target_infonce(embedding_img, embedding_txt, labels, critic, *, tau, mix, symmetric: bool = True,
+                               precision: str = "f32", return_stats: bool = False):
+    """``matrix_soft_target_infonce`` on the fused scores of a make_mlp critic; a batch: n_img == n_txt."""
+    return matrix_soft_target_infonce(fused_critic_scores(embedding_img, embedding_txt, critic, precision), labels,
+                                      tau=tau, mix=mix, symmetric=symmetric, return_stats=return_stats)

@@ -103,7 +103,9 @@ class MultiModalManager:
                  d_img: int = 768, d_txt: int = 768, critic: str = "concat_mlp", hidden_dims=(1024, 512),
                  d_proj: int = 256, image_model=None, text_model=None, bert_config=None, embed_proj_dim=None,
                  autocast_dtype=None, mi_estimator: Optional[str] = None, hard_negatives: Optional[int] = None,
-                 memory_bank: Optional[int] = None, study_positives: bool = False):
+                 memory_bank: Optional[int] = None, study_positives: bool = False, soft_targets=None,
+                 soft_tau: Optional[float] = None, soft_mix: Optional[float] = None,
+                 soft_uncertain_positive: bool = False):
         self.bert_pretrained_dir = bert_pretrained_dir
         self.bert_config_name = bert_config_name
         self.output_channels = output_channels
@@ -169,6 +171,28 @@ class MultiModalManager:
                 raise ValueError("study_positives cannot be combined with hard_negatives or memory_bank (those losses "
                                  "drop same-study pairs; this one trains on them)")
             self.study_positives_estimator = mi_estimator
+        # soft-target InfoNCE (soft_targets.py): the row-wise / symmetric loss with targets from the studies' finding
+        # labels; `soft_targets` is a {study id: mask} table (load_label_table) or the path of the label CSV
+        self.soft_targets = None
+        if soft_targets is not None:
+            from .soft_targets import check_tau_mix, label_key, load_label_table
+            if mi_estimator not in _hip.NCE_ESTIMATORS:
+                raise ValueError(f"soft_targets is a switch on the per-sample InfoNCE: it needs mi_estimator in "
+                                 f"{sorted(_hip.NCE_ESTIMATORS)} (got {mi_estimator!r})")
+            if hard_negatives is not None or memory_bank is not None or study_positives:
+                raise ValueError("soft_targets cannot be combined with hard_negatives, memory_bank or study_positives")
+            if soft_tau is None or soft_mix is None:
+                raise ValueError("soft_targets needs both soft_tau and soft_mix (there is no default to defend)")
+            self.soft_tau, self.soft_mix = check_tau_mix(soft_tau, soft_mix)
+            if isinstance(soft_targets, dict):
+                self.soft_targets = {label_key(k): int(v) for k, v in soft_targets.items()}
+                if any(v < 0 or v >> 63 for v in self.soft_targets.values()):
+                    raise ValueError("soft_targets: a label mask must fit 63 bits and be non-negative")
+            else:
+                self.soft_targets = load_label_table(soft_targets, uncertain_positive=soft_uncertain_positive)
+            self.soft_targets_estimator = mi_estimator
+        elif soft_tau is not None or soft_mix is not None:
+            raise ValueError("soft_tau / soft_mix are parameters of soft_targets: pass the label table too")
         self.d_img, self.d_txt = d_img, d_txt
         self.training_loss = []
         self._graphed = None
@@ -184,6 +208,18 @@ class MultiModalManager:
             raise ValueError("embedding_img, embedding_txt and study_id must have the same length")
         return _CreatePairsFn.apply(embedding_img, embedding_txt, sid)
 
+    def label_masks_of(self, study_id) -> torch.Tensor:
+        """int64 [B] label masks (CPU) of a batch's study ids from the ``soft_targets`` table; KeyError naming the first
+        id the table does not hold."""
+        from .soft_targets import label_key
+        masks = []
+        for s in study_id:
+            key = label_key(s)
+            if key not in self.soft_targets:
+                raise KeyError(f"study id {s!r} is not in the soft_targets label table")
+            masks.append(self.soft_targets[key])
+        return torch.tensor(masks, dtype=torch.int64)
+
     def mi_step(self, embedding_img, embedding_txt, study_id, mi_estimator: str = "dv", precision: str = "f32",
                 fused: bool = True, graph: bool = False):
         """Reference main_utils.py:220-224.  ``fused=False`` runs the literal three-call sequence (pair kernel, critic
@@ -197,8 +233,18 @@ class MultiModalManager:
         ``memory_bank=K`` runs ``memory_bank.memory_bank_infonce`` against its queue ``self.bank`` here, eagerly; the
         training loop pushes each batch's detached embeddings after the optimizer steps.  The queue is not checkpointed:
         after a resume it is empty and refills.  A manager built with ``study_positives=True`` runs
-        ``study_positives.study_positive_infonce`` here, eagerly (a training loss, not an MI bound)."""
+        ``study_positives.study_positive_infonce`` here, eagerly (a training loss, not an MI bound).  A manager built
+        with ``soft_targets=`` looks each study id of the batch up in its label table (an id absent from it raises,
+        naming it) and runs ``soft_targets.soft_target_infonce`` here, eagerly (a training loss too)."""
         est = mi_critics.check_estimator(mi_estimator, self.critic_kind)
+        if self.soft_targets is not None:
+            if mi_estimator != self.soft_targets_estimator:
+                raise ValueError(f"this manager trains the soft-target form of {self.soft_targets_estimator!r}; "
+                                 f"mi_step got mi_estimator={mi_estimator!r}")
+            from .soft_targets import soft_target_infonce
+            return soft_target_infonce(embedding_img, embedding_txt, self.label_masks_of(study_id),
+                                       self.mi_discriminator, tau=self.soft_tau, mix=self.soft_mix,
+                                       symmetric=mi_estimator == "infonce_symmetric", precision=precision)
         if self.study_positives:
             if mi_estimator != self.study_positives_estimator:
                 raise ValueError(f"this manager trains the study-positive form of {self.study_positives_estimator!r}; "

@@ -38,6 +38,13 @@ def construct_training_parameters(argv=None):
     # study-positive InfoNCE: the row-wise / symmetric loss with every same-study pair as a positive (a loss, not an MI
     # bound)
     p.add_argument('--study_positives', action='store_true')
+    # soft-target InfoNCE: the row-wise / symmetric loss with targets from the finding labels of a CheXpert / NegBio label
+    # table (a CSV with a study_id column); temperature and weight of the soft targets are required with it (a loss, not
+    # an MI bound)
+    p.add_argument('--soft_targets', default=None, type=str, metavar='CSV')
+    p.add_argument('--soft_tau', default=None, type=float)
+    p.add_argument('--soft_mix', default=None, type=float)
+    p.add_argument('--soft_uncertain_positive', action='store_true')
     return p.parse_args(argv)
 
 
@@ -67,6 +74,21 @@ def check_training_parameters(args):
                              f"(got {args.mi_estimator!r})")
         if getattr(args, "hard_negatives", None) is not None or getattr(args, "memory_bank", None) is not None:
             raise ValueError("--study_positives cannot be combined with --hard_negatives or --memory_bank")
+    if getattr(args, "soft_targets", None) is not None:
+        from mutual_info_img_txt._hip import NCE_ESTIMATORS
+        from mutual_info_img_txt.soft_targets import check_tau_mix
+        if args.mi_estimator not in NCE_ESTIMATORS:
+            raise ValueError(f"--soft_targets needs --mi_estimator in {sorted(NCE_ESTIMATORS)} "
+                             f"(got {args.mi_estimator!r})")
+        if (getattr(args, "hard_negatives", None) is not None or getattr(args, "memory_bank", None) is not None or
+                getattr(args, "study_positives", False)):
+            raise ValueError("--soft_targets cannot be combined with --hard_negatives, --memory_bank or --study_positives")
+        if args.soft_tau is None or args.soft_mix is None:
+            raise ValueError("--soft_targets needs both --soft_tau and --soft_mix")
+        args.soft_tau, args.soft_mix = check_tau_mix(args.soft_tau, args.soft_mix)
+    elif (getattr(args, "soft_tau", None) is not None or getattr(args, "soft_mix", None) is not None or
+          getattr(args, "soft_uncertain_positive", False)):
+        raise ValueError("--soft_tau, --soft_mix and --soft_uncertain_positive need --soft_targets CSV")
     return args
 
 
