@@ -604,7 +604,8 @@ int mi_banknce_separable_step(const float* x, const float* y, const float* wg, c
  * mean_j S[i, j] >= log b: the loss is not zero.  b == 1 gives loss exactly 0.0 and exact-zero gradients.
  * A TRAINING LOSS, NOT AN MI BOUND: log b - L bounds nothing once some n_i > 1; `mode` codes are those of mi_nce_*, not
  * estimator codes.  Only this averaged-outside form exists (in the image -> report direction the positives of a row are
- * the same report repeated, so the log-of-sum-over-positives form gains nothing).  Whole batch only: no row-block form.
+ * the same report repeated, so the log-of-sum-over-positives form gains nothing).  Row blocks of a sharded batch: the
+ * mi_posnce_*_shard_* calls below.
  * Outputs: loss_out [1]; optional lse_rows [b], lse_cols [b] (r and c, both written in either mode), n_pos_out int32 [b]
  * (n_i).  grad_out may be NULL (1).  Gradient pointers all NULL: the forward launches only, and the workspace query with
  * with_grads == 0 (no G) suffices; otherwise every gradient is written and the workspace is that of with_grads != 0.
@@ -635,6 +636,59 @@ int mi_matrix_posnce_bwd(const float* scores, const int64_t* sid, int64_t b, int
                          const float* lse_cols, const int32_t* n_pos, const float* grad_out, float* grad_scores,
                          void* stream);
 
+/* ---- study-positive InfoNCE on a sharded batch (row blocks, global-batch normalisation) ----------------------------- */
+/* The convention of mi_nce_*_shard_*: rank g of n_ranks owns rows [row_offset, row_offset + b_rows) of the global b x b
+ * matrix, row_offset = g * b_rows, b = n_ranks * b_rows; x [b_rows, d_img] and sid_rows [b_rows] are its own rows, y [b,
+ * d_txt] and sid_cols [b] every rank's (all-gathered in rank order).  Positives are sid_rows[i] == sid_cols[j]; the loss
+ * is the one above at the global b (weights 1/b).  Per step:
+ *   1. *_shard_fwd: the rank's scores; r_i, n_i and the row term t_i of its rows are complete on this rank (a row has
+ *      all of its columns): optional lse_rows [b_rows], n_pos_out int32 [b_rows].  Its PART, part_out[P] with
+ *      P = mi_posnce_part_floats(b_rows, b) = 3 b + 2 b_rows floats:
+ *        [0, 2b)                        (max, sum exp(S - max)) of column j over this rank's rows, j = 0 .. b-1
+ *        [2b, 3b)                       sum of S[p, j] over this rank's rows p with sid_p == sid_j
+ *        [3b, 3b + b_rows)              row terms t_i
+ *        [3b + b_rows, 3b + 2 b_rows)   n_i as floats (exact: b < 2^24 is required); n_i is also the positive count of
+ *                                       column row_offset + i, the same sample
+ *      The workspace keeps what the backward needs (operand copies, T, r, 1/n): pass the SAME workspace to *_shard_bwd.
+ *   2. all-gather the parts in rank order -> parts [n_ranks][P]; mi_posnce_merge_parts walks every column's partials in
+ *      rank order from an empty start (c_j -> lse_cols [b], the column terms) and reduces the 2b per-sample terms in a
+ *      fixed order: every rank computes identical bits, and n_ranks == 1 gives the bits of mi_posnce_*_step.  Its
+ *      workspace: mi_posnce_merge_workspace_bytes(b).
+ *   3. *_shard_bwd with the merged lse_cols (may be NULL in MI_NCE_ROWWISE): gradients of grad_out[0] * loss (grad_out
+ *      may be NULL: 1).  grad_x [b_rows, d_img] is complete; grad_y [b, d_txt] and grad_w / grad_wg / grad_wh are this
+ *      rank's PARTIAL sums (reduce-scatter grad_y, all-reduce the parameter gradients).
+ * Precisions and paths as mi_posnce_*_step (16-bit chain where b_rows, b and the widths are multiples of 8).  MI_EINVAL,
+ * before anything touches the device: null required pointers, sizes < 1, b_rows > b, a row block outside [0, b),
+ * b >= 2^24, an unknown mode, MI_PREC_FP8 / F16 / F16X3, w == NULL with d_img != d_txt, w without grad_w (or grad_w
+ * without w), the symmetric backward without lse_cols, b != n_ranks * b_rows in the merge.  No float atomics. */
+size_t mi_posnce_part_floats(int64_t b_rows, int64_t b);
+size_t mi_posnce_bilinear_shard_workspace_bytes(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, int precision);
+int mi_posnce_bilinear_shard_fwd(const float* x, const float* y, const float* w, const int64_t* sid_rows,
+                                 const int64_t* sid_cols, int64_t b_rows, int64_t b, int64_t row_offset, int64_t d_img,
+                                 int64_t d_txt, int mode, int precision, float* part_out, float* lse_rows,
+                                 int32_t* n_pos_out, void* workspace, size_t workspace_bytes, void* stream);
+int mi_posnce_bilinear_shard_bwd(const float* x, const float* y, const float* w, const int64_t* sid_rows,
+                                 const int64_t* sid_cols, int64_t b_rows, int64_t b, int64_t row_offset, int64_t d_img,
+                                 int64_t d_txt, int mode, int precision, const float* lse_cols, const float* grad_out,
+                                 float* grad_x, float* grad_y, float* grad_w, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+size_t mi_posnce_merge_workspace_bytes(int64_t b);
+int mi_posnce_merge_parts(const float* parts, int64_t n_ranks, int64_t b_rows, int64_t b, int mode, float* loss_out,
+                          float* lse_cols, void* workspace, size_t workspace_bytes, void* stream);
+/* the separable form projects A = X Wg for the rank's rows and C = Y Wh for all b text rows */
+size_t mi_posnce_separable_shard_workspace_bytes(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj,
+                                                 int precision);
+int mi_posnce_separable_shard_fwd(const float* x, const float* y, const float* wg, const float* wh,
+                                  const int64_t* sid_rows, const int64_t* sid_cols, int64_t b_rows, int64_t b,
+                                  int64_t row_offset, int64_t d_img, int64_t d_txt, int64_t d_proj, int mode, int precision,
+                                  float* part_out, float* lse_rows, int32_t* n_pos_out, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+int mi_posnce_separable_shard_bwd(const float* x, const float* y, const float* wg, const float* wh,
+                                  const int64_t* sid_rows, const int64_t* sid_cols, int64_t b_rows, int64_t b,
+                                  int64_t row_offset, int64_t d_img, int64_t d_txt, int64_t d_proj, int mode, int precision,
+                                  const float* lse_cols, const float* grad_out, float* grad_x, float* grad_y,
+                                  float* grad_wg, float* grad_wh, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- soft-target InfoNCE from finding-label bit masks --------------------------------------- */
 /* The row-wise / symmetric InfoNCE with soft targets: the target distribution of row i puts weight on every report in
  * proportion to how similar its finding set is to that of image i (SoftCLIP, label-aware contrast).  Batch x [b, d_img],
@@ -657,7 +711,8 @@ int mi_matrix_posnce_bwd(const float* scores, const int64_t* sid, int64_t b, int
  * small tau (0.02): the loss of mi_posnce_* with those ids.  All masks zero: uniform smoothing of weight exp(-1/tau) off
  * the diagonal.  b == 1 gives loss exactly 0.0 and exact-zero gradients.
  * A TRAINING LOSS, NOT AN MI BOUND: log b - L bounds nothing once mix > 0; `mode` codes are those of mi_nce_*, not
- * estimator codes.  Whole batch only: no row-block form.  No b x b target matrix exists: both GEMM epilogues recompute
+ * estimator codes.  Row blocks of a sharded batch: the mi_softnce_*_shard_* calls below.  No b x b target matrix exists:
+ * both GEMM epilogues recompute
  * the pair weights from the masks and the per-sample z and rs that one launch ahead of the score GEMM writes.
  * Outputs: loss_out [1]; optional lse_rows [b], lse_cols [b] (r and c, both written in either mode), target_norm [b]
  * (z).  grad_out may be NULL (1).  Gradient pointers all NULL: the forward launches only, and the workspace query with
@@ -692,6 +747,62 @@ int mi_matrix_softnce_fwd(const float* scores, const int64_t* label_mask, int64_
 int mi_matrix_softnce_bwd(const float* scores, const int64_t* label_mask, int64_t b, int mode, float tau, float mix,
                           const float* lse_rows, const float* lse_cols, const float* target_norm, const float* grad_out,
                           float* grad_scores, void* stream);
+
+/* ---- soft-target InfoNCE on a sharded batch (row blocks, global-batch normalisation) ------------------------------- */
+/* The convention of mi_nce_*_shard_*: rank g of n_ranks owns rows [row_offset, row_offset + b_rows) of the global b x b
+ * matrix, row_offset = g * b_rows, b = n_ranks * b_rows; x [b_rows, d_img] and label_rows [b_rows] are its own rows, y
+ * [b, d_txt] and label_cols [b] every rank's (all-gathered in rank order).  The loss is the one above at the global b:
+ * z_i sums over all b samples, the diagonal rule a_ii := 1 holds where row_offset + i == j.  Per step:
+ *   1. *_shard_fwd: z, 1/z and rs of ALL b samples from label_cols (every rank: same inputs, same order, same bits; row
+ *      weights take z of the row, column weights z of the column), then the rank's scores.  r_i and the row term t_i of
+ *      its rows are complete on this rank: optional lse_rows [b_rows], target_norm [b_rows] (z of the rank's rows).  Its
+ *      PART, part_out[P] with P = mi_softnce_part_floats(b_rows, b) = 3 b + b_rows floats:
+ *        [0, 2b)               (max, sum exp(S - max)) of column j over this rank's rows, j = 0 .. b-1
+ *        [2b, 3b)              sum of qc_ij S[i, j] over this rank's rows i
+ *        [3b, 3b + b_rows)     row terms t_i
+ *      The workspace keeps what the backward needs (operand copies, T, r, 1/z, rs): pass the SAME workspace to
+ *      *_shard_bwd.
+ *   2. all-gather the parts in rank order -> parts [n_ranks][P]; mi_softnce_merge_parts walks every column's partials in
+ *      rank order from an empty start (c_j -> lse_cols [b], the column terms) and reduces the 2b per-sample terms in a
+ *      fixed order: every rank computes identical bits, and n_ranks == 1 gives the bits of mi_softnce_*_step.  Its
+ *      workspace: mi_softnce_merge_workspace_bytes(b).
+ *   3. *_shard_bwd with the same masks, tau, mix and the merged lse_cols (may be NULL in MI_NCE_ROWWISE): gradients of
+ *      grad_out[0] * loss (grad_out may be NULL: 1).  grad_x [b_rows, d_img] is complete; grad_y [b, d_txt] and grad_w /
+ *      grad_wg / grad_wh are this rank's PARTIAL sums (reduce-scatter grad_y, all-reduce the parameter gradients).
+ * Precisions and paths as mi_softnce_*_step (16-bit chain where b_rows, b and the widths are multiples of 8).  MI_EINVAL,
+ * before anything touches the device: null required pointers, sizes < 1, b_rows > b, a row block outside [0, b),
+ * b >= 2^24 (the limit of the study-positive parts, kept for both), an unknown mode, tau not finite or <= 0, mix outside
+ * [0, 1] or NaN, MI_PREC_FP8 / F16 / F16X3, w == NULL with d_img != d_txt, w without grad_w (or grad_w without w), the
+ * symmetric backward without lse_cols, b != n_ranks * b_rows in the merge.  No float atomics. */
+size_t mi_softnce_part_floats(int64_t b_rows, int64_t b);
+size_t mi_softnce_bilinear_shard_workspace_bytes(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, int precision);
+int mi_softnce_bilinear_shard_fwd(const float* x, const float* y, const float* w, const int64_t* label_rows,
+                                  const int64_t* label_cols, int64_t b_rows, int64_t b, int64_t row_offset, int64_t d_img,
+                                  int64_t d_txt, int mode, int precision, float tau, float mix, float* part_out,
+                                  float* lse_rows, float* target_norm, void* workspace, size_t workspace_bytes,
+                                  void* stream);
+int mi_softnce_bilinear_shard_bwd(const float* x, const float* y, const float* w, const int64_t* label_rows,
+                                  const int64_t* label_cols, int64_t b_rows, int64_t b, int64_t row_offset, int64_t d_img,
+                                  int64_t d_txt, int mode, int precision, float tau, float mix, const float* lse_cols,
+                                  const float* grad_out, float* grad_x, float* grad_y, float* grad_w, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+size_t mi_softnce_merge_workspace_bytes(int64_t b);
+int mi_softnce_merge_parts(const float* parts, int64_t n_ranks, int64_t b_rows, int64_t b, int mode, float* loss_out,
+                           float* lse_cols, void* workspace, size_t workspace_bytes, void* stream);
+/* the separable form projects A = X Wg for the rank's rows and C = Y Wh for all b text rows */
+size_t mi_softnce_separable_shard_workspace_bytes(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj,
+                                                  int precision);
+int mi_softnce_separable_shard_fwd(const float* x, const float* y, const float* wg, const float* wh,
+                                   const int64_t* label_rows, const int64_t* label_cols, int64_t b_rows, int64_t b,
+                                   int64_t row_offset, int64_t d_img, int64_t d_txt, int64_t d_proj, int mode,
+                                   int precision, float tau, float mix, float* part_out, float* lse_rows,
+                                   float* target_norm, void* workspace, size_t workspace_bytes, void* stream);
+int mi_softnce_separable_shard_bwd(const float* x, const float* y, const float* wg, const float* wh,
+                                   const int64_t* label_rows, const int64_t* label_cols, int64_t b_rows, int64_t b,
+                                   int64_t row_offset, int64_t d_img, int64_t d_txt, int64_t d_proj, int mode,
+                                   int precision, float tau, float mix, const float* lse_cols, const float* grad_out,
+                                   float* grad_x, float* grad_y, float* grad_wg, float* grad_wh, void* workspace,
+                                   size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1962,9 +1962,13 @@ static int hardnce_chain(const float* x, const float* y, const float* w, const i
 
 // ------------------------------------------------------------------------------------------------ study-positive InfoNCE
 // (mi_posnce.h)  The chain of the per-sample InfoNCE with the epilogues that take every same-study
-// pair as a positive; whole batch only:
+// pair as a positive:
 //   prep + T = X W -> score GEMM + records -> posnce_merge_kernel -> nce_loss_kernel
 //   [grads] G GEMM -> dT = G Y | dY = G^T T -> dW = X^T dT | dX = dT W^T
+// A rank's row block runs the same chain in three calls, as the per-sample InfoNCE's:
+//   fwd: prep + T -> score GEMM + records -> posnce_rank_part_kernel (r, 1 / n kept; the part)
+//   merge of the gathered parts: posnce_merge_parts_kernel -> nce_loss_kernel
+//   bwd: G GEMM from r, 1 / n and the merged c -> dT | dY -> dW | dX
 struct PosNceEst {
   using StatsOut = PosNceStatsOut;
   using GradIn = PosNceGradIn;
@@ -2026,11 +2030,44 @@ static int posnce_chain(const float* x, const float* y, const float* w, const in
                                 grad_w, n.p, st);
 }
 
+// A rank's row block: the nce shard plan's buffers with the study-positive records, r and 1 / n
+struct PosNceShardBilinearPlan {
+  BilinearPlan p;
+  PosNceShardPlan q;
+  size_t bytes;
+};
+static PosNceShardBilinearPlan plan_posnce_shard_bilinear(Workspace& ws, int64_t br, int64_t b, int64_t dx, int64_t dy,
+                                                          int precision) {
+  PosNceShardBilinearPlan n{};
+  n.p = plan_bilinear(ws, br, b, dx, dy, precision, true, true);
+  n.q = plan_posnce_shard(ws, br, b);
+  n.bytes = ws.off;
+  return n;
+}
+static SeparableChainPlan<PosNceShardBilinearPlan> plan_posnce_shard_separable(Workspace& ws, int64_t br, int64_t b,
+                                                                               int64_t k, int precision) {
+  return plan_separable_chain(ws, br, b, k, [&] { return plan_posnce_shard_bilinear(ws, br, b, k, k, precision); });
+}
+
+// counts travel in the parts as floats: exact below 2^24
+static int posnce_shard_check(const char* fn, int64_t br, int64_t b, int64_t row_offset, int64_t dx, int64_t dy, int mode,
+                              int precision) {
+  const int rc = chain_check<PosNceEst>(fn, br, b, row_offset, dx, dy, mode, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(b < ((int64_t)1 << 24), "%s: b must be below 2^24 on a sharded batch", fn);
+  return MI_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ soft-target InfoNCE
 // (mi_softnce.h)  The chain of the per-sample InfoNCE with the epilogues that weigh every pair by
-// the similarity of its finding sets; whole batch only:
+// the similarity of its finding sets:
 //   softnce_label_norm_kernel -> prep + T = X W -> score GEMM + records -> softnce_merge_kernel -> nce_loss_kernel
 //   [grads] G GEMM -> dT = G Y | dY = G^T T -> dW = X^T dT | dX = dT W^T
+// A rank's row block runs the same chain in three calls, as the per-sample InfoNCE's:
+//   fwd: softnce_label_norm_kernel on the masks of ALL b samples -> prep + T -> score GEMM + records
+//        -> softnce_rank_part_kernel (r, z, 1 / z, rs kept; the part)
+//   merge of the gathered parts: softnce_merge_parts_kernel -> nce_loss_kernel
+//   bwd: G GEMM from r, 1 / z, rs and the merged c -> dT | dY -> dW | dX
 struct SoftNceEst {
   using StatsOut = SoftNceStatsOut;
   using GradIn = SoftNceGradIn;
@@ -2101,6 +2138,50 @@ static int softnce_chain(const float* x, const float* y, const float* w, const i
   return chain_grads<SoftNceEst>(x, y, w, b, b, dx, dy, precision,
                                  softnce_grad_in(lab, n.q.rs, n.q.inv_z, nullptr, n.q.r, n.q.c, grad_out, b, mode, tau, mix),
                                  grad_x, grad_y, grad_w, n.p, st);
+}
+
+// A rank's row block: the nce shard plan's buffers with the soft-target records, r and the label norms of all b samples
+struct SoftNceShardBilinearPlan {
+  BilinearPlan p;
+  SoftNceShardPlan q;
+  size_t bytes;
+};
+static SoftNceShardBilinearPlan plan_softnce_shard_bilinear(Workspace& ws, int64_t br, int64_t b, int64_t dx, int64_t dy,
+                                                            int precision) {
+  SoftNceShardBilinearPlan n{};
+  n.p = plan_bilinear(ws, br, b, dx, dy, precision, true, true);
+  n.q = plan_softnce_shard(ws, br, b);
+  n.bytes = ws.off;
+  return n;
+}
+static SeparableChainPlan<SoftNceShardBilinearPlan> plan_softnce_shard_separable(Workspace& ws, int64_t br, int64_t b,
+                                                                                 int64_t k, int precision) {
+  return plan_separable_chain(ws, br, b, k, [&] { return plan_softnce_shard_bilinear(ws, br, b, k, k, precision); });
+}
+
+static int softnce_shard_check(const char* fn, int64_t br, int64_t b, int64_t row_offset, int64_t dx, int64_t dy, int mode,
+                               int precision, float tau, float mix) {
+  int rc = chain_check<SoftNceEst>(fn, br, b, row_offset, dx, dy, mode, precision);
+  if (rc) return rc;
+  rc = softnce_check_targets(fn, b, mode, tau, mix);
+  if (rc) return rc;
+  MI_CHECK_ARG(b < ((int64_t)1 << 24), "%s: b must be below 2^24 on a sharded batch", fn);
+  return MI_OK;
+}
+
+// the label norms of all b samples (z of the rank's rows to target_norm), the rank's scores and records, its part
+static int softnce_shard_fwd_chain(const float* x, const float* y, const float* w, const int64_t* lab_rows,
+                                   const int64_t* lab_cols, int64_t br, int64_t b, int64_t row_offset, int64_t dx,
+                                   int64_t dy, int precision, float tau, float mix, float* part_out, float* lse_rows,
+                                   float* target_norm, const SoftNceShardBilinearPlan& n, hipStream_t st) {
+  const SoftNceShardPlan& q = n.q;
+  int rc = softnce_label_norm(lab_cols, b, tau, chain_16bit_ok(br, b, dx, dy, precision), q.z, q.inv_z, q.rs, target_norm,
+                              row_offset, br, st);
+  if (rc) return rc;
+  rc = chain_scores<SoftNceEst>(x, y, w, nullptr, nullptr, br, b, 0, dx, dy, precision,
+                                softnce_stats_out(q, lab_rows, lab_cols, row_offset, tau, mix), n.p, st);
+  if (rc) return rc;
+  return softnce_rank_part(q, br, b, part_out, lse_rows, st);
 }
 
 // ------------------------------------------------------------------------------------------------ memory-bank InfoNCE
@@ -3140,6 +3221,139 @@ int mi_matrix_posnce_bwd(const float* scores, const int64_t* sid, int64_t b, int
   return MI_OK;
 }
 
+/* Row blocks of a sharded batch (include/mi_critic.h): forward -> part, merge of the gathered parts -> loss and c,
+ * backward from the forward's workspace and the merged c. */
+size_t mi_posnce_part_floats(int64_t b_rows, int64_t b) {
+  if (b_rows <= 0 || b <= 0) return 0;
+  return (size_t)posnce_part_floats(b_rows, b);
+}
+
+size_t mi_posnce_bilinear_shard_workspace_bytes(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, int precision) {
+  if (b_rows <= 0 || b <= 0 || d_img <= 0 || d_txt <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_posnce_shard_bilinear(ws, b_rows, b, d_img, d_txt, precision).bytes + 256;
+}
+
+int mi_posnce_bilinear_shard_fwd(const float* x, const float* y, const float* w, const int64_t* sid_rows,
+                                 const int64_t* sid_cols, int64_t b_rows, int64_t b, int64_t row_offset, int64_t d_img,
+                                 int64_t d_txt, int mode, int precision, float* part_out, float* lse_rows,
+                                 int32_t* n_pos_out, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && sid_rows && sid_cols && part_out && workspace, "mi_posnce_bilinear_shard_fwd: null pointer");
+  int rc = posnce_shard_check("mi_posnce_bilinear_shard_fwd", b_rows, b, row_offset, d_img, d_txt, mode, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(w || d_img == d_txt, "mi_posnce_bilinear_shard_fwd: w == NULL (S = X Y^T) needs d_img == d_txt");
+  Workspace ws(workspace, workspace_bytes);
+  const PosNceShardBilinearPlan n = plan_posnce_shard_bilinear(ws, b_rows, b, d_img, d_txt, precision);
+  rc = ws_fits(ws, "mi_posnce_bilinear_shard_fwd");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  rc = chain_scores<PosNceEst>(x, y, w, nullptr, nullptr, b_rows, b, 0, d_img, d_txt, precision,
+                               posnce_stats_out(n.q, sid_rows, sid_cols), n.p, st);
+  if (rc) return rc;
+  return posnce_rank_part(n.q, b_rows, b, part_out, lse_rows, n_pos_out, st);
+}
+
+int mi_posnce_bilinear_shard_bwd(const float* x, const float* y, const float* w, const int64_t* sid_rows,
+                                 const int64_t* sid_cols, int64_t b_rows, int64_t b, int64_t row_offset, int64_t d_img,
+                                 int64_t d_txt, int mode, int precision, const float* lse_cols, const float* grad_out,
+                                 float* grad_x, float* grad_y, float* grad_w, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+  MI_CHECK_ARG(x && y && sid_rows && sid_cols && grad_x && grad_y && workspace,
+               "mi_posnce_bilinear_shard_bwd: null pointer");
+  int rc = posnce_shard_check("mi_posnce_bilinear_shard_bwd", b_rows, b, row_offset, d_img, d_txt, mode, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || lse_cols, "mi_posnce_bilinear_shard_bwd: the symmetric mode needs lse_cols");
+  MI_CHECK_ARG((w && grad_w) || (!w && !grad_w && d_img == d_txt),
+               "mi_posnce_bilinear_shard_bwd: w != NULL needs grad_w; w == NULL (S = X Y^T) needs d_img == d_txt, no "
+               "grad_w");
+  Workspace ws(workspace, workspace_bytes);
+  const PosNceShardBilinearPlan n = plan_posnce_shard_bilinear(ws, b_rows, b, d_img, d_txt, precision);
+  rc = ws_fits(ws, "mi_posnce_bilinear_shard_bwd");
+  if (rc) return rc;
+  return chain_grads<PosNceEst>(x, y, w, b_rows, b, d_img, d_txt, precision,
+                                posnce_grad_in(sid_rows, sid_cols, n.q.r, lse_cols, n.q.inv_n, nullptr, grad_out, b, mode),
+                                grad_x, grad_y, grad_w, n.p, (hipStream_t)stream);
+}
+
+size_t mi_posnce_merge_workspace_bytes(int64_t b) {
+  if (b <= 0) return 0;
+  return (size_t)(2 * b) * sizeof(float) + 256;
+}
+
+int mi_posnce_merge_parts(const float* parts, int64_t n_ranks, int64_t b_rows, int64_t b, int mode, float* loss_out,
+                          float* lse_cols, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(parts && loss_out && lse_cols && workspace, "mi_posnce_merge_parts: null pointer");
+  MI_CHECK_ARG(n_ranks >= 1 && b_rows >= 1 && b == n_ranks * b_rows,
+               "mi_posnce_merge_parts: need b == n_ranks * b_rows >= 1 (got %lld ranks of %lld rows, b %lld)",
+               (long long)n_ranks, (long long)b_rows, (long long)b);
+  MI_CHECK_ARG(b < ((int64_t)1 << 24), "mi_posnce_merge_parts: b must be below 2^24 on a sharded batch");
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || mode == MI_NCE_SYMMETRIC, "mi_posnce_merge_parts: unknown mode %d", mode);
+  Workspace ws(workspace, workspace_bytes);
+  float* terms = ws.take<float>(2 * b);
+  const int rc = ws_fits(ws, "mi_posnce_merge_parts");
+  if (rc) return rc;
+  return posnce_merge_parts(parts, n_ranks, b_rows, b, mode, loss_out, lse_cols, terms, (hipStream_t)stream);
+}
+
+size_t mi_posnce_separable_shard_workspace_bytes(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj,
+                                                 int precision) {
+  if (b_rows <= 0 || b <= 0 || d_img <= 0 || d_txt <= 0 || d_proj <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_posnce_shard_separable(ws, b_rows, b, d_proj, precision).bytes + 256;
+}
+
+int mi_posnce_separable_shard_fwd(const float* x, const float* y, const float* wg, const float* wh,
+                                  const int64_t* sid_rows, const int64_t* sid_cols, int64_t b_rows, int64_t b,
+                                  int64_t row_offset, int64_t d_img, int64_t d_txt, int64_t d_proj, int mode, int precision,
+                                  float* part_out, float* lse_rows, int32_t* n_pos_out, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && wg && wh && sid_rows && sid_cols && part_out && workspace,
+               "mi_posnce_separable_shard_fwd: null pointer");
+  int rc = posnce_shard_check("mi_posnce_separable_shard_fwd", b_rows, b, row_offset, d_img, d_txt, mode, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(d_proj >= 1, "mi_posnce_separable_shard_fwd: projection width must be >= 1");
+  Workspace ws(workspace, workspace_bytes);
+  const auto sp = plan_posnce_shard_separable(ws, b_rows, b, d_proj, precision);
+  rc = ws_fits(ws, "mi_posnce_separable_shard_fwd");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t k = d_proj;
+  rc = separable_project(PosNceEst::kSep, precision == MI_PREC_BF16, x, y, wg, wh, b_rows, b, d_img, d_txt, k, sp.a, sp.c,
+                         st);
+  if (rc) return rc;
+  rc = chain_scores<PosNceEst>(sp.a, sp.c, nullptr, nullptr, nullptr, b_rows, b, 0, k, k, precision,
+                               posnce_stats_out(sp.n.q, sid_rows, sid_cols), sp.n.p, st);
+  if (rc) return rc;
+  return posnce_rank_part(sp.n.q, b_rows, b, part_out, lse_rows, n_pos_out, st);
+}
+
+int mi_posnce_separable_shard_bwd(const float* x, const float* y, const float* wg, const float* wh,
+                                  const int64_t* sid_rows, const int64_t* sid_cols, int64_t b_rows, int64_t b,
+                                  int64_t row_offset, int64_t d_img, int64_t d_txt, int64_t d_proj, int mode, int precision,
+                                  const float* lse_cols, const float* grad_out, float* grad_x, float* grad_y,
+                                  float* grad_wg, float* grad_wh, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && wg && wh && sid_rows && sid_cols && grad_x && grad_y && grad_wg && grad_wh && workspace,
+               "mi_posnce_separable_shard_bwd: null pointer");
+  int rc = posnce_shard_check("mi_posnce_separable_shard_bwd", b_rows, b, row_offset, d_img, d_txt, mode, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(d_proj >= 1, "mi_posnce_separable_shard_bwd: projection width must be >= 1");
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || lse_cols, "mi_posnce_separable_shard_bwd: the symmetric mode needs lse_cols");
+  Workspace ws(workspace, workspace_bytes);
+  const auto sp = plan_posnce_shard_separable(ws, b_rows, b, d_proj, precision);
+  rc = ws_fits(ws, "mi_posnce_separable_shard_bwd");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t k = d_proj;
+  rc = chain_grads<PosNceEst>(sp.a, sp.c, nullptr, b_rows, b, k, k, precision,
+                              posnce_grad_in(sid_rows, sid_cols, sp.n.q.r, lse_cols, sp.n.q.inv_n, nullptr, grad_out, b,
+                                             mode),
+                              sp.da, sp.dc, nullptr, sp.n.p, st);
+  if (rc) return rc;
+  // dA -> the rank's dX and its partial dWg; the rank's partial dC (all b text rows) -> partial dY and dWh
+  return separable_project_back(PosNceEst::kSep, precision == MI_PREC_BF16, x, y, wg, wh, b_rows, b, d_img, d_txt, k, sp.da,
+                                sp.dc, grad_x, grad_y, grad_wg, grad_wh, st);
+}
+
 // ------------------------------------------------------------------------------------------------ soft-target InfoNCE
 size_t mi_softnce_bilinear_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int precision, int with_grads) {
   if (b <= 0 || d_img <= 0 || d_txt <= 0) return 0;
@@ -3250,6 +3464,142 @@ int mi_matrix_softnce_bwd(const float* scores, const int64_t* label_mask, int64_
   }
   MI_LAUNCH_CHECK("softnce_matrix_grad_kernel");
   return MI_OK;
+}
+
+/* Row blocks of a sharded batch (include/mi_critic.h): forward -> part, merge of the gathered parts -> loss and c,
+ * backward from the forward's workspace and the merged c. */
+size_t mi_softnce_part_floats(int64_t b_rows, int64_t b) {
+  if (b_rows <= 0 || b <= 0) return 0;
+  return (size_t)softnce_part_floats(b_rows, b);
+}
+
+size_t mi_softnce_bilinear_shard_workspace_bytes(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, int precision) {
+  if (b_rows <= 0 || b <= 0 || d_img <= 0 || d_txt <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_softnce_shard_bilinear(ws, b_rows, b, d_img, d_txt, precision).bytes + 256;
+}
+
+int mi_softnce_bilinear_shard_fwd(const float* x, const float* y, const float* w, const int64_t* label_rows,
+                                  const int64_t* label_cols, int64_t b_rows, int64_t b, int64_t row_offset, int64_t d_img,
+                                  int64_t d_txt, int mode, int precision, float tau, float mix, float* part_out,
+                                  float* lse_rows, float* target_norm, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+  MI_CHECK_ARG(x && y && label_rows && label_cols && part_out && workspace, "mi_softnce_bilinear_shard_fwd: null pointer");
+  int rc = softnce_shard_check("mi_softnce_bilinear_shard_fwd", b_rows, b, row_offset, d_img, d_txt, mode, precision, tau,
+                               mix);
+  if (rc) return rc;
+  MI_CHECK_ARG(w || d_img == d_txt, "mi_softnce_bilinear_shard_fwd: w == NULL (S = X Y^T) needs d_img == d_txt");
+  Workspace ws(workspace, workspace_bytes);
+  const SoftNceShardBilinearPlan n = plan_softnce_shard_bilinear(ws, b_rows, b, d_img, d_txt, precision);
+  rc = ws_fits(ws, "mi_softnce_bilinear_shard_fwd");
+  if (rc) return rc;
+  return softnce_shard_fwd_chain(x, y, w, label_rows, label_cols, b_rows, b, row_offset, d_img, d_txt, precision, tau, mix,
+                                 part_out, lse_rows, target_norm, n, (hipStream_t)stream);
+}
+
+int mi_softnce_bilinear_shard_bwd(const float* x, const float* y, const float* w, const int64_t* label_rows,
+                                  const int64_t* label_cols, int64_t b_rows, int64_t b, int64_t row_offset, int64_t d_img,
+                                  int64_t d_txt, int mode, int precision, float tau, float mix, const float* lse_cols,
+                                  const float* grad_out, float* grad_x, float* grad_y, float* grad_w, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && label_rows && label_cols && grad_x && grad_y && workspace,
+               "mi_softnce_bilinear_shard_bwd: null pointer");
+  int rc = softnce_shard_check("mi_softnce_bilinear_shard_bwd", b_rows, b, row_offset, d_img, d_txt, mode, precision, tau,
+                               mix);
+  if (rc) return rc;
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || lse_cols, "mi_softnce_bilinear_shard_bwd: the symmetric mode needs lse_cols");
+  MI_CHECK_ARG((w && grad_w) || (!w && !grad_w && d_img == d_txt),
+               "mi_softnce_bilinear_shard_bwd: w != NULL needs grad_w; w == NULL (S = X Y^T) needs d_img == d_txt, no "
+               "grad_w");
+  Workspace ws(workspace, workspace_bytes);
+  const SoftNceShardBilinearPlan n = plan_softnce_shard_bilinear(ws, b_rows, b, d_img, d_txt, precision);
+  rc = ws_fits(ws, "mi_softnce_bilinear_shard_bwd");
+  if (rc) return rc;
+  return chain_grads<SoftNceEst>(x, y, w, b_rows, b, d_img, d_txt, precision,
+                                 softnce_grad_in(label_rows, label_cols, row_offset, n.q.rs, n.q.inv_z, nullptr, n.q.r,
+                                                 lse_cols, grad_out, b, mode, tau, mix),
+                                 grad_x, grad_y, grad_w, n.p, (hipStream_t)stream);
+}
+
+size_t mi_softnce_merge_workspace_bytes(int64_t b) {
+  if (b <= 0) return 0;
+  return (size_t)(2 * b) * sizeof(float) + 256;
+}
+
+int mi_softnce_merge_parts(const float* parts, int64_t n_ranks, int64_t b_rows, int64_t b, int mode, float* loss_out,
+                           float* lse_cols, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(parts && loss_out && lse_cols && workspace, "mi_softnce_merge_parts: null pointer");
+  MI_CHECK_ARG(n_ranks >= 1 && b_rows >= 1 && b == n_ranks * b_rows,
+               "mi_softnce_merge_parts: need b == n_ranks * b_rows >= 1 (got %lld ranks of %lld rows, b %lld)",
+               (long long)n_ranks, (long long)b_rows, (long long)b);
+  MI_CHECK_ARG(b < ((int64_t)1 << 24), "mi_softnce_merge_parts: b must be below 2^24 on a sharded batch");
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || mode == MI_NCE_SYMMETRIC, "mi_softnce_merge_parts: unknown mode %d", mode);
+  Workspace ws(workspace, workspace_bytes);
+  float* terms = ws.take<float>(2 * b);
+  const int rc = ws_fits(ws, "mi_softnce_merge_parts");
+  if (rc) return rc;
+  return softnce_merge_parts(parts, n_ranks, b_rows, b, mode, loss_out, lse_cols, terms, (hipStream_t)stream);
+}
+
+size_t mi_softnce_separable_shard_workspace_bytes(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj,
+                                                  int precision) {
+  if (b_rows <= 0 || b <= 0 || d_img <= 0 || d_txt <= 0 || d_proj <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_softnce_shard_separable(ws, b_rows, b, d_proj, precision).bytes + 256;
+}
+
+int mi_softnce_separable_shard_fwd(const float* x, const float* y, const float* wg, const float* wh,
+                                   const int64_t* label_rows, const int64_t* label_cols, int64_t b_rows, int64_t b,
+                                   int64_t row_offset, int64_t d_img, int64_t d_txt, int64_t d_proj, int mode,
+                                   int precision, float tau, float mix, float* part_out, float* lse_rows,
+                                   float* target_norm, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && wg && wh && label_rows && label_cols && part_out && workspace,
+               "mi_softnce_separable_shard_fwd: null pointer");
+  int rc = softnce_shard_check("mi_softnce_separable_shard_fwd", b_rows, b, row_offset, d_img, d_txt, mode, precision, tau,
+                               mix);
+  if (rc) return rc;
+  MI_CHECK_ARG(d_proj >= 1, "mi_softnce_separable_shard_fwd: projection width must be >= 1");
+  Workspace ws(workspace, workspace_bytes);
+  const auto sp = plan_softnce_shard_separable(ws, b_rows, b, d_proj, precision);
+  rc = ws_fits(ws, "mi_softnce_separable_shard_fwd");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t k = d_proj;
+  rc = separable_project(SoftNceEst::kSep, precision == MI_PREC_BF16, x, y, wg, wh, b_rows, b, d_img, d_txt, k, sp.a, sp.c,
+                         st);
+  if (rc) return rc;
+  return softnce_shard_fwd_chain(sp.a, sp.c, nullptr, label_rows, label_cols, b_rows, b, row_offset, k, k, precision, tau,
+                                 mix, part_out, lse_rows, target_norm, sp.n, st);
+}
+
+int mi_softnce_separable_shard_bwd(const float* x, const float* y, const float* wg, const float* wh,
+                                   const int64_t* label_rows, const int64_t* label_cols, int64_t b_rows, int64_t b,
+                                   int64_t row_offset, int64_t d_img, int64_t d_txt, int64_t d_proj, int mode,
+                                   int precision, float tau, float mix, const float* lse_cols, const float* grad_out,
+                                   float* grad_x, float* grad_y, float* grad_wg, float* grad_wh, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && wg && wh && label_rows && label_cols && grad_x && grad_y && grad_wg && grad_wh && workspace,
+               "mi_softnce_separable_shard_bwd: null pointer");
+  int rc = softnce_shard_check("mi_softnce_separable_shard_bwd", b_rows, b, row_offset, d_img, d_txt, mode, precision, tau,
+                               mix);
+  if (rc) return rc;
+  MI_CHECK_ARG(d_proj >= 1, "mi_softnce_separable_shard_bwd: projection width must be >= 1");
+  MI_CHECK_ARG(mode == MI_NCE_ROWWISE || lse_cols, "mi_softnce_separable_shard_bwd: the symmetric mode needs lse_cols");
+  Workspace ws(workspace, workspace_bytes);
+  const auto sp = plan_softnce_shard_separable(ws, b_rows, b, d_proj, precision);
+  rc = ws_fits(ws, "mi_softnce_separable_shard_bwd");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t k = d_proj;
+  const SoftNceShardPlan& q = sp.n.q;
+  rc = chain_grads<SoftNceEst>(sp.a, sp.c, nullptr, b_rows, b, k, k, precision,
+                               softnce_grad_in(label_rows, label_cols, row_offset, q.rs, q.inv_z, nullptr, q.r, lse_cols,
+                                               grad_out, b, mode, tau, mix),
+                               sp.da, sp.dc, nullptr, sp.n.p, st);
+  if (rc) return rc;
+  // dA -> the rank's dX and its partial dWg; the rank's partial dC (all b text rows) -> partial dY and dWh
+  return separable_project_back(SoftNceEst::kSep, precision == MI_PREC_BF16, x, y, wg, wh, b_rows, b, d_img, d_txt, k, sp.da,
+                                sp.dc, grad_x, grad_y, grad_wg, grad_wh, st);
 }
 
 // ------------------------------------------------------------------------------------------------ memory-bank InfoNCE

@@ -10,13 +10,19 @@
 // pairs enter the denominators, and they share the positive weight.  All ids equal: t_i = r_i - mean_j S[i, j] >= log B,
 // not zero.  B == 1: loss exactly 0 and exact-zero gradients (m = S_00, s = 1, logf(1) = 0, exp2(0) - 1 = 0).  Each row's
 // share of dL/dS sums to zero.  A training loss, not an MI bound: log B - L bounds nothing once some n_i > 1.
-// Building blocks (written for the MFMA 32x32 accumulator layout that nce_tile_stats documents), whole batch only:
+// Building blocks (written for the MFMA 32x32 accumulator layout that nce_tile_stats documents):
 //   posnce_tile_stats:   one 64 x 64 wave tile -> per-row (max, sum exp) over ALL in-range columns of the tile and a
 //                        positive record (sum S, count) over its same-id columns; the same per column over its rows.
 //                        Positives may sit in any tile; a tile without one (a wave-uniform vote) stores zero records
 //   posnce_merge_kernel: the records of every tile, in tile order -> r, c, n_pos, 1/n, the per-sample terms
 //                        -> nce_loss_kernel (fixed order everywhere, no float atomics: bit-reproducible)
 //   posnce_tile_grad:    one wave tile of recomputed scores -> G = grad_out * dL/dS from r, c and 1/n of the row
+// Row blocks (the sharded step): the tiles of rows [row_offset, row_offset + M) of the global B x B
+// matrix, with the ids of the block's rows and of every column.  Positives are found by id, so no offset enters a tile: a
+// row sees all of its columns (r_i, n_i and t_i are complete on the owning rank), a column only this rank's rows.  The
+// whole batch is sid_rows == sid_cols.
+//   posnce_rank_part_kernel:   a rank's records -> r and 1/n (kept), one flat part (column partials, row terms, counts)
+//   posnce_merge_parts_kernel: the parts of every rank, in rank order -> c, the per-sample terms -> nce_loss_kernel
 //   EpiPosNceStats<FAST> / EpiPosNceGrad<TG> / EpiPosNceGrad2: the epilogues of the score GEMM and of the G GEMM on the
 //                        generic kernels and on the 16-bit chain
 #pragma once
@@ -31,22 +37,24 @@ struct PosRec {
 };
 
 struct PosNceStatsOut {
-  const int64_t* sid;  // [B] (rows and columns index the same samples)
-  NceRec* rowp;        // [B][n_t]: row i over the columns of tile t
-  NceRec* colp;        // [B][n_t]: column j over the rows of tile t
-  PosRec* rowq;        // [B][n_t]: the positives of row i among the columns of tile t
-  PosRec* colq;        // [B][n_t]: the positives of column j among the rows of tile t
-  int64_t n_t;
+  const int64_t* sid_rows;  // [M]
+  const int64_t* sid_cols;  // [N] (the whole batch: the same array)
+  NceRec* rowp;             // [M][n_ct]: row i over the columns of tile t
+  NceRec* colp;             // [N][n_rt]: column j over the rows of tile t
+  PosRec* rowq;             // [M][n_ct]: the positives of row i among the columns of tile t
+  PosRec* colq;             // [N][n_rt]: the positives of column j among the rows of tile t
+  int64_t n_ct, n_rt;
 };
 
 struct PosNceGradIn {
-  const int64_t* sid;     // [B]
-  const float* r;         // [B] row LSE
-  const float* c;         // [B] column LSE (symmetric mode)
-  const float* inv_n;     // [B] 1 / n_i, or null: then from n_pos
-  const int32_t* n_pos;   // [B] n_i (read where inv_n is null)
-  const float* grad_out;  // [1] or null (1)
-  float wr, wc;
+  const int64_t* sid_rows;  // [M]
+  const int64_t* sid_cols;  // [N]
+  const float* r;           // [M] row LSE
+  const float* c;           // [N] column LSE (symmetric mode)
+  const float* inv_n;       // [M] 1 / n_i of the rows, or null: then from n_pos
+  const int32_t* n_pos;     // [M] n_i (read where inv_n is null)
+  const float* grad_out;    // [1] or null (1)
+  float wr, wc;             // 1/B, 0 (rowwise) or 1/(2B), 1/(2B) (symmetric); B is the global batch
 };
 
 // acc element (tm, tn, r) of this lane: as nce_tile_stats.  Consumes acc.  No block-level barrier.
@@ -61,7 +69,7 @@ __device__ __forceinline__ void posnce_tile_stats(f32x16 (&acc)[2][2], int64_t m
   for (int tn = 0; tn < 2; ++tn) {
     const int64_t col = nb + tn * 32 + col_l;
     cok[tn] = col < N;
-    sc[tn] = cok[tn] ? o.sid[col] : 0;
+    sc[tn] = cok[tn] ? o.sid_cols[col] : 0;
   }
   // the only mask: elements outside M x N become -inf.  pm[tn] bit (tm 16 + r): that element is a same-id pair
   uint32_t pm[2] = {0u, 0u};
@@ -71,7 +79,7 @@ __device__ __forceinline__ void posnce_tile_stats(f32x16 (&acc)[2][2], int64_t m
     for (int r = 0; r < 16; ++r) {
       const int64_t row = mb + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
       const bool rok = row < M;
-      const int64_t sr = rok ? o.sid[row] : 0;
+      const int64_t sr = rok ? o.sid_rows[row] : 0;
 #pragma unroll
       for (int tn = 0; tn < 2; ++tn) {
         const bool ok = rok && cok[tn];
@@ -111,8 +119,8 @@ __device__ __forceinline__ void posnce_tile_stats(f32x16 (&acc)[2][2], int64_t m
         }
         const int64_t row = mb + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
         if (col_l == 0 && row < M) {
-          o.rowp[row * o.n_t + t] = NceRec{m, s};
-          o.rowq[row * o.n_t + t] = q;
+          o.rowp[row * o.n_ct + t] = NceRec{m, s};
+          o.rowq[row * o.n_ct + t] = q;
         }
       }
   }
@@ -150,8 +158,8 @@ __device__ __forceinline__ void posnce_tile_stats(f32x16 (&acc)[2][2], int64_t m
       }
       const int64_t col = nb + tn * 32 + col_l;
       if (half == 0 && col < N) {
-        o.colp[col * o.n_t + t] = NceRec{m, s};
-        o.colq[col * o.n_t + t] = q;
+        o.colp[col * o.n_rt + t] = NceRec{m, s};
+        o.colq[col * o.n_rt + t] = q;
       }
     }
   }
@@ -174,7 +182,7 @@ __device__ __forceinline__ void posnce_tile_grad(f32x16 (&acc)[2][2], int64_t mb
   for (int tn = 0; tn < 2; ++tn) {
     const int64_t col = nb + tn * 32 + col_l;
     cok[tn] = col < N;
-    sc[tn] = cok[tn] ? g.sid[col] : 0;
+    sc[tn] = cok[tn] ? g.sid_cols[col] : 0;
     cc[tn] = cok[tn] && cols ? g.c[col] : 0.0f;
   }
 #pragma unroll
@@ -183,7 +191,7 @@ __device__ __forceinline__ void posnce_tile_grad(f32x16 (&acc)[2][2], int64_t mb
     for (int r = 0; r < 16; ++r) {
       const int64_t row = mb + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
       const bool rok = row < M;
-      const int64_t sr = rok ? g.sid[row] : 0;
+      const int64_t sr = rok ? g.sid_rows[row] : 0;
       const float rr = rok ? g.r[row] : 0.0f;
       const float inv = !rok ? 0.0f : g.inv_n ? g.inv_n[row] : 1.0f / (float)g.n_pos[row];
 #pragma unroll
@@ -310,6 +318,79 @@ static __global__ __launch_bounds__(256) void posnce_merge_kernel(const NceRec* 
   terms[k] = lse - ps / (float)pc;
 }
 
+// ------------------------------------------------------------------------------------------------ row blocks
+// The part of one rank (posnce_part_floats(br, b) floats, gathered in rank order by the caller):
+//   [0, 2b)                  column j: (m, s) over this rank's rows, merged in row-tile order (NceRec)
+//   [2b, 3b)                 column j: sum of S[p, j] over this rank's rows p with sid_p == sid_j, in row-tile order
+//   [3b, 3b + br)            row term t_i = r_i - (1/n_i) sum_{p in P_i} S[i, p] of local row i (complete on this rank)
+//   [3b + br, 3b + 2 br)     n_i of local row i as a float (exact below 2^24: the entry points refuse larger b); it is
+//                            also the count of column row_offset + i, the same sample
+__host__ __device__ inline int64_t posnce_part_floats(int64_t br, int64_t b) { return 3 * b + 2 * br; }
+
+// thread k < br: local row k (records merged and positives added in tile order exactly as posnce_merge_kernel: the same
+// r, n and term bits), br <= k < br + b: column k - br over this rank's row tiles
+static __global__ __launch_bounds__(256) void posnce_rank_part_kernel(const NceRec* __restrict__ rowp,
+                                                                      const NceRec* __restrict__ colp,
+                                                                      const PosRec* __restrict__ rowq,
+                                                                      const PosRec* __restrict__ colq, int64_t br,
+                                                                      int64_t b, int64_t n_ct, int64_t n_rt, float* r_ws,
+                                                                      float* inv_n, float* r_out, int32_t* n_pos_out,
+                                                                      float* __restrict__ part) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= br + b) return;
+  const bool is_row = k < br;
+  const int64_t i = is_row ? k : k - br;
+  const int64_t n = is_row ? n_ct : n_rt;
+  const NceRec* p = (is_row ? rowp : colp) + i * n;
+  const PosRec* q = (is_row ? rowq : colq) + i * n;
+  float m = MI_NEG_INF, s = 0.0f, ps = 0.0f;
+  int32_t pc = 0;
+  for (int64_t t = 0; t < n; ++t) {
+    lse_merge(m, s, p[t].m, p[t].s);
+    ps += q[t].sum;
+    pc += q[t].count;
+  }
+  if (!is_row) {
+    part[2 * i] = m;
+    part[2 * i + 1] = s;
+    part[2 * b + i] = ps;
+    return;
+  }
+  const float lse = s > 0.0f ? m + logf(s) : MI_NEG_INF;
+  r_ws[i] = lse;
+  if (r_out) r_out[i] = lse;
+  inv_n[i] = 1.0f / (float)pc;
+  if (n_pos_out) n_pos_out[i] = pc;
+  part[3 * b + i] = lse - ps / (float)pc;
+  part[3 * b + br + i] = (float)pc;
+}
+
+// parts [n_ranks][posnce_part_floats(br, b)] in rank order (rank g holds rows [g br, (g + 1) br)).  Thread k < b: the row
+// term of sample k, copied; b <= k < 2b: column j = k - b, its (m, s) merged and its positive scores added in rank order
+// from an empty (-inf, 0), 0 start -- exact for one rank, so one rank gives the bits of posnce_merge_kernel -- then c_j
+// and its term c_j - sum / n_j (n_j from the part of the rank that owns sample j).  Every rank runs this on the same
+// gathered buffer: identical bits.
+static __global__ __launch_bounds__(256) void posnce_merge_parts_kernel(const float* __restrict__ parts, int64_t n_ranks,
+                                                                        int64_t br, int64_t b, float* c_out,
+                                                                        float* __restrict__ terms) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= 2 * b) return;
+  const int64_t pf = posnce_part_floats(br, b);
+  if (k < b) {
+    terms[k] = parts[(k / br) * pf + 3 * b + k % br];
+    return;
+  }
+  const int64_t j = k - b;
+  float m = MI_NEG_INF, s = 0.0f, ps = 0.0f;
+  for (int64_t g = 0; g < n_ranks; ++g) {
+    lse_merge(m, s, parts[g * pf + 2 * j], parts[g * pf + 2 * j + 1]);
+    ps += parts[g * pf + 2 * b + j];
+  }
+  const float lse = s > 0.0f ? m + logf(s) : MI_NEG_INF;
+  c_out[j] = lse;
+  terms[k] = lse - ps / parts[(j / br) * pf + 3 * b + br + j % br];
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 struct PosNcePlan {
   NceRec* rowp;
@@ -335,14 +416,21 @@ static inline PosNcePlan plan_posnce(Workspace& ws, int64_t b) {
 }
 
 static inline PosNceStatsOut posnce_stats_out(const PosNcePlan& q, const int64_t* sid) {
-  return PosNceStatsOut{sid, q.rowp, q.colp, q.rowq, q.colq, q.n_t};
+  return PosNceStatsOut{sid, sid, q.rowp, q.colp, q.rowq, q.colq, q.n_t, q.n_t};
 }
 
+// b: the GLOBAL batch (the loss weights); a row block passes its own ids and the global ids
+static inline PosNceGradIn posnce_grad_in(const int64_t* sid_rows, const int64_t* sid_cols, const float* r, const float* c,
+                                          const float* inv_n, const int32_t* n_pos, const float* grad_out, int64_t b,
+                                          int mode) {
+  const float fb = (float)b;
+  if (mode == MI_NCE_SYMMETRIC)
+    return PosNceGradIn{sid_rows, sid_cols, r, c, inv_n, n_pos, grad_out, 0.5f / fb, 0.5f / fb};
+  return PosNceGradIn{sid_rows, sid_cols, r, c, inv_n, n_pos, grad_out, 1.0f / fb, 0.0f};
+}
 static inline PosNceGradIn posnce_grad_in(const int64_t* sid, const float* r, const float* c, const float* inv_n,
                                           const int32_t* n_pos, const float* grad_out, int64_t b, int mode) {
-  const float fb = (float)b;
-  if (mode == MI_NCE_SYMMETRIC) return PosNceGradIn{sid, r, c, inv_n, n_pos, grad_out, 0.5f / fb, 0.5f / fb};
-  return PosNceGradIn{sid, r, c, inv_n, n_pos, grad_out, 1.0f / fb, 0.0f};
+  return posnce_grad_in(sid, sid, r, c, inv_n, n_pos, grad_out, b, mode);
 }
 
 // records -> r, c, n_pos (workspace and the caller's optional copies), loss
@@ -357,6 +445,63 @@ static inline int posnce_finish(const PosNcePlan& q, int64_t b, int mode, float*
   {
     ProfScope prof_("nce_loss_kernel", st);
     hipLaunchKernelGGL(nce_loss_kernel, dim3(1), dim3(256), 0, st, q.terms, b, mode == MI_NCE_SYMMETRIC ? 1 : 0, loss_out);
+  }
+  MI_LAUNCH_CHECK("nce_loss_kernel");
+  return MI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ row blocks, host side
+// The records of one rank's row block [br] x [b], the row LSE r and 1 / n of its rows: the forward writes r and 1 / n,
+// the backward reads them from the same workspace (the same plan gives the same offsets).
+struct PosNceShardPlan {
+  NceRec* rowp;  // [br][n_ct]
+  NceRec* colp;  // [b][n_rt]
+  PosRec* rowq;  // [br][n_ct]
+  PosRec* colq;  // [b][n_rt]
+  float *r, *inv_n;
+  int64_t n_ct, n_rt;
+};
+
+static inline PosNceShardPlan plan_posnce_shard(Workspace& ws, int64_t br, int64_t b) {
+  PosNceShardPlan q{};
+  q.n_ct = (b + 63) / 64;
+  q.n_rt = (br + 63) / 64;
+  q.rowp = ws.take<NceRec>(br * q.n_ct);
+  q.colp = ws.take<NceRec>(b * q.n_rt);
+  q.rowq = ws.take<PosRec>(br * q.n_ct);
+  q.colq = ws.take<PosRec>(b * q.n_rt);
+  q.r = ws.take<float>(br);
+  q.inv_n = ws.take<float>(br);
+  return q;
+}
+
+static inline PosNceStatsOut posnce_stats_out(const PosNceShardPlan& q, const int64_t* sid_rows, const int64_t* sid_cols) {
+  return PosNceStatsOut{sid_rows, sid_cols, q.rowp, q.colp, q.rowq, q.colq, q.n_ct, q.n_rt};
+}
+
+static inline int posnce_rank_part(const PosNceShardPlan& q, int64_t br, int64_t b, float* part_out, float* lse_rows,
+                                   int32_t* n_pos_out, hipStream_t st) {
+  {
+    ProfScope prof_("posnce_rank_part_kernel", st);
+    hipLaunchKernelGGL(posnce_rank_part_kernel, dim3((unsigned)((br + b + 255) / 256)), dim3(256), 0, st, q.rowp, q.colp,
+                       q.rowq, q.colq, br, b, q.n_ct, q.n_rt, q.r, q.inv_n, lse_rows, n_pos_out, part_out);
+  }
+  MI_LAUNCH_CHECK("posnce_rank_part_kernel");
+  return MI_OK;
+}
+
+// terms: [2b] scratch
+static inline int posnce_merge_parts(const float* parts, int64_t n_ranks, int64_t br, int64_t b, int mode, float* loss_out,
+                                     float* lse_cols, float* terms, hipStream_t st) {
+  {
+    ProfScope prof_("posnce_merge_parts_kernel", st);
+    hipLaunchKernelGGL(posnce_merge_parts_kernel, dim3((unsigned)((2 * b + 255) / 256)), dim3(256), 0, st, parts, n_ranks,
+                       br, b, lse_cols, terms);
+  }
+  MI_LAUNCH_CHECK("posnce_merge_parts_kernel");
+  {
+    ProfScope prof_("nce_loss_kernel", st);
+    hipLaunchKernelGGL(nce_loss_kernel, dim3(1), dim3(256), 0, st, terms, b, mode == MI_NCE_SYMMETRIC ? 1 : 0, loss_out);
   }
   MI_LAUNCH_CHECK("nce_loss_kernel");
   return MI_OK;

@@ -211,6 +211,15 @@ SIGNATURES = {
     "mi_matrix_posnce_workspace_bytes": (_SZ, [_I64]),
     "mi_matrix_posnce_fwd": (c_int, [_P, _P, _I64, _I] + [_P] * 5 + [_SZ, _P]),
     "mi_matrix_posnce_bwd": (c_int, [_P, _P, _I64, _I] + [_P] * 6),
+    "mi_posnce_part_floats": (_SZ, [_I64, _I64]),
+    "mi_posnce_bilinear_shard_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I]),
+    "mi_posnce_bilinear_shard_fwd": (c_int, [_P] * 5 + [_I64] * 5 + [_I, _I] + [_P] * 4 + [_SZ, _P]),
+    "mi_posnce_bilinear_shard_bwd": (c_int, [_P] * 5 + [_I64] * 5 + [_I, _I] + [_P] * 6 + [_SZ, _P]),
+    "mi_posnce_merge_workspace_bytes": (_SZ, [_I64]),
+    "mi_posnce_merge_parts": (c_int, [_P, _I64, _I64, _I64, _I, _P, _P, _P, _SZ, _P]),
+    "mi_posnce_separable_shard_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I64, _I]),
+    "mi_posnce_separable_shard_fwd": (c_int, [_P] * 6 + [_I64] * 6 + [_I, _I] + [_P] * 4 + [_SZ, _P]),
+    "mi_posnce_separable_shard_bwd": (c_int, [_P] * 6 + [_I64] * 6 + [_I, _I] + [_P] * 7 + [_SZ, _P]),
     "mi_softnce_bilinear_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I, _I]),
     "mi_softnce_bilinear_step": (c_int, [_P] * 4 + [_I64] * 3 + [_I, _I, c_float, c_float] + [_P] * 9 + [_SZ, _P]),
     "mi_softnce_separable_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I, _I]),
@@ -218,6 +227,15 @@ SIGNATURES = {
     "mi_matrix_softnce_workspace_bytes": (_SZ, [_I64]),
     "mi_matrix_softnce_fwd": (c_int, [_P, _P, _I64, _I, c_float, c_float] + [_P] * 5 + [_SZ, _P]),
     "mi_matrix_softnce_bwd": (c_int, [_P, _P, _I64, _I, c_float, c_float] + [_P] * 6),
+    "mi_softnce_part_floats": (_SZ, [_I64, _I64]),
+    "mi_softnce_bilinear_shard_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I]),
+    "mi_softnce_bilinear_shard_fwd": (c_int, [_P] * 5 + [_I64] * 5 + [_I, _I, c_float, c_float] + [_P] * 4 + [_SZ, _P]),
+    "mi_softnce_bilinear_shard_bwd": (c_int, [_P] * 5 + [_I64] * 5 + [_I, _I, c_float, c_float] + [_P] * 6 + [_SZ, _P]),
+    "mi_softnce_merge_workspace_bytes": (_SZ, [_I64]),
+    "mi_softnce_merge_parts": (c_int, [_P, _I64, _I64, _I64, _I, _P, _P, _P, _SZ, _P]),
+    "mi_softnce_separable_shard_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I64, _I]),
+    "mi_softnce_separable_shard_fwd": (c_int, [_P] * 6 + [_I64] * 6 + [_I, _I, c_float, c_float] + [_P] * 4 + [_SZ, _P]),
+    "mi_softnce_separable_shard_bwd": (c_int, [_P] * 6 + [_I64] * 6 + [_I, _I, c_float, c_float] + [_P] * 7 + [_SZ, _P]),
 }
 MI_TOPK_MAX_K = 32  # include/mi_critic.h
 MI_SOFTNCE_MAX_LABELS = 63  # include/mi_critic.h

@@ -330,6 +330,66 @@ class _HipOps:
         self.nce_bwd_call(saved, lse_cols, grad_out, out)()
         return out
 
+    # ---------------------------------------------- study-positive InfoNCE on a row block (distributed.GlobalBatchPosNceFn)
+    def posnce_forward(self, x, y_all, params, sid_rows, sid_all, row_offset, mode, precision, need_grad=True):
+        """The row block's part (``mi_posnce_part_floats`` floats, gathered in rank order by the caller), its row LSEs and
+        positive counts: (part, lse_rows [b_rows], n_pos int32 [b_rows], saved).  ``saved`` holds the workspace the
+        backward goes on with."""
+        br, b, dev = x.shape[0], y_all.shape[0], x.device
+        ws = _hip.workspace(self.posnce_shard_workspace_bytes(br, b, x.shape[1], y_all.shape[1], params, precision), dev)
+        part = torch.empty(_hip.load().mi_posnce_part_floats(br, b), dtype=torch.float32, device=dev)
+        r = torch.empty(br, dtype=torch.float32, device=dev)
+        n_pos = torch.empty(br, dtype=torch.int32, device=dev)
+        self.posnce_fwd_call(x, y_all, params, sid_rows, sid_all, row_offset, mode, precision, part, r, n_pos, ws)()
+        return part, r, n_pos, (x, y_all, list(params), sid_rows, sid_all, row_offset, mode, precision, ws)
+
+    @staticmethod
+    def _merge_parts(entry, parts, b_rows, mode):
+        dev, b = parts.device, parts.shape[0] * b_rows
+        loss, c = torch.empty(1, dtype=torch.float32, device=dev), torch.empty(b, dtype=torch.float32, device=dev)
+        ws = _hip.workspace(getattr(_hip.load(), f"{entry}_merge_workspace_bytes")(b), dev)
+        _hip.call(f"{entry}_merge_parts", dev, parts.data_ptr(), parts.shape[0], b_rows, b, mode, loss.data_ptr(),
+                  c.data_ptr(), ws.data_ptr(), ws.numel())
+        return loss, c
+
+    @classmethod
+    def posnce_merge(cls, parts, b_rows, mode):
+        """parts [n_ranks, P] in rank order -> (loss [1], lse_cols [b]); identical bits on every rank."""
+        return cls._merge_parts("mi_posnce", parts, b_rows, mode)
+
+    def posnce_backward(self, saved, lse_cols, grad_out, out=None):
+        """(grad_x, grad_y partial over this row block, [grad_params...] partial) of grad_out[0] * loss."""
+        x, y_all, params = saved[:3]
+        if out is None:
+            out = (torch.empty_like(x), torch.empty_like(y_all), [torch.empty_like(p) for p in params])
+        self.posnce_bwd_call(saved, lse_cols, grad_out, out)()
+        return out
+
+    # ---------------------------------------------- soft-target InfoNCE on a row block (distributed_label_targets.GlobalBatchSoftNceFn)
+    def softnce_forward(self, x, y_all, params, lab_rows, lab_all, row_offset, mode, precision, tau, mix, need_grad=True):
+        """The row block's part (``mi_softnce_part_floats`` floats, gathered in rank order by the caller), its row LSEs and
+        target norms: (part, lse_rows [b_rows], target_norm [b_rows], saved).  ``saved`` holds the workspace the backward
+        goes on with."""
+        br, b, dev = x.shape[0], y_all.shape[0], x.device
+        ws = _hip.workspace(self.softnce_shard_workspace_bytes(br, b, x.shape[1], y_all.shape[1], params, precision), dev)
+        part = torch.empty(_hip.load().mi_softnce_part_floats(br, b), dtype=torch.float32, device=dev)
+        r, z = torch.empty(br, dtype=torch.float32, device=dev), torch.empty(br, dtype=torch.float32, device=dev)
+        self.softnce_fwd_call(x, y_all, params, lab_rows, lab_all, row_offset, mode, precision, tau, mix, part, r, z, ws)()
+        return part, r, z, (x, y_all, list(params), lab_rows, lab_all, row_offset, mode, precision, tau, mix, ws)
+
+    @classmethod
+    def softnce_merge(cls, parts, b_rows, mode):
+        """parts [n_ranks, P] in rank order -> (loss [1], lse_cols [b]); identical bits on every rank."""
+        return cls._merge_parts("mi_softnce", parts, b_rows, mode)
+
+    def softnce_backward(self, saved, lse_cols, grad_out, out=None):
+        """(grad_x, grad_y partial over this row block, [grad_params...] partial) of grad_out[0] * loss."""
+        x, y_all, params = saved[:3]
+        if out is None:
+            out = (torch.empty_like(x), torch.empty_like(y_all), [torch.empty_like(p) for p in params])
+        self.softnce_bwd_call(saved, lse_cols, grad_out, out)()
+        return out
+
 
 class HipBilinearOps(_HipOps):
     """S = (X W) Y^T row block; params = [W] ([] on one GPU: S = X Y^T)."""
@@ -476,6 +536,42 @@ class HipBilinearOps(_HipOps):
                      sid_rows.data_ptr(), sid_all.data_ptr(), x.shape[0], y.shape[0], row_offset, x.shape[1], y.shape[1],
                      mode, precision, lse_cols.data_ptr(), grad_out.data_ptr(), gx.data_ptr(), gy.data_ptr(),
                      _p(gp[0] if gp else None), ws.data_ptr(), ws.numel())
+
+    @staticmethod
+    def posnce_shard_workspace_bytes(br, b, dx, dy, params, precision):
+        return _hip.load().mi_posnce_bilinear_shard_workspace_bytes(br, b, dx, dy, precision)
+
+    def posnce_fwd_call(self, x, y, params, sid_rows, sid_all, row_offset, mode, precision, part, r, n_pos, ws):
+        return _call("mi_posnce_bilinear_shard_fwd", x.device, x.data_ptr(), y.data_ptr(),
+                     _p(params[0] if params else None), sid_rows.data_ptr(), sid_all.data_ptr(), x.shape[0], y.shape[0],
+                     row_offset, x.shape[1], y.shape[1], mode, precision, part.data_ptr(), _p(r), _p(n_pos), ws.data_ptr(),
+                     ws.numel())
+
+    def posnce_bwd_call(self, saved, lse_cols, grad_out, out):
+        x, y, params, sid_rows, sid_all, row_offset, mode, precision, ws = saved
+        gx, gy, gp = out
+        return _call("mi_posnce_bilinear_shard_bwd", x.device, x.data_ptr(), y.data_ptr(),
+                     _p(params[0] if params else None), sid_rows.data_ptr(), sid_all.data_ptr(), x.shape[0], y.shape[0],
+                     row_offset, x.shape[1], y.shape[1], mode, precision, _p(lse_cols), _p(grad_out), gx.data_ptr(),
+                     gy.data_ptr(), _p(gp[0] if gp else None), ws.data_ptr(), ws.numel())
+
+    @staticmethod
+    def softnce_shard_workspace_bytes(br, b, dx, dy, params, precision):
+        return _hip.load().mi_softnce_bilinear_shard_workspace_bytes(br, b, dx, dy, precision)
+
+    def softnce_fwd_call(self, x, y, params, lab_rows, lab_all, row_offset, mode, precision, tau, mix, part, r, z, ws):
+        return _call("mi_softnce_bilinear_shard_fwd", x.device, x.data_ptr(), y.data_ptr(),
+                     _p(params[0] if params else None), lab_rows.data_ptr(), lab_all.data_ptr(), x.shape[0], y.shape[0],
+                     row_offset, x.shape[1], y.shape[1], mode, precision, tau, mix, part.data_ptr(), _p(r), _p(z),
+                     ws.data_ptr(), ws.numel())
+
+    def softnce_bwd_call(self, saved, lse_cols, grad_out, out):
+        x, y, params, lab_rows, lab_all, row_offset, mode, precision, tau, mix, ws = saved
+        gx, gy, gp = out
+        return _call("mi_softnce_bilinear_shard_bwd", x.device, x.data_ptr(), y.data_ptr(),
+                     _p(params[0] if params else None), lab_rows.data_ptr(), lab_all.data_ptr(), x.shape[0], y.shape[0],
+                     row_offset, x.shape[1], y.shape[1], mode, precision, tau, mix, _p(lse_cols), _p(grad_out),
+                     gx.data_ptr(), gy.data_ptr(), _p(gp[0] if gp else None), ws.data_ptr(), ws.numel())
 
     # ------------------------------------------------------------------------------------------ sharded extras
     def prep_local(self, x, params, b, precision) -> bool:
@@ -708,6 +804,42 @@ class HipSeparableOps(_HipOps):
                      sid_rows.data_ptr(), sid_all.data_ptr(), x.shape[0], y.shape[0], row_offset, x.shape[1], y.shape[1],
                      wg.shape[1], mode, precision, lse_cols.data_ptr(), grad_out.data_ptr(), gx.data_ptr(),
                      gy.data_ptr(), gg.data_ptr(), gh.data_ptr(), ws.data_ptr(), ws.numel())
+
+    @staticmethod
+    def posnce_shard_workspace_bytes(br, b, dx, dy, params, precision):
+        return _hip.load().mi_posnce_separable_shard_workspace_bytes(br, b, dx, dy, params[0].shape[1], precision)
+
+    def posnce_fwd_call(self, x, y, params, sid_rows, sid_all, row_offset, mode, precision, part, r, n_pos, ws):
+        wg, wh = params
+        return _call("mi_posnce_separable_shard_fwd", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
+                     sid_rows.data_ptr(), sid_all.data_ptr(), x.shape[0], y.shape[0], row_offset, x.shape[1], y.shape[1],
+                     wg.shape[1], mode, precision, part.data_ptr(), _p(r), _p(n_pos), ws.data_ptr(), ws.numel())
+
+    def posnce_bwd_call(self, saved, lse_cols, grad_out, out):
+        x, y, (wg, wh), sid_rows, sid_all, row_offset, mode, precision, ws = saved
+        gx, gy, (gg, gh) = out
+        return _call("mi_posnce_separable_shard_bwd", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
+                     sid_rows.data_ptr(), sid_all.data_ptr(), x.shape[0], y.shape[0], row_offset, x.shape[1], y.shape[1],
+                     wg.shape[1], mode, precision, _p(lse_cols), _p(grad_out), gx.data_ptr(), gy.data_ptr(),
+                     gg.data_ptr(), gh.data_ptr(), ws.data_ptr(), ws.numel())
+
+    @staticmethod
+    def softnce_shard_workspace_bytes(br, b, dx, dy, params, precision):
+        return _hip.load().mi_softnce_separable_shard_workspace_bytes(br, b, dx, dy, params[0].shape[1], precision)
+
+    def softnce_fwd_call(self, x, y, params, lab_rows, lab_all, row_offset, mode, precision, tau, mix, part, r, z, ws):
+        wg, wh = params
+        return _call("mi_softnce_separable_shard_fwd", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
+                     lab_rows.data_ptr(), lab_all.data_ptr(), x.shape[0], y.shape[0], row_offset, x.shape[1], y.shape[1],
+                     wg.shape[1], mode, precision, tau, mix, part.data_ptr(), _p(r), _p(z), ws.data_ptr(), ws.numel())
+
+    def softnce_bwd_call(self, saved, lse_cols, grad_out, out):
+        x, y, (wg, wh), lab_rows, lab_all, row_offset, mode, precision, tau, mix, ws = saved
+        gx, gy, (gg, gh) = out
+        return _call("mi_softnce_separable_shard_bwd", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
+                     lab_rows.data_ptr(), lab_all.data_ptr(), x.shape[0], y.shape[0], row_offset, x.shape[1], y.shape[1],
+                     wg.shape[1], mode, precision, tau, mix, _p(lse_cols), _p(grad_out), gx.data_ptr(), gy.data_ptr(),
+                     gg.data_ptr(), gh.data_ptr(), ws.data_ptr(), ws.numel())
 
 
 class HipConcatMlpOps(_HipOps):

@@ -251,6 +251,104 @@ def global_batch_mi_bound(embedding_img, embedding_txt, study_id_codes, critic_p
     return (loss, stats[0] if len(stats) == 1 else tuple(stats)) if return_stats else loss
 
 
+def _gather_block_inputs(group, y, codes):
+    """The two input all-gathers of a row-block step, both in flight at once: (y_all [B, d_txt], codes_all [B])."""
+    y_all, work_y = _all_gather_rows(y, group, async_op=True)
+    codes_all, work_c = _all_gather_rows(codes, group, async_op=True)
+    work_y.wait()
+    work_c.wait()
+    return y_all, codes_all
+
+
+def _exchange_block_gradients(group, param_like, gx, gy_partial, gparams):
+    """dY partial -> reduce-scatter, the parameter gradients -> ONE flat all-reduce: (gx, gy, *gparams)."""
+    flat, views = flat_views(param_like)
+    if flat is not None:
+        for v, g in zip(views, gparams):
+            v.copy_(g)
+        gparams = views
+    gy = _reduce_scatter_rows(gy_partial, group)
+    if flat is not None:
+        dist.all_reduce(flat, group=group)
+    return (gx, gy, *gparams)
+
+
+class GlobalBatchPosNceFn(torch.autograd.Function):
+    """Study-positive InfoNCE over the GLOBAL batch from this rank's row block (DESIGN.md section
+    5); the label-weighted InfoNCE of section 16 has the same protocol in ``distributed_label_targets``.  Returns (loss [1], lse_rows [b_rows], lse_cols [B], n_pos int32 [b_rows]).
+
+    forward : all-gather Y and the ids; the rank's scores -> one flat part (column LSE partials, column positive-score
+              partials, row terms, row counts); all-gather the parts; merge them in rank order -> c, loss (identical bits
+              on every rank).
+    backward: the rank's gradients from its r, 1/n and the merged c -> dX complete, dY partial (reduce-scatter),
+              parameter gradients partial (one flat all-reduce).  Five collectives per step, as GlobalBatchNceFn's."""
+
+    @staticmethod
+    def forward(ctx, ops, group, mode: int, precision: int, sid_rows, x, y, *params):
+        rank = dist.get_rank(group)
+        br = x.shape[0]
+        x = x.contiguous()
+        params_c = [p.contiguous() for p in params]
+        y_all, sid_all = _gather_block_inputs(group, y, sid_rows)
+        part, lse_rows, n_pos, saved = ops.posnce_forward(x, y_all, params_c, sid_rows.contiguous(), sid_all, rank * br,
+                                                          mode, precision)
+        parts = _all_gather_rows(part.reshape(1, -1), group)  # [G, P], rank order
+        loss, lse_cols = ops.posnce_merge(parts, br, mode)
+        ctx.ops, ctx.group, ctx.saved = ops, group, saved
+        ctx.param_like = [p.detach() for p in params]
+        ctx.save_for_backward(lse_cols)
+        ctx.mark_non_differentiable(lse_rows, lse_cols, n_pos)
+        return loss, lse_rows, lse_cols, n_pos
+
+    @staticmethod
+    def backward(ctx, grad_loss, *_):
+        (lse_cols,) = ctx.saved_tensors
+        go = grad_loss.reshape(-1)[:1].to(lse_cols.dtype).contiguous()
+        gx, gy_partial, gparams = ctx.ops.posnce_backward(ctx.saved, lse_cols, go)
+        return (None,) * 5 + _exchange_block_gradients(ctx.group, ctx.param_like, gx, gy_partial, gparams)
+
+
+_BLOCK_LOSS_PRECISIONS = (_hip.MI_PREC_F32, _hip.MI_PREC_BF16, _hip.MI_PREC_BF16X3)
+
+
+def _block_loss_setup(what: str, embedding_img, embedding_txt, codes, critic_params, precision: str, critic: str, ops):
+    """(ops, precision code) of a training loss on a sharded batch: bilinear and separable critics, the precisions of the
+    one-GPU losses; ``codes`` is this rank's int64 [B/G] id or mask tensor."""
+    if critic not in ("bilinear", "separable"):
+        raise ValueError(f"{what} is implemented for the bilinear and separable critics only (got {critic!r})")
+    if embedding_img.dim() != 2 or embedding_txt.dim() != 2 or embedding_img.shape[0] != embedding_txt.shape[0]:
+        raise ValueError("embedding_img / embedding_txt must be [B/G, d_img] / [B/G, d_txt]")
+    if codes.dtype != torch.int64 or codes.dim() != 1 or codes.shape[0] != embedding_img.shape[0]:
+        raise ValueError("the id codes / label masks of a rank must be an int64 tensor [B/G]")
+    prec = resolve_critic(critic, precision, embedding_img.shape[0], embedding_img.shape[1], embedding_txt.shape[1],
+                          critic_params)[2]  # (as global_batch_mi_bound: bf16x3 looks at this rank's row count)
+    if prec not in _BLOCK_LOSS_PRECISIONS:
+        raise ValueError(f'precision="{precision}" is not available for {what} of the {critic} critic '
+                         '(use "f32", "f32_exact", "bf16" or "bf16x3")')
+    return (ops if ops is not None else OPS[critic]()), prec
+
+
+def global_batch_study_positive_infonce(embedding_img, embedding_txt, study_id_codes,
+                                        critic_params: Sequence[torch.Tensor], symmetric: bool = True,
+                                        precision: str = "f32", critic: str = "bilinear", group=None, ops=None,
+                                        return_stats: bool = False):
+    """``study_positives.study_positive_infonce`` at B = world_size * local_batch with this rank's [B/G, d] embeddings:
+    every same-study pair of the GLOBAL batch is a positive, wherever its two members sit (GlobalBatchPosNceFn).
+    ``study_id_codes``: int64 tensor [B/G] (codes must be consistent across ranks, e.g. the integer study ids);
+    ``critic`` "bilinear" (``critic_params`` = [W]) or "separable" ([Wg, Wh]).  Every rank returns the same 0-d loss;
+    ``.backward()`` leaves the gradient of the global loss w.r.t. the local embeddings and the (all-reduced) gradient
+    w.r.t. the critic parameters.  A training loss, not an MI bound, and not an estimator name.
+
+    ``return_stats=True``: ``(loss, {"lse_rows": r [B/G], "lse_cols": c [B], "n_pos": n int32 [B/G]})``."""
+    ops, prec = _block_loss_setup("the study-positive InfoNCE", embedding_img, embedding_txt, study_id_codes,
+                                  critic_params, precision, critic, ops)
+    mode = _hip.MI_NCE_SYMMETRIC if symmetric else _hip.MI_NCE_ROWWISE
+    loss, r, c, n_pos = GlobalBatchPosNceFn.apply(ops, group, mode, prec, study_id_codes, embedding_img, embedding_txt,
+                                                  *critic_params)
+    loss = loss.reshape(())
+    return (loss, {"lse_rows": r, "lse_cols": c, "n_pos": n_pos}) if return_stats else loss
+
+
 class GlobalBatchGraphStep:
     """Forward + backward of the global-batch bound for FIXED shapes and storage, with the two compute sections of a
     step replayed from hipGraphs and the collectives issued eagerly between them:
