@@ -804,6 +804,59 @@ int mi_softnce_separable_shard_bwd(const float* x, const float* y, const float* 
                                    float* grad_x, float* grad_y, float* grad_wg, float* grad_wh, void* workspace,
                                    size_t workspace_bytes, void* stream);
 
+/* ---- MI estimates from one forward sweep -------------------------------------------------- */
+/* How much mutual information a trained critic has found on a batch: every bound of the package and SMILE (Song & Ermon
+ * 2020: DV with the negatives' scores clipped to [-tau, tau]) from ONE pass over S[i, j] = critic(img_i, txt_j).  Pairs as
+ * everywhere above: n_pos = b positives (i, i), n_neg negatives i != j with sid_i != sid_j, equal-id off-diagonal pairs
+ * dropped.  sp(x) = log(1 + e^x).  ESTIMATES, not losses: higher means more MI, in nats.  est_out [MI_EST_FLOATS], device:
+ *   MI_EST_DV         mean_pos s - (LSE_neg s - log n_neg)
+ *   MI_EST_NWJ        mean_pos s - exp(LSE_neg s - log n_neg - 1)
+ *   MI_EST_JSD        -(mean_pos sp(-s) + mean_neg sp(s))                      (+ 2 log 2: the JS divergence)
+ *   MI_EST_NCE_I2T    (1/b) sum_i (S_ii - r_i + log |C_i|)                     r_i, C_i of mi_nce_* above
+ *   MI_EST_NCE_T2I    (1/b) sum_j (S_jj - c_j + log |R_j|)                     |C_i| = |R_i| = b + 1 - #{j : sid_j == sid_i}
+ *   MI_EST_POS_MEAN   mean_pos s          MI_EST_NEG_MEAN   mean_neg s          MI_EST_LOG_N_NEG   logf((float)n_neg)
+ *   MI_EST_SMILE + k  mean_pos s - (log sum_neg exp(clip(s, -tau_k, tau_k)) - log n_neg)   for k < n_tau, NaN for k >= n_tau
+ * With unique ids nce_i2t = log b - (the row-wise loss of mi_nce_*); tau >= max |s_neg| makes SMILE equal DV.  Without
+ * negatives (every id equal, b == 1) dv, nwj, jsd, neg_mean and smile are NaN, log_n_neg is -inf and nce_* is exactly 0.
+ * taus_host is a HOST array of n_tau clips, read during the call and copied by value into the kernel arguments (NULL
+ * allowed with n_tau == 0).  n_tau in [0, MI_EST_MAX_TAUS]; every tau finite, 0 < tau <= 40: the terms exp(clip(s)) of
+ * the clipped sum then lie in [e^-40, e^40], normal fp32 numbers whose sum over fewer than 2^62 pairs stays finite, so it
+ * needs no running maximum.
+ * Forward only: no gradients, no mode, not an estimator of the training entry points.  Every one of the MI_EST_FLOATS
+ * outputs is written.  Fixed-order reductions, integer counts (64-bit in total), no float atomics: identical bits from
+ * call to call.  MI_EINVAL before anything touches the device: null required pointers, sizes < 1, b >= 2^31, n_tau or a
+ * tau out of range, MI_PREC_FP8 / F16 / F16X3, w == NULL with d_img != d_txt; MI_EWORKSPACE: workspace too small. */
+#define MI_EST_DV 0
+#define MI_EST_NWJ 1
+#define MI_EST_JSD 2
+#define MI_EST_NCE_I2T 3
+#define MI_EST_NCE_T2I 4
+#define MI_EST_POS_MEAN 5
+#define MI_EST_NEG_MEAN 6
+#define MI_EST_LOG_N_NEG 7
+#define MI_EST_SMILE 8
+#define MI_EST_MAX_TAUS 4
+#define MI_EST_FLOATS 12
+/* a caller's fp32 [b, b] score matrix (any critic): one wave per 64 x 64 tile, exact expf; the workspace holds the tile
+ * and row / column records, 16 b ceil(b / 64) + 48 ceil(b / 64)^2 bytes and O(b) floats */
+size_t mi_estimates_matrix_workspace_bytes(int64_t b);
+int mi_estimates_matrix(const float* scores, const int64_t* sid, int64_t b, const float* taus_host, int n_tau,
+                        float* est_out, void* workspace, size_t workspace_bytes, void* stream);
+/* Bilinear S = (X W) Y^T (w == NULL: X Y^T, d_img == d_txt) on the forward half of the GEMM chain, as mi_rank_bilinear:
+ * prep and T = X W, the score sweep with the statistics epilogue, merge, finalize.  The workspace is the forward half's
+ * operand copies and T plus the records of the matrix call: no G, no G^T, no b x b float buffer.  Precisions and paths as
+ * mi_rank_*: MI_PREC_F32 (exact fp32 products), MI_PREC_BF16 / MI_PREC_BF16X3 (16-bit chain where b and the widths are
+ * multiples of 8, generic kernels otherwise). */
+size_t mi_estimates_bilinear_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int precision);
+int mi_estimates_bilinear(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t d_img,
+                          int64_t d_txt, int precision, const float* taus_host, int n_tau, float* est_out,
+                          void* workspace, size_t workspace_bytes, void* stream);
+/* separable S = (X Wg)(Y Wh)^T: projects first, then the w == NULL form on the projections, as mi_rank_separable */
+size_t mi_estimates_separable_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int precision);
+int mi_estimates_separable(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid, int64_t b,
+                           int64_t d_img, int64_t d_txt, int64_t d_proj, int precision, const float* taus_host, int n_tau,
+                           float* est_out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@
 #include "mi_banknce.h"
 #include "mi_posnce.h"
 #include "mi_softnce.h"
+#include "mi_estimates.h"
 
 namespace mi {
 
@@ -1495,6 +1496,20 @@ struct TopkEst {
   static constexpr SepLabels kSep = {"topk separable A = X Wg", "topk separable C = Y Wh"};
 };
 
+// MI estimates (mi_estimates.h): the forward half once more, the score GEMM's epilogue writes one
+// record per tile and the per-sample InfoNCE's row / column records.  No mode, no gradient half.
+struct EstimatesEst {
+  using StatsOut = EstStatsOut;
+  using Stats = EpiEstStats<false>;
+  using Stats16 = EpiEstStats<true>;
+  static int check_mode(const char*, int) { return MI_OK; }
+  static constexpr const char* kName = "the MI estimates";
+  static constexpr const char* kT = "estimates T = X W (generic)";
+  static constexpr const char* kScores = "estimates score + records (generic)";
+  static constexpr const char* kScores16 = "estimates score + records";
+  static constexpr SepLabels kSep = {"estimates separable A = X Wg", "estimates separable C = Y Wh"};
+};
+
 static bool chain_16bit_ok(int64_t br, int64_t b, int64_t dx, int64_t dy, int precision) {
   return (precision == MI_PREC_BF16 || precision == MI_PREC_BF16X3) && br % 8 == 0 && b % 8 == 0 && dx % 8 == 0 &&
          dy % 8 == 0;
@@ -1728,6 +1743,49 @@ static int rank_chain(const float* x, const float* y, const float* w, const int6
   }
   if (rc) return rc;
   return chain_sweep<RankEst>(x, y, w, b, b, dx, dy, precision, o, p, st);
+}
+
+// ------------------------------------------------------------------------------------------------ MI estimates
+// The forward half's buffers (plan_rank_bilinear) and the records: b^2 / 64 of them, no G, no G^T, no b x b floats
+struct EstBilinearPlan {
+  BilinearPlan p;
+  EstPlan q;
+  size_t bytes;
+};
+static EstBilinearPlan plan_est_bilinear(Workspace& ws, int64_t b, int64_t dx, int64_t dy, int precision) {
+  EstBilinearPlan n{};
+  n.p = plan_rank_bilinear(ws, b, dx, dy, precision).p;
+  n.q = plan_est(ws, b);
+  n.bytes = ws.off;
+  return n;
+}
+struct EstSeparablePlan {
+  float *a, *c;  // the projections A = X Wg, C = Y Wh [b][k]
+  EstBilinearPlan n;
+  size_t bytes;
+};
+static EstSeparablePlan plan_est_separable(Workspace& ws, int64_t b, int64_t k, int precision) {
+  EstSeparablePlan s{};
+  s.a = ws.take<float>(b * k);
+  s.c = ws.take<float>(b * k);
+  s.n = plan_est_bilinear(ws, b, k, k, precision);
+  s.bytes = ws.off;
+  return s;
+}
+
+// prep / T, the sweep with the statistics epilogue, merge and finalize
+static int est_chain(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t dx, int64_t dy,
+                     int precision, const EstTaus& taus, float* est_out, const EstBilinearPlan& n, hipStream_t st) {
+  const int rc = chain_scores<EstimatesEst>(x, y, w, sid, sid, b, b, 0, dx, dy, precision, est_stats_out(n.q, sid, taus),
+                                            n.p, st);
+  if (rc) return rc;
+  return est_finish(n.q, sid, b, taus, est_out, st);
+}
+
+// the arguments every estimates entry point shares: the batch size and the clips (read from the host array)
+static int est_check(const char* fn, int64_t b, const float* taus_host, int n_tau, EstTaus& taus) {
+  MI_CHECK_ARG(b >= 1 && b < ((int64_t)1 << 31), "%s: need 1 <= b < 2^31 (got %lld)", fn, (long long)b);
+  return est_read_taus(fn, taus_host, n_tau, taus);
 }
 
 // ------------------------------------------------------------------------------------------------ top-k retrieval
@@ -2917,6 +2975,78 @@ int mi_rank_separable(const float* x, const float* y, const float* wg, const flo
   rc = separable_project(RankEst::kSep, precision == MI_PREC_BF16, x, y, wg, wh, b, b, d_img, d_txt, k, sp.a, sp.c, st);
   if (rc) return rc;
   return rank_chain(sp.a, sp.c, nullptr, sid, b, k, k, precision, rank_i2t, rank_t2i, diag_out, sp.n, st);
+}
+
+// ------------------------------------------------------------------------------------------------ MI estimates
+size_t mi_estimates_matrix_workspace_bytes(int64_t b) {
+  if (b <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  plan_est(ws, b);
+  return ws.off + 256;
+}
+
+int mi_estimates_matrix(const float* scores, const int64_t* sid, int64_t b, const float* taus_host, int n_tau,
+                        float* est_out, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(scores && sid && est_out && workspace, "mi_estimates_matrix: null pointer");
+  EstTaus taus;
+  int rc = est_check("mi_estimates_matrix", b, taus_host, n_tau, taus);
+  if (rc) return rc;
+  MI_CHECK_ARG((b + 63) / 64 <= 65535, "mi_estimates_matrix: b %lld needs more than 65535 tile rows", (long long)b);
+  Workspace ws(workspace, workspace_bytes);
+  const EstPlan q = plan_est(ws, b);
+  rc = ws_fits(ws, "mi_estimates_matrix");
+  if (rc) return rc;
+  return est_matrix(scores, sid, b, taus, est_out, q, (hipStream_t)stream);
+}
+
+size_t mi_estimates_bilinear_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int precision) {
+  if (b <= 0 || d_img <= 0 || d_txt <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_est_bilinear(ws, b, d_img, d_txt, precision).bytes + 256;
+}
+
+int mi_estimates_bilinear(const float* x, const float* y, const float* w, const int64_t* sid, int64_t b, int64_t d_img,
+                          int64_t d_txt, int precision, const float* taus_host, int n_tau, float* est_out,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && sid && est_out && workspace, "mi_estimates_bilinear: null pointer");
+  int rc = chain_check<EstimatesEst>("mi_estimates_bilinear", b, b, 0, d_img, d_txt, 0, precision);
+  if (rc) return rc;
+  EstTaus taus;
+  rc = est_check("mi_estimates_bilinear", b, taus_host, n_tau, taus);
+  if (rc) return rc;
+  MI_CHECK_ARG(w || d_img == d_txt, "mi_estimates_bilinear: w == NULL (S = X Y^T) needs d_img == d_txt");
+  Workspace ws(workspace, workspace_bytes);
+  const EstBilinearPlan n = plan_est_bilinear(ws, b, d_img, d_txt, precision);
+  rc = ws_fits(ws, "mi_estimates_bilinear");
+  if (rc) return rc;
+  return est_chain(x, y, w, sid, b, d_img, d_txt, precision, taus, est_out, n, (hipStream_t)stream);
+}
+
+size_t mi_estimates_separable_workspace_bytes(int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int precision) {
+  if (b <= 0 || d_img <= 0 || d_txt <= 0 || d_proj <= 0) return 0;
+  Workspace ws(nullptr, 0);
+  return plan_est_separable(ws, b, d_proj, precision).bytes + 256;
+}
+
+int mi_estimates_separable(const float* x, const float* y, const float* wg, const float* wh, const int64_t* sid, int64_t b,
+                           int64_t d_img, int64_t d_txt, int64_t d_proj, int precision, const float* taus_host, int n_tau,
+                           float* est_out, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_CHECK_ARG(x && y && wg && wh && sid && est_out && workspace, "mi_estimates_separable: null pointer");
+  int rc = chain_check<EstimatesEst>("mi_estimates_separable", b, b, 0, d_img, d_txt, 0, precision);
+  if (rc) return rc;
+  MI_CHECK_ARG(d_proj >= 1, "mi_estimates_separable: projection width must be >= 1");
+  EstTaus taus;
+  rc = est_check("mi_estimates_separable", b, taus_host, n_tau, taus);
+  if (rc) return rc;
+  Workspace ws(workspace, workspace_bytes);
+  const EstSeparablePlan sp = plan_est_separable(ws, b, d_proj, precision);
+  rc = ws_fits(ws, "mi_estimates_separable");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t k = d_proj;
+  rc = separable_project(EstimatesEst::kSep, precision == MI_PREC_BF16, x, y, wg, wh, b, b, d_img, d_txt, k, sp.a, sp.c, st);
+  if (rc) return rc;
+  return est_chain(sp.a, sp.c, nullptr, sid, b, k, k, precision, taus, est_out, sp.n, st);
 }
 
 // ------------------------------------------------------------------------------------------------ top-k retrieval

@@ -187,6 +187,12 @@ SIGNATURES = {
     "mi_rank_bilinear": (c_int, [_P] * 4 + [_I64] * 3 + [_I] + [_P] * 4 + [_SZ, _P]),
     "mi_rank_separable_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I]),
     "mi_rank_separable": (c_int, [_P] * 5 + [_I64] * 4 + [_I] + [_P] * 4 + [_SZ, _P]),
+    "mi_estimates_matrix_workspace_bytes": (_SZ, [_I64]),
+    "mi_estimates_matrix": (c_int, [_P, _P, _I64, _P, _I, _P, _P, _SZ, _P]),
+    "mi_estimates_bilinear_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I]),
+    "mi_estimates_bilinear": (c_int, [_P] * 4 + [_I64] * 3 + [_I, _P, _I] + [_P] * 2 + [_SZ, _P]),
+    "mi_estimates_separable_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I]),
+    "mi_estimates_separable": (c_int, [_P] * 5 + [_I64] * 4 + [_I, _P, _I] + [_P] * 2 + [_SZ, _P]),
     "mi_topk_matrix_workspace_bytes": (_SZ, [_I64, _I64, _I, _I]),
     "mi_topk_matrix": (c_int, [_P, _I64, _I64, _P, _P, _I, _I, _P, _P, _P, _SZ, _P]),
     "mi_topk_bilinear_workspace_bytes": (_SZ, [_I64] * 4 + [_I, _I]),
@@ -239,6 +245,10 @@ SIGNATURES = {
 }
 MI_TOPK_MAX_K = 32  # include/mi_critic.h
 MI_SOFTNCE_MAX_LABELS = 63  # include/mi_critic.h
+# slots of the MI estimates' output (mi_estimates_*), include/mi_critic.h
+(MI_EST_DV, MI_EST_NWJ, MI_EST_JSD, MI_EST_NCE_I2T, MI_EST_NCE_T2I, MI_EST_POS_MEAN, MI_EST_NEG_MEAN, MI_EST_LOG_N_NEG,
+ MI_EST_SMILE) = range(9)
+MI_EST_MAX_TAUS, MI_EST_FLOATS = 4, 12
 
 _lib: Optional[ctypes.CDLL] = None
 

@@ -1,5 +1,5 @@
 """The one binding of the critic entry points of the C ABI (mi_bilinear_*, mi_separable_*, mi_concat_mlp_*, mi_nce_*,
-mi_fdiv_*, mi_rank_*, mi_topk_*, mi_hardnce_*, mi_banknce_*, mi_posnce_*, mi_softnce_*), shared by ``mi_critics`` (eager autograd), ``graphed`` (hipGraph step) and ``distributed`` (sharded step).
+mi_fdiv_*, mi_rank_*, mi_topk_*, mi_estimates_*, mi_hardnce_*, mi_banknce_*, mi_posnce_*, mi_softnce_*), shared by ``mi_critics`` (eager autograd), ``graphed`` (hipGraph step) and ``distributed`` (sharded step).
 
 An ops object scores the row block ``x`` [b_rows, d_img] (starting at ``row_offset``) against all of ``y_all``
 [b, d_txt]; a whole batch is ``b_rows == b``, ``row_offset == 0``.  Each ``*_call`` method writes one entry point's
@@ -85,6 +85,21 @@ def rank_matrix(scores, sid, i2t=True, t2i=True):
     rt = torch.empty(b, dtype=torch.int32, device=dev) if t2i else None
     _hip.call("mi_rank_matrix", dev, scores.data_ptr(), sid.data_ptr(), b, _p(ri), _p(rt))
     return ri, rt
+
+
+def estimates_taus(taus):
+    """The clips of an estimates call as the C array the entry points read (a host pointer, copied during the call)."""
+    return (ctypes.c_float * max(len(taus), 1))(*taus)
+
+
+def estimates_matrix(scores, sid, taus):
+    """MI estimates of a float32 [B, B] score matrix (mi_estimates_matrix): float32 [MI_EST_FLOATS] on the device."""
+    b, dev = scores.shape[0], scores.device
+    ws = _hip.workspace(_hip.load().mi_estimates_matrix_workspace_bytes(b), dev)
+    est = torch.empty(_hip.MI_EST_FLOATS, dtype=torch.float32, device=dev)
+    _hip.call("mi_estimates_matrix", dev, scores.data_ptr(), sid.data_ptr(), b, estimates_taus(taus), len(taus),
+              est.data_ptr(), ws.data_ptr(), ws.numel())
+    return est
 
 
 def topk_outputs(n_q, k, device):
@@ -235,6 +250,15 @@ class _HipOps:
         diag = torch.empty(b, dtype=torch.float32, device=dev) if want_diag else None
         self.rank_call(x, y, params, sid, precision, ri, rt, diag, ws)()
         return (ri, rt, diag) if want_diag else (ri, rt)
+
+    def estimates_step(self, x, y, params, sid, precision, taus):
+        """MI estimates of the whole batch in one call of ``mi_estimates_<critic>`` (bilinear and separable critics):
+        float32 [MI_EST_FLOATS] on the device (the slots ``_hip.MI_EST_*``)."""
+        b, dev = x.shape[0], x.device
+        ws = _hip.workspace(self.estimates_workspace_bytes(b, x.shape[1], y.shape[1], params, precision), dev)
+        est = torch.empty(_hip.MI_EST_FLOATS, dtype=torch.float32, device=dev)
+        self.estimates_call(x, y, params, sid, precision, taus, est, ws)()
+        return est
 
     def topk_step(self, x, y, params, sid_img, sid_txt, precision, k, i2t=True, t2i=True):
         """Top-k retrieval of x [n_img, d_img] against y [n_txt, d_txt] in one call of ``mi_topk_<critic>`` (bilinear and
@@ -455,6 +479,17 @@ class HipBilinearOps(_HipOps):
         return _call("mi_rank_bilinear", x.device, x.data_ptr(), y.data_ptr(), _p(params[0] if params else None),
                      sid.data_ptr(), x.shape[0], x.shape[1], y.shape[1], precision, _p(rank_i2t), _p(rank_t2i), _p(diag),
                      ws.data_ptr(), ws.numel())
+
+    @staticmethod
+    def estimates_workspace_bytes(b, dx, dy, params, precision):
+        return _hip.load().mi_estimates_bilinear_workspace_bytes(b, dx, dy, precision)
+
+    def estimates_call(self, x, y, params, sid, precision, taus, est, ws):
+        """MI estimates of the whole batch (mi_estimates_bilinear); ``taus`` a sequence of at most MI_EST_MAX_TAUS clips,
+        ``est`` float32 [MI_EST_FLOATS]."""
+        return _call("mi_estimates_bilinear", x.device, x.data_ptr(), y.data_ptr(), _p(params[0] if params else None),
+                     sid.data_ptr(), x.shape[0], x.shape[1], y.shape[1], precision, estimates_taus(taus), len(taus),
+                     est.data_ptr(), ws.data_ptr(), ws.numel())
 
     @staticmethod
     def topk_workspace_bytes(n_img, n_txt, dx, dy, params, precision, k):
@@ -722,6 +757,17 @@ class HipSeparableOps(_HipOps):
         return _call("mi_rank_separable", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
                      sid.data_ptr(), x.shape[0], x.shape[1], y.shape[1], wg.shape[1], precision, _p(rank_i2t),
                      _p(rank_t2i), _p(diag), ws.data_ptr(), ws.numel())
+
+    @staticmethod
+    def estimates_workspace_bytes(b, dx, dy, params, precision):
+        return _hip.load().mi_estimates_separable_workspace_bytes(b, dx, dy, params[0].shape[1], precision)
+
+    def estimates_call(self, x, y, params, sid, precision, taus, est, ws):
+        """MI estimates of the whole batch (mi_estimates_separable), as ``HipBilinearOps.estimates_call``."""
+        wg, wh = params
+        return _call("mi_estimates_separable", x.device, x.data_ptr(), y.data_ptr(), wg.data_ptr(), wh.data_ptr(),
+                     sid.data_ptr(), x.shape[0], x.shape[1], y.shape[1], wg.shape[1], precision, estimates_taus(taus),
+                     len(taus), est.data_ptr(), ws.data_ptr(), ws.numel())
 
     @staticmethod
     def topk_workspace_bytes(n_img, n_txt, dx, dy, params, precision, k):

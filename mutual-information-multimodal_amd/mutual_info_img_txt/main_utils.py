@@ -304,6 +304,19 @@ class MultiModalManager:
         ri, rt = retrieval.retrieval_ranks(embedding_img, embedding_txt, study_id, self.mi_discriminator, precision)
         return {"i2t": retrieval.retrieval_metrics(ri, ks), "t2i": retrieval.retrieval_metrics(rt, ks)}
 
+    def mi_estimates_eval(self, embedding_img, embedding_txt, study_id, taus=(1.0, 5.0), precision: str = "f32"):
+        """MI estimates of the batch under the manager's critic (``mi_estimates.mi_estimates``) as Python floats:
+        ``{"dv", "nwj", "jsd", "nce_i2t", "nce_t2i", "pos_mean", "neg_mean", "log_n_neg"}`` and ``"smile"``, a list with
+        one value per clip of ``taus``.  Estimates in nats (higher: more MI), not losses; one host copy."""
+        from . import mi_estimates as _est
+        out = _est.mi_estimates(embedding_img, embedding_txt, study_id, self.mi_discriminator, taus, precision)
+        n_tau = out["smile"].numel()
+        names = list(_est.ESTIMATE_NAMES)
+        host = torch.cat([torch.stack([out[n] for n in names]), out["smile"]]).cpu().tolist()
+        res = dict(zip(names, host[:len(names)]))
+        res["smile"] = host[len(names):len(names) + n_tau]
+        return res
+
     def gallery_eval(self, embedding_img, img_ids, embedding_txt, txt_ids, ks=(1, 5, 10), precision: str = "f32"):
         """Gallery retrieval under the manager's critic (``retrieval.retrieval_topk`` without exclusion): N images against
         M reports, relevance by study id (a study may have several images).  ``{"i2t": metrics, "t2i": metrics}`` with
