@@ -240,6 +240,18 @@ int mi_bilinear_step_bf16(const void* x_bf16, const void* y_bf16, const float* w
 int mi_bilinear_path(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, int precision);
 int mi_separable_path(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, int64_t d_proj, int precision);
 
+/* Which kernel the 16-bit GEMM launcher issues for one m x n problem of depth k without split-K and with a storing (not
+ * partial-reducing) epilogue -- the score GEMM of every loss family on the 16-bit chain, where k is d_txt (bf16) or
+ * 3 * d_txt (bf16x3): one of MI_GEMM16_*, or MI_EINVAL on a size < 1.  The launcher switches on the same host function;
+ * nothing is launched and no GPU is needed. */
+#define MI_GEMM16_PLAIN 0       /* 128 x 128 tiles, operands staged through registers (k % 64 != 0)        */
+#define MI_GEMM16_GLDS 1        /* 128 x 128 tiles, LDS-DMA, two stages                                     */
+#define MI_GEMM16_GLDS4 2       /* 128 x 128 tiles, LDS-DMA, four stages (k >= 256, at most 512 tiles)      */
+#define MI_GEMM16_PIPE128 3     /* 128 x 128 tiles, ping-pong K groups (k >= 2048, at most 256 tiles)       */
+#define MI_GEMM16_PIPE256X128 4 /* 256 x 128 tiles, ping-pong K groups (k >= 2048, 160 .. 256 such tiles)   */
+#define MI_GEMM16_BIG 5         /* 256 x 256 tiles (at least 192 of them)                                   */
+int mi_gemm16_variant(int64_t m, int64_t n, int64_t k);
+
 /* ---- fused separable critic: S = (X Wg)(Y Wh)^T, bound, all gradients ------------------------------- */
 /* BASELINE.json configs[1] (an extension: the reference has no separable critic; bound, masking and pair semantics are
  * the reference's).  X [b_rows, d_img], Y [b, d_txt], Wg [d_img, d_proj], Wh [d_txt, d_proj].  The projections run on

@@ -1050,6 +1050,18 @@ int mi_bilinear_path(int64_t b_rows, int64_t b, int64_t d_img, int64_t d_txt, in
   return plan_bilinear(ws, b_rows, b, d_img, d_txt, precision, true).path;
 }
 
+/* Which kernel launch_gemm_bf16 issues for one m x n x k problem, n_splits = 1, a storing epilogue: MI_GEMM16_* (the
+ * launcher switches on the same function; nothing is launched). */
+int mi_gemm16_variant(int64_t m, int64_t n, int64_t k) {
+  if (m <= 0 || n <= 0 || k <= 0) return MI_EINVAL;
+  static_assert(kGemm16Plain == MI_GEMM16_PLAIN && kGemm16Glds == MI_GEMM16_GLDS && kGemm16Glds4 == MI_GEMM16_GLDS4 &&
+                    kGemm16Pipe128 == MI_GEMM16_PIPE128 && kGemm16Pipe256x128 == MI_GEMM16_PIPE256X128 &&
+                    kGemm16Big == MI_GEMM16_BIG,
+                "include/mi_critic.h out of step with GemmBf16Variant");
+  const int64_t ks[2] = {k, 0};
+  return gemm_bf16_variant(m, n, ks, 1, 1, k, false);
+}
+
 }  // extern "C"
 
 // ================================================================================================ separable critic

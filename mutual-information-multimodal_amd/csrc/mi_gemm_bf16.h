@@ -1354,6 +1354,47 @@ static inline int64_t gemm_bf16_n_partials(int64_t m, int64_t n, int64_t k) {
 constexpr size_t kG2SmemGlds = 2 * 2 * 16384;  // 65,536 bytes
 constexpr size_t kG2Smem = 2 * 2 * kTile * kG2LD * sizeof(bf16_t);  // 73,728 bytes
 
+// The kernel launch_gemm_bf16 issues, from the shape alone (the values of MI_GEMM16_* in include/mi_critic.h).  Pure host
+// arithmetic: launch_gemm_bf16 switches on it and mi_gemm16_variant reports it, so the two cannot disagree.  mm x nn is
+// the larger problem's output, k[q] problem q's K; `reduces`: Epi::kReducesPartial (no ping-pong kernels).
+enum GemmBf16Variant {
+  kGemm16Plain = 0,
+  kGemm16Glds = 1,
+  kGemm16Glds4 = 2,
+  kGemm16Pipe128 = 3,
+  kGemm16Pipe256x128 = 4,
+  kGemm16Big = 5
+};
+static inline GemmBf16Variant gemm_bf16_variant(int64_t mm, int64_t nn, const int64_t (&k)[2], int n_problems, int n_splits,
+                                                int64_t k_chunk, bool reduces) {
+  bool dma_ok = k_chunk % kG2KT == 0 || n_splits == 1;
+  for (int q = 0; q < n_problems; ++q) dma_ok = dma_ok && k[q] % kG2KT == 0 && k[q] > 0;
+  // two long-K problems that fill the chip with 256 x 256 tiles together (dT | dY at B = 8192: 2 x 128 tiles): the
+  // same kernel, blockIdx.z = problem.  MI_GEMM_NO_BIG2=1: A/B switch.
+  static const bool no_big2 = getenv("MI_GEMM_NO_BIG2") != nullptr;
+  const bool big2 = !reduces && !no_big2 && dma_ok && n_problems == 2 && n_splits == 1 && k[0] >= 2048 && k[1] >= 2048 &&
+                    !gemm_old_kernels() && 2 * ((mm + 255) / 256) * ((nn + 255) / 256) >= 192;
+  // long K, N too wide for one round of 128 x 128 tiles, too narrow to fill the chip with 256 x 256 ones: 256 x 128 tiles on
+  // the ping-pong kernel when they make one round that fills at least 5/8 of the CUs.  MI_GEMM_NO_P256=1: A/B switch.
+  if (!reduces) {
+    static const bool no_p256 = getenv("MI_GEMM_NO_P256") != nullptr;
+    const int64_t t128 = ((mm + 127) / 128) * ((nn + 127) / 128) * n_problems;
+    const int64_t t256 = ((mm + 255) / 256) * ((nn + 127) / 128) * n_problems;
+    static const int64_t p256_min_k = getenv("MI_GEMM_P256_MINK") ? atoll(getenv("MI_GEMM_P256_MINK")) : 2048;  // A/B
+    if (!big2 && !no_p256 && dma_ok && n_splits == 1 && k[0] >= p256_min_k && !gemm_old_kernels() && t128 > 256 &&
+        t256 <= 256 && t256 >= 160 && !(n_problems == 1 && gemm_bf16_use_big(mm, nn, k[0])))
+      return kGemm16Pipe256x128;
+  }
+  if (big2 || (dma_ok && n_problems == 1 && n_splits == 1 && gemm_bf16_use_big(mm, nn, k[0]))) return kGemm16Big;
+  const int64_t tiles = (int64_t)(unsigned)((nn + kTile - 1) / kTile) * (unsigned)((mm + kTile - 1) / kTile) *
+                        (unsigned)(n_problems * n_splits);
+  // measured (profiles/README.md): the ping-pong kernel wins on the long-K launch that has one workgroup per CU
+  // (dT | dY: 51.5 -> 43.3 us) and loses where two 4-wave workgroups per CU fit (T, dW | dX) or K is short
+  if (!reduces && dma_ok && !gemm_old_kernels() && k[0] >= 2048 && tiles <= 256) return kGemm16Pipe128;
+  if (dma_ok && gemm_use_glds4() && k[0] >= 4 * kG2KT && tiles <= 512) return kGemm16Glds4;
+  return dma_ok ? kGemm16Glds : kGemm16Plain;
+}
+
 template <class Epi>
 static inline int launch_gemm_bf16(const GemmBf16Args& args_in, int n_splits, const Epi& epi, hipStream_t st,
                                    const char* what) {
@@ -1366,6 +1407,9 @@ static inline int launch_gemm_bf16(const GemmBf16Args& args_in, int n_splits, co
     if (args.p[1].n > nn) nn = args.p[1].n;
   }
   if (mm <= 0 || nn <= 0) return MI_OK;
+  const int64_t ks[2] = {args.p[0].k, args.n_problems == 2 ? args.p[1].k : 0};
+  const GemmBf16Variant variant =
+      gemm_bf16_variant(mm, nn, ks, args.n_problems, n_splits, args.k_chunk, Epi::kReducesPartial);
   // per Epi instantiation, per device, thread-safe (mi_common.h)
   MI_SET_DYN_SMEM((gemm_bf16_kernel<Epi>), kG2Smem, "hipFuncSetAttribute(gemm_bf16_kernel)");
   MI_SET_DYN_SMEM((gemm_bf16_glds_kernel<Epi>), kG2SmemGlds, "hipFuncSetAttribute(gemm_bf16_glds_kernel)");
@@ -1373,24 +1417,8 @@ static inline int launch_gemm_bf16(const GemmBf16Args& args_in, int n_splits, co
   if constexpr (!Epi::kReducesPartial)
     MI_SET_DYN_SMEM((gemm_bf16_pipe_kernel<PipeCfg128, Epi>), PipeCfg128::SMEM,
                     "hipFuncSetAttribute(gemm_bf16_pipe_kernel 128)");
-  bool dma_ok = args.k_chunk % kG2KT == 0 || n_splits == 1;
-  for (int q = 0; q < args.n_problems; ++q) dma_ok = dma_ok && args.p[q].k % kG2KT == 0 && args.p[q].k > 0;
-  // two long-K problems that fill the chip with 256 x 256 tiles together (dT | dY at B = 8192: 2 x 128 tiles): the
-  // same kernel, blockIdx.z = problem.  MI_GEMM_NO_BIG2=1: A/B switch.
-  static const bool no_big2 = getenv("MI_GEMM_NO_BIG2") != nullptr;
-  bool big2 = false;
-  if constexpr (!Epi::kReducesPartial)
-    big2 = !no_big2 && dma_ok && args.n_problems == 2 && n_splits == 1 && args.p[0].k >= 2048 && args.p[1].k >= 2048 &&
-           !gemm_old_kernels() && 2 * ((mm + 255) / 256) * ((nn + 255) / 256) >= 192;
-  // long K, N too wide for one round of 128 x 128 tiles, too narrow to fill the chip with 256 x 256 ones: 256 x 128 tiles on
-  // the ping-pong kernel when they make one round that fills at least 5/8 of the CUs.  MI_GEMM_NO_P256=1: A/B switch.
   if constexpr (!Epi::kReducesPartial) {
-    static const bool no_p256 = getenv("MI_GEMM_NO_P256") != nullptr;
-    const int64_t t128 = ((mm + 127) / 128) * ((nn + 127) / 128) * args.n_problems;
-    const int64_t t256 = ((mm + 255) / 256) * ((nn + 127) / 128) * args.n_problems;
-    static const int64_t p256_min_k = getenv("MI_GEMM_P256_MINK") ? atoll(getenv("MI_GEMM_P256_MINK")) : 2048;  // A/B
-    if (!big2 && !no_p256 && dma_ok && n_splits == 1 && args.p[0].k >= p256_min_k && !gemm_old_kernels() && t128 > 256 &&
-        t256 <= 256 && t256 >= 160 && !(args.n_problems == 1 && gemm_bf16_use_big(mm, nn, args.p[0].k))) {
+    if (variant == kGemm16Pipe256x128) {
       MI_SET_DYN_SMEM((gemm_bf16_pipe_kernel<PipeCfg256x128, Epi>), PipeCfg256x128::SMEM,
                       "hipFuncSetAttribute(gemm_bf16_pipe_kernel 256x128)");
       dim3 grid((unsigned)((nn + 127) / 128), (unsigned)((mm + 255) / 256), (unsigned)args.n_problems);
@@ -1403,7 +1431,7 @@ static inline int launch_gemm_bf16(const GemmBf16Args& args_in, int n_splits, co
       return MI_OK;
     }
   }
-  if (big2 || (dma_ok && args.n_problems == 1 && n_splits == 1 && gemm_bf16_use_big(mm, nn, args.p[0].k))) {
+  if (variant == kGemm16Big) {
     MI_SET_DYN_SMEM((gemm_bf16_big_kernel<Epi>), kG2SmemBig, "hipFuncSetAttribute(gemm_bf16_big_kernel)");
     dim3 grid((unsigned)((nn + 255) / 256), (unsigned)((mm + 255) / 256), (unsigned)args.n_problems);
     xcd_pick_blocks(grid.y, grid.x, 256, args.p[0].k, 1, args.xcd_gy, args.xcd_gx);
@@ -1421,20 +1449,21 @@ static inline int launch_gemm_bf16(const GemmBf16Args& args_in, int n_splits, co
   MI_STAMP_SELECT(what, st);
   {
     ProfScope prof_(what, st);
-    bool piped = false;
-    if constexpr (!Epi::kReducesPartial) {
-      // measured (profiles/README.md): the ping-pong kernel wins on the long-K launch that has one workgroup per CU
-      // (dT | dY: 51.5 -> 43.3 us) and loses where two 4-wave workgroups per CU fit (T, dW | dX) or K is short
-      piped = dma_ok && !gemm_old_kernels() && args.p[0].k >= 2048 &&
-              (int64_t)grid.x * grid.y * grid.z <= 256;
-      if (piped)
-        hipLaunchKernelGGL((gemm_bf16_pipe_kernel<PipeCfg128, Epi>), grid, dim3(512), PipeCfg128::SMEM, st, args, epi);
+    switch (variant) {
+      case kGemm16Pipe128:
+        if constexpr (!Epi::kReducesPartial)
+          hipLaunchKernelGGL((gemm_bf16_pipe_kernel<PipeCfg128, Epi>), grid, dim3(512), PipeCfg128::SMEM, st, args, epi);
+        break;
+      case kGemm16Glds4:
+        hipLaunchKernelGGL((gemm_bf16_glds4_kernel<Epi>), grid, dim3(256), 2 * kG2SmemGlds, st, args, epi);
+        break;
+      case kGemm16Glds:
+        hipLaunchKernelGGL((gemm_bf16_glds_kernel<Epi>), grid, dim3(256), kG2SmemGlds, st, args, epi);
+        break;
+      default:  // kGemm16Plain (the 256-tile variants returned above)
+        hipLaunchKernelGGL((gemm_bf16_kernel<Epi>), grid, dim3(256), kG2Smem, st, args, epi);
+        break;
     }
-    if (piped) {
-    } else if (dma_ok && gemm_use_glds4() && args.p[0].k >= 4 * kG2KT && (int64_t)grid.x * grid.y * grid.z <= 512)
-      hipLaunchKernelGGL((gemm_bf16_glds4_kernel<Epi>), grid, dim3(256), 2 * kG2SmemGlds, st, args, epi);
-    else if (dma_ok) hipLaunchKernelGGL((gemm_bf16_glds_kernel<Epi>), grid, dim3(256), kG2SmemGlds, st, args, epi);
-    else hipLaunchKernelGGL((gemm_bf16_kernel<Epi>), grid, dim3(256), kG2Smem, st, args, epi);
   }
   MI_LAUNCH_CHECK(what);
   return MI_OK;

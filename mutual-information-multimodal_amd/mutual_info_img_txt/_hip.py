@@ -144,6 +144,7 @@ SIGNATURES = {
     "mi_bilinear_step_bf16": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _SZ, _P]),
     "mi_bilinear_path": (c_int, [_I64, _I64, _I64, _I64, _I]),
     "mi_separable_path": (c_int, [_I64, _I64, _I64, _I64, _I64, _I]),
+    "mi_gemm16_variant": (c_int, [_I64, _I64, _I64]),
     "mi_separable_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I64, _I]),
     "mi_separable_step": (c_int, [_P] * 5 + [_I64] * 4 + [_I, _I] + [_P] * 9 + [_SZ, _P]),
     "mi_separable_fwd": (c_int, [_P] * 6 + [_I64] * 6 + [_I, _I, _I] + [_P] * 4 + [_SZ, _P]),
@@ -282,6 +283,8 @@ MI_PATH_GENERIC, MI_PATH_GEMMS, MI_PATH_FUSED, MI_PATH_FUSED_TAIL, MI_PATH_FP8_G
 PATH_NAMES = {0: "generic strided-operand kernels", 1: "16-bit GEMM chain with G / G^T through HBM",
               2: "fused B x B kernel, three-launch tail", 3: "fused B x B kernel, two-launch tail", 4: "fp8 GEMM chain"}
 _warned_paths = set()
+# kernels of the 16-bit GEMM launcher reported by mi_gemm16_variant, include/mi_critic.h
+(MI_GEMM16_PLAIN, MI_GEMM16_GLDS, MI_GEMM16_GLDS4, MI_GEMM16_PIPE128, MI_GEMM16_PIPE256X128, MI_GEMM16_BIG) = range(6)
 
 
 def note_path(kind: str, shape: tuple, precision: int) -> int:

@@ -133,3 +133,38 @@ def test_path_queries(lib, caplog):
         assert _hip.note_path("bilinear", (4096, 4096, 512, 512), _hip.MI_PREC_BF16) == _hip.MI_PATH_FUSED_TAIL
     assert sum("outside the fused" in r.getMessage() for r in caplog.records) == 1
 
+
+def test_gemm16_variant_query(lib):
+    """mi_gemm16_variant is host-only and reports the kernel the 16-bit GEMM launcher switches on.  The six boundary
+    shapes of tests/gemm_variant_cases.py (the smallest ragged batch that reaches each kernel), a zero size, and the whole
+    table with its rectangular forms -- so a threshold change fails here and does not quietly take a kernel out of
+    tests/test_gemm_variants_gpu.py."""
+    import gemm_variant_cases as cases
+    from mutual_info_img_txt import _hip
+    v = lib.mi_gemm16_variant
+    assert v(136, 136, 40) == _hip.MI_GEMM16_PLAIN          # K % 64 != 0
+    assert v(136, 136, 64) == _hip.MI_GEMM16_GLDS           # K < 256
+    assert v(3000, 3000, 256) == _hip.MI_GEMM16_GLDS        # 24 x 24 = 576 tiles of 128 > 512
+    assert v(136, 136, 256) == _hip.MI_GEMM16_GLDS4
+    assert v(136, 136, 2112) == _hip.MI_GEMM16_PIPE128 and v(136, 136, 2048) == _hip.MI_GEMM16_PIPE128
+    assert v(2312, 2312, 2112) == _hip.MI_GEMM16_PIPE256X128  # 10 x 19 = 190 tiles of 256 x 128
+    assert v(3336, 3336, 64) == _hip.MI_GEMM16_BIG          # 14 x 14 = 196 tiles of 256 x 256
+    assert v(4096, 4096, 512) == _hip.MI_GEMM16_BIG         # the product's own batch (BASELINE.json configs[3])
+    # one step inside each threshold
+    assert v(3328, 3328, 64) == _hip.MI_GEMM16_GLDS and v(2312, 2312, 1984) == _hip.MI_GEMM16_GLDS4
+    assert v(136, 136, 192) == _hip.MI_GEMM16_GLDS and v(2816, 2816, 256) == _hip.MI_GEMM16_GLDS4  # 22 x 22 = 484 tiles
+    for bad in ((0, 136, 64), (136, 0, 64), (136, 136, 0), (-8, 136, 64)):
+        assert v(*bad) == -1
+    assert (_hip.MI_GEMM16_PLAIN, _hip.MI_GEMM16_GLDS, _hip.MI_GEMM16_GLDS4, _hip.MI_GEMM16_PIPE128,
+            _hip.MI_GEMM16_PIPE256X128, _hip.MI_GEMM16_BIG) == (0, 1, 2, 3, 4, 5)
+    header = open(os.path.join(ROOT, "include", "mi_critic.h")).read()
+    for name in cases.VARIANTS:
+        assert re.search(rf"#define MI_GEMM16_{name} {getattr(_hip, 'MI_GEMM16_' + name)}\b", header), name
+    cases.check_table()
+    # the exact data of the GPU tests: exactness in bf16 is asserted inside, on the host
+    for name in ("plain", "pipe128"):
+        c = cases.exact_case(name)
+        assert c["s_all"].shape == (136 + cases.EXTRA,) * 2 and c["x"].shape == (136, cases.D_IMG)
+    assert cases.seam_ids(3336)[[3, 3335, 258, 3333]].tolist() == [2, 0, 254, 300]
+    assert cases.seam_ids(136)[[3, 135, 130]].tolist() == [2, 0, 126]
+

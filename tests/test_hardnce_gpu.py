@@ -262,7 +262,7 @@ def test_two_samples(dev, precision):
 
 
 # ------------------------------------------------------------------------------------------------ matrix entry
-@pytest.mark.parametrize("b", [1, 33, 65, 200])
+@pytest.mark.parametrize("b", [1, 33, 65, 200, 1000])
 @pytest.mark.parametrize("ids", ["unique", "dup"])
 def test_matrix_entry_support_and_values(dev, b, ids):
     from mutual_info_img_txt import hard_negatives as hn

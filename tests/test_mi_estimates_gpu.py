@@ -92,7 +92,7 @@ def _matrix_call(s, sid, taus, fill=float("nan")):
 
 
 @pytest.mark.parametrize("pattern", ["unique", "dup", "all_equal"])
-@pytest.mark.parametrize("b", [1, 9, 72, 200, 256])
+@pytest.mark.parametrize("b", [1, 9, 72, 200, 256, 1100])
 def test_matrix_estimates(b, pattern):
     from mutual_info_img_txt.mi_estimates import ESTIMATE_NAMES, matrix_mi_estimates
     gen = torch.Generator().manual_seed(500 + b)
@@ -114,7 +114,7 @@ def test_matrix_estimates(b, pattern):
     assert out["dv"].untyped_storage().data_ptr() == out["smile"].untyped_storage().data_ptr()
 
 
-@pytest.mark.parametrize("b", [9, 200])
+@pytest.mark.parametrize("b", [9, 200, 1100])
 def test_matrix_estimates_without_taus(b):
     gen = torch.Generator().manual_seed(600 + b)
     s = (torch.randn(b, b, generator=gen) * 2.0).float()

@@ -274,7 +274,7 @@ def test_single_sample_is_exactly_zero(dev, precision):
 
 
 # ------------------------------------------------------------------------------------------------ matrix entry
-@pytest.mark.parametrize("b", [1, 3, 64, 130])
+@pytest.mark.parametrize("b", [1, 3, 64, 130, 1000])
 @pytest.mark.parametrize("scale", [3.0, 80.0])
 def test_matrix_entry_vs_restatement_and_torch(dev, b, scale):
     from mutual_info_img_txt import _hip, critic_ops, mi_critics, study_positives as sp

@@ -40,6 +40,11 @@ def dev():
     return torch.device("cuda:0")
 
 
+def softnce_max_labels():
+    from mutual_info_img_txt import _hip
+    return _hip.MI_SOFTNCE_MAX_LABELS
+
+
 def _masks(b, kind):
     """int64 [b] label masks of a pattern; None where the pattern does not fit the batch."""
     gen = torch.Generator().manual_seed(1000 + b)
@@ -57,8 +62,10 @@ def _masks(b, kind):
     if kind == "far":             # identical sets at (i, i + 70) only: the heavy off-diagonal weights lie outside the
         if b < 71:                # diagonal tiles
             return None
-        m = rnd.clone()
-        m[70:] = m[:b - 70]
+        m = rnd.clone()           # (b > 140: in pairs of 70-blocks, so that each set still has one partner, 70 away)
+        n = torch.arange(b)
+        second = (n // 70) % 2 == 1
+        m[second] = rnd[n[second] - 70]
         return m
     if kind == "group5":          # identical sets at indices 62 .. 66: straddles a tile edge
         if b < 67:
@@ -66,7 +73,9 @@ def _masks(b, kind):
         m = rnd.clone()
         m[62:67] = m[62]
         return m
-    if kind == "study":           # one bit per group of three samples
+    if kind == "study":           # one bit per group of three samples: fits the 63 label bits up to b = 189
+        if b > 3 * softnce_max_labels():
+            return None
         return torch.ones(b, dtype=torch.int64) << (torch.arange(b, dtype=torch.int64) // 3)
     raise ValueError(kind)
 
@@ -315,7 +324,17 @@ def test_single_sample_is_exactly_zero(dev, precision):
 
 
 # ------------------------------------------------------------------------------------------------ matrix entry
-@pytest.mark.parametrize("b", [1, 3, 64, 130])
+def _row_sum_floor(b, smax):
+    """What the fp32 r_i alone contributes to a row sum of dL/dS, on top of the elementwise 2e-5 * max|grad|.  The
+    backward reads r_i as the fp32 number the forward stored, off the exact log-sum-exp by d_i, so in exact arithmetic
+    the row sums to (exp(-d_i) - 1) / B = -d_i / B, not to 0.  d_i is held to 2e-6 * max(1, |S|max) by this test's own
+    lse_rows figure (and cannot be below half an ulp of r_i, 4.8e-7 at r = 10), while max|grad| falls like 1 / B^2: at
+    B = 1000 no fp32 r_i meets 2e-5 * max|grad| alone (measured there: row sum 1.2e-9 = 1.2e-6 / B, 9.7 x that figure).
+    The batches up to 130 meet the elementwise figure without this term and keep it as it was."""
+    return 2e-6 * smax / b if b > 130 else 0.0
+
+
+@pytest.mark.parametrize("b", [1, 3, 64, 130, 1000])
 @pytest.mark.parametrize("scale", [3.0, 80.0])
 def test_matrix_entry_vs_restatement_and_torch(dev, b, scale):
     from mutual_info_img_txt import _hip, critic_ops, soft_targets as st
@@ -341,8 +360,9 @@ def test_matrix_entry_vs_restatement_and_torch(dev, b, scale):
                 _close(g, o["grad"], 2e-5 * gmax, what=f"{what} grad")
                 if est == "infonce_rowwise":     # each row's share of dL/dS sums to zero
                     rows = g.double().sum(dim=1).abs().max()
-                    print(f"softnce-err {what} row sums {float(rows) / (2e-5 * float(g.abs().max()) + 1e-300):.3f}")
-                    assert float(rows) <= 2e-5 * float(g.abs().max()), what
+                    row_tol = 2e-5 * float(g.abs().max()) + _row_sum_floor(b, smax)
+                    print(f"softnce-err {what} row sums {float(rows) / (row_tol + 1e-300):.3f}")
+                    assert float(rows) <= row_tol, what
                 # the public autograd path against torch's own logsumexp route on the device
                 sl = sd.clone().requires_grad_(True)
                 l2, stats = st.matrix_soft_target_infonce(sl, masks, tau=tau, mix=mix, symmetric=est == "infonce_symmetric",
